@@ -2,6 +2,7 @@
 """bench.py — training throughput of the contrastive hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp16|fp32] [--batch B_per_gpu]
+                    [--dump-outputs DIR]   (the last timed step's outputs as DIR/<name>.npy, for build-to-build comparison)
 
 One step = BrainEncoder forward + CLIPLoss + top-k ranks + backward + (N > 1: gradient all-reduce) + Adam
 on one synthetic Gwilliams2022-shaped batch (208 sensors x 360 samples, 27 subjects, F = 1024,
@@ -65,7 +66,13 @@ def parse_args():
     ap.add_argument("--no-host-sync-leg", action="store_true", help="skip the extra loop that reads loss/ranks back every step")
     ap.add_argument("--coll-timer-steps", type=int, default=0, help="N > 1: extra steps (after the timed region) with HIP-event "
                     "brackets around every collective; adds `collectives_us_per_step` to the JSON line")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed region, write what its LAST step computed "
+                    "as DIR/<name>.npy (rank 0): loss, retrieval ranks, brain embedding Z, updated parameters and their gradients; "
+                    "arrays larger than the sample size are a fixed, seeded sample of their elements (see dump_outputs)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def spawn_ranks(a):
@@ -79,6 +86,47 @@ def spawn_ranks(a):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     return subprocess.call(cmd, env=env)
+
+
+# ----------------------------------------------------------------------------------------------- output dump
+DUMP_Z_SAMPLE = 1 << 21          # elements of Z written (8 MB in fp32); Z itself is B x F x T
+DUMP_PARAM_SAMPLE = 1 << 16      # elements written per parameter / gradient larger than this
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_sample(t, n_max: int, name: str):
+    """Flat float32 (float64 stays float64) copy of `t` on the host; above n_max elements a seeded sample of them: the same
+    indices in every run of every build (seeded by the array's name and size only), sorted, drawn with replacement."""
+    import zlib
+    import torch
+    t = t.detach()
+    if t.is_complex():
+        t = torch.view_as_real(t)
+    t = t.reshape(-1)
+    if t.numel() > n_max:
+        g = torch.Generator().manual_seed(zlib.crc32(f"{name}/{t.numel()}".encode()))
+        idx = torch.randint(0, t.numel(), (n_max,), generator=g).sort().values
+        t = t[idx.to(t.device)]
+    return t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+
+
+def dump_outputs(path: str, loss, ranks, Z, named_params) -> None:
+    """What a caller of the timed step holds after its last step: the loss, the retrieval ranks (Classifier semantics), the
+    encoder's output Z, and every parameter after the optimiser step together with the gradient it was stepped with."""
+    import numpy as np
+    arrays = {"loss": np.asarray([float(loss.detach())], dtype=np.float64),
+              "ranks": _dump_sample(ranks, DUMP_Z_SAMPLE, "ranks"),
+              "Z": _dump_sample(Z, DUMP_Z_SAMPLE, "Z")}
+    for n, p in named_params:
+        arrays[f"param.{n}"] = _dump_sample(p, DUMP_PARAM_SAMPLE, f"param.{n}")
+        if p.grad is not None:
+            arrays[f"grad.{n}"] = _dump_sample(p.grad, DUMP_PARAM_SAMPLE, f"grad.{n}")
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total / 2 ** 20:.1f} MB (limit {DUMP_LIMIT_BYTES >> 20} MB)")
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 # ----------------------------------------------------------------------------------------------- CPU baseline
@@ -297,6 +345,8 @@ def main():
     # instead of the forward's two and a half.  The loss keeps two packed buffers in rotation for exactly this overlap.
     ahead = dp and not a.no_prefetch_ahead
     primed = [False]
+    dump_at = a.warmup + a.steps - 1 if a.dump_outputs else -1  # index of the last timed step: its Z is kept for --dump-outputs
+    kept = {}
 
     def step(i, host_sync=False, batch=None, after_forward=None):
         if batch is None:
@@ -307,6 +357,8 @@ def main():
         if not (ahead and primed[0]) or batch is not None:
             lossf.prefetch(Y, enc.compute_dtype)             # pack Y (+ all-gather it under DP) while the encoder runs
         Z = enc(X, subj)
+        if i == dump_at:
+            kept["Z"] = Z
         loss = lossf(Y, Z)
         cnt = sda_loss.retrieval_ranks(Y, Z)                 # Classifier semantics (train.py:193-194)
         if ahead and batch is None:
@@ -366,6 +418,10 @@ def main():
     ranks_acc.clear()
     dt, loss = timed(a.steps, a.warmup)                      # the contract number: K clean steps
     host_main = host_enqueue[0]
+    if a.dump_outputs and rank == 0:                         # before any later leg trains the parameters further
+        dump_outputs(a.dump_outputs, loss, ranks_acc[-1], kept.pop("Z"),
+                     list(enc.named_parameters()) + [("loss." + n, p) for n, p in lossf.named_parameters()])
+    kept.clear()
     cnt = torch.cat([c.to(dev) for c in ranks_acc[-3:]]).float()
     top10_train = float((cnt < 10).float().mean())           # on the batches the last three steps trained on (for reference)
     final_loss = float(loss.detach())

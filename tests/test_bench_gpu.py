@@ -95,3 +95,28 @@ def test_bench_emulated_world_config_and_feed_legs():
     assert out.returncode == 0, out.stderr[-3000:]
     (line,) = _json_lines(out.stdout)
     assert line["with_feed"]["value"] > 0 and line["with_feed"]["host_enqueue_ms_per_step"] > 0
+
+
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's loss, ranks, Z (seeded sample) and every parameter / gradient as .npy files in
+    float32 / float64, at most 64 MB in all; the loss file is the step whose loss the JSON line reports."""
+    import numpy as np
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--batch", "32",
+           "--no-kernel-timer", "--no-host-sync-leg", "--no-feed-leg", "--dump-outputs", str(out_dir)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    (line,) = _json_lines(out.stdout)
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    files = {f[:-4]: np.load(out_dir / f) for f in os.listdir(out_dir)}
+    assert all(f.endswith(".npy") for f in os.listdir(out_dir))
+    assert sum(v.nbytes for v in files.values()) <= 64 << 20
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in files.values())
+    assert abs(float(files["loss"][0]) - line["final_loss"]) <= 1e-4
+    assert files["Z"].shape == (1 << 21,)                              # 32 x 1024 x 360 elements: the seeded sample
+    r = files["ranks"]
+    assert r.shape == (32,) and (r >= 0).all() and (r < 32).all()
+    params = [k for k in files if k.startswith("param.")]
+    assert "param.conv_final2.weight" in params and "param.loss.temp" in params
+    assert "grad.conv_final2.weight" in files and "grad.loss.temp" in files
+    assert all("param." + k[len("grad."):] in files for k in files if k.startswith("grad."))

@@ -305,3 +305,21 @@ def test_feed_rank_shards_union_to_the_single_process_batch(monkeypatch):
         rec = np.concatenate([parts[0][b][0], parts[1][b][0]])
         on = np.concatenate([parts[0][b][1], parts[1][b][1]])
         assert rec.tolist() == ref[b][0].tolist() and on.tolist() == ref[b][1].tolist()
+
+
+def test_bench_dump_sample_is_seeded_and_bounded():
+    """bench.py --dump-outputs: arrays above the sample size are written as the same seeded sample in every run (so two builds
+    compare element for element), smaller ones whole; integer and complex inputs come out as float32."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    t = torch.randn(3, 1000, 7)
+    a, b = bench._dump_sample(t, 4096, "Z"), bench._dump_sample(t.clone(), 4096, "Z")
+    assert a.dtype == np.float32 and a.shape == (4096,) and np.array_equal(a, b)
+    assert np.isin(a, t.numpy().reshape(-1)).all()
+    assert not np.array_equal(a, bench._dump_sample(t, 4096, "param.other"))        # each array has a sample of its own
+    small = torch.arange(10, dtype=torch.int32)
+    assert np.array_equal(bench._dump_sample(small, 4096, "ranks"), np.arange(10, dtype=np.float32))
+    assert bench._dump_sample(torch.ones(5, dtype=torch.float64), 4096, "x").dtype == np.float64
+    assert bench._dump_sample(torch.ones(4, dtype=torch.complex64), 4096, "c").shape == (8,)
