@@ -84,94 +84,27 @@ class EncoderEngine:
         self._seg_cache: Dict[tuple, tuple] = {}
         self._gen = 0                        # generation of the TRAIN workspace (bumped by grad-mode forwards only)
         self.reuse_workspace = True
-        self.fuse_bn_backward_stats = True   # BatchNorm-backward sums in the data-gradient conv's epilogue
         self.wgrad_target_wgs = 256          # workgroups per weight-gradient launch (split over sample segments)
         # weight-gradient chains (wgrad_gemm -> reduce_slabs -> unpack) depend only on dy and a saved
         # activation, never on each other or on the data-gradient chain: run them on a second HIP stream
-        self.wgrad_flat_rows = True          # shared-weight gradients contract a segment's rows as one run (pad rows of dy are zero)
         self.wgrad_side_stream = True
-        self.wgrad_reduce_stream = False     # the K-split slab sums behind every weight-gradient GEMM (HBM-bound, 17 launches, 0.36 ms
-                                             # of the weight-gradient stream's 3.5 ms in the step) on a THIRD stream, so that the
-                                             # next GEMM does not queue behind them: measured 7.06-7.10 vs 6.99-7.07 ms (and 0.4 ms
-                                             # more host time per step for the extra events) — off
         self.side_stream_priority = 0        # HIP stream priority of the weight-gradient / packing stream
         self.probe = None                    # diagnostics (tools/stream_waits.py): a list collects (label, event, event) around
                                              # every point where the main stream waits for another stream
         self.pack_on_side_stream = True      # per-step operand packing runs beside the first layers, not in front
-        self.forward_pair_tiles = True       # forward k = 3 convs (nothing competes for the CU's LDS there): two
-                                             # tiles per workgroup share each weight slab — fewer LDS-DMA bytes per FLOP
         self.flat_tiles_forward = True       # k = 3 convs on the 256-row flat-tile kernel (conv3_flat.hip) where it applies
         self.flat_tiles_forward_fp32 = True  # ... for fp32 storage as well (round 5: the fp32 instantiation runs 128-row tiles only —
                                              # 80 accumulator registers per wave, no scratch; round 4's 256-row form spilled ~300
                                              # registers into its K loop and the exact path went back to the tile kernel)
-        self.flat_tile_options = 1024        # extra conv3_flat flags: 1024 = the second workgroup of a CU takes its 128-row tile FIRST
-                                             # (the pair's epilogues — HBM bursts with the matrix pipe idle — fall at different
-                                             # times: 68.6 -> 67.3 us per 320 -> 320 conv with the priority hand-over, round 4),
-                                             # 64 = no priority hand-over between the two (diagnostic)
         self.fuse_glu_forward = True         # F.glu in conv2's epilogue (flat-tile kernel, D2p % 80 == 0): no [value | gate] buffer
-        self.bias_sums_at_end = False        # ... all of them at the END of backward, on the weight-gradient stream (round 5: seven
-                                             # ~10 us launches leave the main chain — and lengthen the serial tail the optimiser
-                                             # waits for: 6.72-6.75 against 6.64-6.68 ms, three alternations; off)
-        self.bias_sums_on_side = False       # final reduction of the bias-gradient column sums on the weight-gradient stream
-                                             # (round 3: on; re-measured in round 4 against the same library, three alternations on
-                                             # one box: 7.15-7.20 ms on, 7.09-7.14 ms off — the short reductions delay the
-                                             # weight-gradient GEMMs queued behind them more than they cost the main stream)
         self.fuse_glu_backward = False       # the GLU backward in the epilogue of the conv that produces its incoming gradient
-                                             # (needs the fused forward: bufs hold (out, gate)); not with flat-tile data gradients.
-                                             # Off: measured 7.87 vs 7.77 ms — the separate pass is HBM-bound and runs beside the
-                                             # weight-gradient stream's MFMA work for free, the heavier conv epilogue does not
+                                             # (needs the fused forward: bufs hold (out, gate)).  Off: measured 7.87 vs 7.77 ms —
+                                             # the separate pass is HBM-bound and runs beside the weight-gradient stream's MFMA
+                                             # work for free, the heavier conv epilogue does not
         self.tail_products_on_side = True    # composed SubjectBlock backward: the parameter-space products only the optimiser reads
                                              # (subj_w, sb_w, sb_b) on the weight-gradient stream, off the chain to dz
-        self.subj_wgrad_target_wgs = 0       # workgroups of the PER-SUBJECT weight-gradient launches (0 = wgrad_target_wgs): more
-                                             # slices per subject even out the subjects' unequal sample counts
-        self.skip_x0_gradient = True         # composed SubjectBlock: its weight gradient straight from block 0's dh0 and X (kernel-3
-                                             # per-subject weight gradient + chain rule) instead of conv0's data gradient + dx0 (x) X
         self.compose_subject_block = True    # SpatialAttention, the shared 1x1 conv and the per-subject 1x1 conv as ONE per-subject
                                              # matrix (needs a spare padding channel for the folded bias: C < Cp)
-        # backward keeps the 128-row tile kernel (40 KB of LDS per workgroup): the flat kernel's two 76 KB workgroups fill a
-        # CU's LDS, the weight-gradient GEMMs of the side stream then wait for the conv instead of running beside it
-        # (measured in the step: +2 %; with one flat workgroup per CU: +7 %)
-        self.flat_tiles_backward = False
-        self.flat_backward_one_per_cu = False
-        # the 1x1 projections (conv_final1/2) on conv1_flat.hip's 256-row flat tiles: forward (conv_final2 then leaves per-row
-        # partial sums of squares instead of per-tile statistics for ||Z_b||^2), and their data gradients — conv_final2's with
-        # the GELU backward of conv_final1 and its bias-gradient column sums in the epilogue (SDA_EPI_GELU_BWD: no
-        # gelu_backward_colsum pass over the 640-wide gradient)
-        self.bn_backward_store_dg = False    # the data-gradient convs that feed a BatchNorm+GELU backward store dg = dy * GELU'(u) (which
-                                             # their statistics epilogue computes anyway) instead of dy: the pass that applies the
-                                             # BatchNorm backward does not evaluate GELU' again (SDA_EPI_BN_STORE_DG).  Off: worth
-                                             # 0.02 ms of 7.16 (that pass is HBM-bound either way), and the extra rounding of dg to
-                                             # bf16 moves the conv2 bias gradients — almost cancelling sums over 92 160 rows — from
-                                             # under to over their 6e-2 parity bound at the full batch (7.7e-2)
-        self.fuse_gelu_backward_1x1 = False  # conv_final2's data gradient applies conv_final1's GELU backward in its epilogue and keeps
-                                             # the bias-gradient column sums (SDA_EPI_GELU_BWD): no pass over the 640-wide gradient.
-                                             # Off: measured 7.10 vs 7.04 ms — like the GLU backward below, the separate pass is
-                                             # HBM-bound and runs beside the weight-gradient stream for free; vector work added to an
-                                             # MFMA kernel's epilogue takes the matrix pipe's issue slots
-        # (measured twice: with the step on torch's default stream neither paid — 7.15-7.21 vs 7.16 ms; with the step's chain on
-        #  a high-priority stream (streams.py), where a flat kernel gets the CUs it wants when it wants them, the backward pair
-        #  is worth 0.10 ms — 6.77-6.87 vs 6.91-6.92, three alternations — and the forward pair nothing: 6.80-6.87 with both)
-        self.flat_1x1_forward = False
-        self.flat_1x1_backward = True
-        # round 5: conv1_wide.hip's 256-row x 256 / 320-channel tiles (eight waves, one persistent workgroup per CU, the next
-        # tile's K-steps requested before the epilogue of the current one; 16-bit storage, widths that are multiples of 256 or
-        # 320).  Alone at config 2 (tools/probes/bench_1x1_wide.py, us, tile / flat / wide): conv_final2 forward 246 / 253 / 216,
-        # conv_final1 forward 105 / 106 / 106, conv_final2's data gradient 211 / 180 / 180, conv_final1's 60 / 46 / 58.  In the
-        # step: conv_final2 forward on it (nothing co-runs in forward; -0.03 ms, inside the noise of an alternation); the data
-        # gradients on it +0.2 ms (one 160 KB workgroup per CU: the weight-gradient GEMMs wait instead of running beside them)
-        self.wide_1x1_forward = True         # conv_final2's forward (widths that are multiples of 256)
-        self.wide_1x1_forward_all = False    # ... conv_final1's as well (320-channel tiles: equal to the tile kernel)
-        self.wide_1x1_backward = False
-        self.dgrad_wave_priority = True      # the backward's tile-kernel data gradients at s_setprio 3 (SDA_CONV_WAVE_PRIO): with the
-                                             # HBM-bound passes of the chain raised as well (elementwise.hip, SDA_EW_BWD_PRIO) the
-                                             # step's chain wins each SIMD's issue arbitration against the weight-gradient GEMMs it
-                                             # runs beside: 6.725 against 6.771 ms, six alternations (either one alone: nothing)
-        self.flat_1x1_options = 0            # extra conv1_flat flags (1024 = staggered tile order, 32768 = one workgroup per CU)
-        # CU partition for backward (experiment, default off): k > 0 gives the data-gradient chain (the stream backward() is
-        # called on hands over to a CU-masked stream) k of the 8 XCDs and the weight-gradient stream the other 8 - k, instead
-        # of letting the two streams' workgroups compete for every CU (hipExtStreamCreateWithCUMask)
-        self.cu_partition_xcds = 0
-        self._part = {}
         self._side = {}
         self._const = {}                     # persistent operand buffers (composed SubjectBlock matrices)
 
@@ -355,7 +288,7 @@ class EncoderEngine:
             # (sized by the subjects PRESENT in the batch: a batch drawn from a few recordings — 8 of 27 subjects — otherwise
             # runs the launch on a third of its workgroups: +0.3 ms per step, measured with the resident feed in round 5)
             present = max(1, int(np.unique(sidx).size))
-            r = int(max(1, min(max(1, B // present), round((self.subj_wgrad_target_wgs or self.wgrad_target_wgs) / max(1, ntiles * present)))))
+            r = int(max(1, min(max(1, B // present), round(self.wgrad_target_wgs / max(1, ntiles * present)))))
             perm, seg = subject_segments(sidx, d.S, r)
             ctx.subj_perm = up("subj_perm", perm, dev)
             ctx.subj_seg = up("subj_seg", seg, dev)
@@ -394,9 +327,10 @@ class EncoderEngine:
             composed = self.composed
             Xt = rows("Xt", d.Cp)
             ops.pack_rows(X, Xt, ones_channel=d.C if composed else None)
-        k3_flags = L.CONV_PAIR_TILES if self.forward_pair_tiles else 0
+        # forward k = 3 convs (nothing competes for the CU's LDS there): two tiles per workgroup share each weight slab
+        k3_flags = L.CONV_PAIR_TILES
         if self.flat_forward:
-            k3_flags |= L.CONV_FLAT_TILES | self.flat_tile_options
+            k3_flags |= L.CONV_FLAT_TILES | 1024     # 1024: a CU's second workgroup takes its 128-row tile first (staggered epilogues)
 
         # ---- SubjectBlock (models.py:111-117)
         bufs["Xt"] = Xt
@@ -492,20 +426,18 @@ class EncoderEngine:
 
         # ---- two 1x1 projections with GELU (models.py:194-195)
         u1, g1 = rows("u1", d.F1p), rows("g1", d.F1p)
-        f_flags = (L.CONV_FLAT_TILES | self.flat_1x1_options) if self.flat_1x1_forward else 0
-        wide_ok = lambda cp: dt != torch.float32 and (cp % 256 == 0 or cp % 320 == 0)      # noqa: E731
-        f1_flags = L.CONV_WIDE_TILES if (self.wide_1x1_forward_all and wide_ok(d.F1p)) else f_flags
-        f2_wide = bool(self.wide_1x1_forward and dt != torch.float32 and d.Fp % 256 == 0)
+        # conv_final2 on conv1_wide.hip's 256-row tiles where its width allows (16-bit storage, Fp % 256 == 0)
+        f2_wide = dt != torch.float32 and d.Fp % 256 == 0
         ops.conv_gemm(x, pk["f1w"], g1, B=B, T=T, KS=1, dil=0, bias=pk["f1b"], y_pre=u1 if need_grad else None,
-                      gelu=True, alg_dims=(d.D2, d.F1), flags=f1_flags)
+                      gelu=True, alg_dims=(d.D2, d.F1))
         # Z is handed to the caller: a FRESH buffer per forward (the reference returns a new tensor each call), so
         # embeddings kept across forwards stay valid; everything else lives in the reused workspace
         u2, Zt = rows("u2", d.Fp), ops.new_rows_uninit(B, T, d.Fp, dt, dev)
         # ||Z_b||^2 for the loss comes out of the epilogue's sums: no separate pass over Z (loss.py:65)
-        if f2_wide or (f_flags and d.Fp % 128 == 0):
+        if f2_wide:
             zparts = torch.empty((B * L.rows_tp(T), d.Fp // 128), dtype=torch.float32, device=dev)
             ops.conv_gemm(g1, pk["f2w"], Zt, B=B, T=T, KS=1, dil=0, bias=pk["f2b"], y_pre=u2 if need_grad else None,
-                          gelu=True, row_sumsq=zparts, alg_dims=(d.F1, d.F), flags=L.CONV_WIDE_TILES if f2_wide else f_flags)
+                          gelu=True, row_sumsq=zparts, alg_dims=(d.F1, d.F), flags=L.CONV_WIDE_TILES)
             ops.ROW_NORMS.put(Zt, ops.rows_sumsq_from_row_parts(zparts, B, T))
         else:
             zstats = torch.empty((B * ops.n_t_tiles(T), 2, d.Fp), dtype=torch.float32, device=dev)
@@ -519,64 +451,12 @@ class EncoderEngine:
         return ctx
 
     # ------------------------------------------------------------------ backward
-    def _partition_streams(self, dev, k: int):
-        """(main, side, main_cus): two CU-masked streams.  Bit i of a mask is CU (i // 8) of XCD (i % 8) — the runtime deals
-        consecutive indices round-robin to the XCDs, and an XCD whose share of the mask is EMPTY runs unrestricted
-        (tools/probes/cumask_probe.py: masks `i % 8 < 1` and `i % 8 < 4` change nothing, `i < 128` halves every XCD) — so a
-        partition is a subset of every XCD's CUs: the first k / 8 of each XCD's 32 (k = 5: 20 CUs x 8 XCDs) against the rest.
-        k = 8 + m (diagnostic): both streams unrestricted."""
-        key = (str(dev), k)
-        if key not in self._part:
-            cus = torch.cuda.get_device_properties(dev).multi_processor_count
-            per_xcd = cus // 8
-            bits_a = [1 if (i // 8) < (per_xcd * k) // 8 else 0 for i in range(cus)]
-            if k >= 8:
-                bits_a = [1] * cus
-            if k == 9:        # (diagnostic) the same hand-over on two ordinary streams
-                self._part[key] = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev), cus)
-                return self._part[key]
-            streams = []
-            for bits in (bits_a, [1 - b for b in bits_a] if k < 8 else bits_a):
-                words = [sum(bits[32 * w + j] << j for j in range(32) if 32 * w + j < cus) for w in range((cus + 31) // 32)]
-                streams.append(torch.cuda.ExternalStream(ops.stream_create_cumask(words), device=dev))
-            self._part[key] = (streams[0], streams[1], sum(bits_a))
-        return self._part[key]
-
     def backward(self, P: Dict[str, torch.Tensor], ctx: EncoderCtx, dZt: torch.Tensor) -> Dict[str, torch.Tensor]:
-        k = int(self.cu_partition_xcds)
-        if not (0 < k <= 9 and self.wgrad_side_stream):
-            return self._backward(P, ctx, dZt)
-        dev = dZt.device
-        outer = torch.cuda.current_stream(dev)
-        main_p, side_p, main_cus = self._partition_streams(dev, k)
-        ev = torch.cuda.Event()
-        ev.record(outer)
-        main_p.wait_event(ev)
-        saved_side = self._side.get(str(dev))
-        self._side[str(dev)] = side_p
-        old_limit = L.load().sda_set_cu_limit(main_cus)          # persistent grids launched below size themselves for the partition
-        try:
-            with torch.cuda.stream(main_p):
-                grads = self._backward(P, ctx, dZt)
-                done = torch.cuda.Event()
-                done.record(main_p)
-        finally:
-            L.load().sda_set_cu_limit(old_limit)
-            if saved_side is not None:
-                self._side[str(dev)] = saved_side
-            else:
-                self._side.pop(str(dev), None)
-        # (no record_stream: blocks allocated on main_p are consumed on `outer` strictly behind `done`, and the next backward's
-        # main_p work starts behind an event of `outer` — record_stream would only make the allocator hold them back)
-        outer.wait_event(done)
-        return grads
-
-    def _backward(self, P: Dict[str, torch.Tensor], ctx: EncoderCtx, dZt: torch.Tensor) -> Dict[str, torch.Tensor]:
         if ctx.gen != self._gen and self.reuse_workspace:
             raise L.SdaError("the activation workspace of this forward was overwritten by a later forward of the same "
                              "encoder; call backward before the next training-mode forward, or set "
                              "engine.reuse_workspace = False")
-        d, dt = self.d, self.dtype
+        d = self.d
         B, T, bufs = ctx.B, ctx.T, ctx.bufs
         dev = dZt.device
         if getattr(ctx, "packed_T_ready", None) is not None:
@@ -605,10 +485,6 @@ class EncoderEngine:
                         f.record_stream(side)
                 pending.append(dist.all_reduce(b, op=dist.ReduceOp.SUM, group=side_group("grads", self.group), async_op=True))
                 return b
-            if red is not None:                   # the weight gradients of this group come from the slab-sum stream
-                ev = torch.cuda.Event()
-                ev.record(red)
-                side.wait_event(ev)
             bucket = on_side(pack_and_reduce)
             off = 0
             for n, f in zip(names, flats):
@@ -645,21 +521,11 @@ class EncoderEngine:
                 t.record_stream(main)
             return out
 
-        red = None
-        if side is not None and self.wgrad_reduce_stream:
-            red = self._side.get(str(dev) + "/reduce")
-            if red is None:
-                red = self._side[str(dev) + "/reduce"] = torch.cuda.Stream(device=dev)
-
         def join_side():
             if side is not None:
                 ev = torch.cuda.Event()
                 ev.record(side)
                 self._wait("weight-gradient stream joined", main, ev)
-            if red is not None:
-                ev = torch.cuda.Event()
-                ev.record(red)
-                self._wait("slab-sum stream joined", main, ev)
 
         def wgrad(dy, x, KS, dil, Cout, Cin, **glu):
             Cout_p, Cin_p = dy.shape[1], x.shape[1]
@@ -668,22 +534,14 @@ class EncoderEngine:
 
             def chain():
                 slabs = ops.wgrad_gemm(dy, x, B=B, T=T, KS=KS, dil=dil, perm=perm, seg_start=seg, nseg=nseg,
-                                       alg_dims=(Cin, Cout), flat_rows=self.wgrad_flat_rows)
-                if red is None:
-                    return ops.reduce_unpack_wgrad(slabs, Cout, Cin, KS, **glu)
-                ev = torch.cuda.Event()
-                ev.record(side)
-                red.wait_event(ev)
-                with torch.cuda.stream(red):
-                    out = ops.reduce_unpack_wgrad(slabs, Cout, Cin, KS, **glu)
-                slabs.record_stream(red)
-                return out
+                                       alg_dims=(Cin, Cout), flat_rows=True)
+                return ops.reduce_unpack_wgrad(slabs, Cout, Cin, KS, **glu)
             return on_side(chain)
 
         ntile = B * ops.n_t_tiles(T)
 
         W0cat = None
-        if ctx.composed is not None and self.skip_x0_gradient:
+        if ctx.composed is not None:
             # block 0's conv0 weights as [d][tap][o] (o zero-padded to D2p; the padding is written once), the left operand of the
             # composed SubjectBlock's gradient at the END of backward: a parameter-only copy, so it is made here, on the
             # weight-gradient stream while that has nothing to do, not in the serial tail of the step
@@ -707,21 +565,22 @@ class EncoderEngine:
             reduction pass over (out, h) is not needed.  glu_bwd = (x_out, gate) of the block BELOW: the conv's output is
             the gradient entering that block's F.glu, and the epilogue writes the GLU backward [d value | d gate] into `out`
             (twice as wide) plus the per-tile column sums of both halves (second value) instead of the gradient itself."""
-            bflags = (L.CONV_FLAT_TILES | (L.CONV_ONE_PER_CU if self.flat_backward_one_per_cu else 0)) if (self.flat_tiles_backward and KS == 3) else 0
-            if self.dgrad_wave_priority and not bflags:
-                bflags |= L.CONV_WAVE_PRIO
+            # (the 128-row tile kernel, 40 KB of LDS per workgroup: the flat kernel's two 76 KB workgroups fill a CU's LDS and the
+            # weight-gradient GEMMs of the side stream wait instead of running beside it; at s_setprio 3, so that the chain wins
+            # each SIMD's issue arbitration against those GEMMs)
+            bflags = L.CONV_WAVE_PRIO
             if glu_bwd is not None:
                 st = torch.empty((ops.conv_stats_rows(B, T, KS, Cin_p, 0), 2, Cin_p), dtype=torch.float32, device=dev)
                 ops.conv_gemm(dy, ctx.packed_T[key], out, B=B, T=T, KS=KS, dil=dil, res=res, widx=widx, stats=st, glu_bwd=glu_bwd,
                               alg_dims=(w_fp32.shape[-3], w_fp32.shape[-2]))
                 return out, st
-            if bn is None or not self.fuse_bn_backward_stats or bn[1] is None:
+            if bn is None or bn[1] is None:
                 return ops.conv_gemm(dy, ctx.packed_T[key], out, B=B, T=T, KS=KS, dil=dil, res=res, widx=widx,
                                      alg_dims=(w_fp32.shape[-3], w_fp32.shape[-2]), flags=bflags), None
             st = torch.empty((ops.conv_stats_rows(B, T, KS, out.shape[1], bflags), 2, out.shape[1]), dtype=torch.float32, device=dev)
             ops.conv_gemm(dy, ctx.packed_T[key], out, B=B, T=T, KS=KS, dil=dil, res=res, widx=widx, stats=st,
                           bn_x=bn[0], bn_coef=bn[1], alg_dims=(w_fp32.shape[-3], w_fp32.shape[-2]),
-                          flags=bflags | (L.EPI_BN_STORE_DG if self.bn_backward_store_dg else 0))
+                          flags=bflags)
             return out, st
 
         def bias_grad(cs, C, glu_half=0, glu_half_p=0):
@@ -732,68 +591,33 @@ class EncoderEngine:
             return ops.unpack_vector(cs, C, glu_half, glu_half_p)
 
         # ---- final projections
-        # the last stage of a bias gradient (partial rows -> column sums) feeds nothing on the main stream: it goes to the
-        # weight-gradient stream, each launch with partial rows of its own
-        deferred_sums = []                    # (gradient name, finish closure): final reductions postponed to the end of backward
-
-        def colsum_on_side(fn, *args, width, then=None, name=None):
-            """Column sums of fn's output; `then` (the bias-gradient un-packing, where it needs a kernel) runs on the SAME
-            stream as the sums' final reduction, right behind it: on the main stream it would read them before they exist.
-            bias_sums_at_end: the partial rows are kept and the final reduction of every bias gradient runs once, on the
-            weight-gradient stream behind its last GEMM — seven ~10 us launches leave the main chain (nothing on it reads a bias
-            gradient); not under overlapped gradient all-reduces, which want each layer group's gradients as they appear."""
-            if name is not None and side is not None and self.bias_sums_at_end and not overlap:
-                finish = fn(*args, B, T, ops.reduce_scratch(width, dev), defer=True)
-                deferred_sums.append((name, (lambda: then(finish())) if then is not None else finish))
-                return None
-            if side is None or not self.bias_sums_on_side:
-                cs = fn(*args, B, T, scratch)
-                return then(cs) if then is not None else cs
-            finish = fn(*args, B, T, ops.reduce_scratch(width, dev), defer=True)
-            return on_side((lambda: then(finish())) if then is not None else finish)
-
-        def finish_deferred_sums():
-            if not deferred_sums:
-                return
-            def run():
-                return [fin() for _, fin in deferred_sums]
-            outs = on_side(run)
-            for (nm, _), g_ in zip(deferred_sums, outs):
-                grads[nm] = g_
-
         du2 = tmp("du2", d.Fp)
-        grads["f2b"] = colsum_on_side(ops.gelu_backward_colsum, bufs["u2"], dZt, du2, width=d.Fp, then=lambda cs: bias_grad(cs, d.F), name="f2b")
-        b1_flags = (L.CONV_FLAT_TILES | self.flat_1x1_options) if self.flat_1x1_backward else 0
-        wide_ok = lambda cp: dt != torch.float32 and (cp % 256 == 0 or cp % 320 == 0)      # noqa: E731
-        b2_flags = b1_flags                   # conv_final2's data gradient (width F1p) / conv_final1's (width D2p)
-        if self.wide_1x1_backward and wide_ok(d.F1p):
-            b2_flags = L.CONV_WIDE_TILES
-        b1w_flags = L.CONV_WIDE_TILES if (self.wide_1x1_backward and wide_ok(d.D2p)) else b1_flags
+        grads["f2b"] = bias_grad(ops.gelu_backward_colsum(bufs["u2"], dZt, du2, B, T, scratch), d.F)
+        # the 1x1 data gradients on conv1_flat.hip's 256-row flat tiles
         du1 = tmp("du1", d.F1p)
-        if self.fuse_gelu_backward_1x1 or (b2_flags & L.CONV_WIDE_TILES) or (b1_flags and (d.F1p % 160 == 0 or d.F1p % 128 == 0)):
+        if d.F1p % 160 == 0 or d.F1p % 128 == 0:
             # conv_final2's data gradient with conv_final1's GELU backward in its epilogue: du1 directly, plus per-unit column sums
-            gst = torch.empty((ops.conv_stats_rows(B, T, 1, d.F1p, b2_flags | L.EPI_GELU_BWD), 2, d.F1p), dtype=torch.float32, device=dev)
+            gst = torch.empty((ops.conv_stats_rows(B, T, 1, d.F1p, L.CONV_FLAT_TILES | L.EPI_GELU_BWD), 2, d.F1p),
+                              dtype=torch.float32, device=dev)
             ops.conv_gemm(du2, ctx.packed_T["f2w"], du1, B=B, T=T, KS=1, dil=0, gelu_bwd_u=bufs["u1"], stats=gst,
-                          alg_dims=(d.F, d.F1), flags=b2_flags)
+                          alg_dims=(d.F, d.F1), flags=L.CONV_FLAT_TILES)
             grads["f2w"] = wgrad(du2, bufs["g1"], 1, 0, d.F, d.F1)
             grads["f1b"] = on_side(lambda: bias_grad(ops.reduce_stats(gst)[:d.F1p], d.F1))
         else:
             dg1, _ = dgrad(du2, "f2w", P["f2w"], d.Fp, d.F1p, tmp("dg1", d.F1p), 1, 0)
             grads["f2w"] = wgrad(du2, bufs["g1"], 1, 0, d.F, d.F1)
-            grads["f1b"] = colsum_on_side(ops.gelu_backward_colsum, bufs["u1"], dg1, du1, width=d.F1p, then=lambda cs: bias_grad(cs, d.F1), name="f1b")
+            grads["f1b"] = bias_grad(ops.gelu_backward_colsum(bufs["u1"], dg1, du1, B, T, scratch), d.F1)
         # Where the forward kept (out, gate) of every F.glu, the conv that produces the gradient entering a block's GLU (this
         # 1x1 data gradient for block 4, conv0's data gradient of block k + 1 for block k) applies the GLU backward in its
         # epilogue: `glu_pending` = (dc2, per-tile column sums) for the block about to be processed, and dx is never stored
-        glu_in_epilogue = bool(ctx.glu_fused and self.fuse_glu_backward and not self.flat_tiles_backward)
+        glu_in_epilogue = bool(ctx.glu_fused and self.fuse_glu_backward)
         glu_pending = None
         if glu_in_epilogue:
             glu_pending = dgrad(du1, "f1w", P["f1w"], d.F1p, d.D2p, tmp("dc2.4", 2 * d.D2p), 1, 0, glu_bwd=(bufs["x5"], bufs["b4.g"]))
             dx = None
         else:
-            if b1w_flags:
-                dx = ops.conv_gemm(du1, ctx.packed_T["f1w"], tmp("dxA", d.D2p), B=B, T=T, KS=1, dil=0, alg_dims=(d.F1, d.D2), flags=b1w_flags)
-            else:
-                dx, _ = dgrad(du1, "f1w", P["f1w"], d.F1p, d.D2p, tmp("dxA", d.D2p), 1, 0)
+            dx = ops.conv_gemm(du1, ctx.packed_T["f1w"], tmp("dxA", d.D2p), B=B, T=T, KS=1, dil=0, alg_dims=(d.F1, d.D2),
+                               flags=L.CONV_FLAT_TILES)
         grads["f1w"] = wgrad(du1, bufs["x5"], 1, 0, d.F1, d.D2)
         flush(["f2w", "f2b", "f1w", "f1b"])
 
@@ -814,8 +638,7 @@ class EncoderEngine:
             else:
                 dc2 = tmp(f"dc2.{k}", 2 * d.D2p)      # per-layer buffers: a side-stream wgrad may still read them
                 if ctx.glu_fused:
-                    grads[f"b{k}.c2b"] = colsum_on_side(ops.glu_backward_colsum_og, bufs[f"x{k + 1}"], bufs[f"b{k}.g"], dx, dc2,
-                                                        width=2 * d.D2p, then=c2b, name=f"b{k}.c2b")
+                    grads[f"b{k}.c2b"] = c2b(ops.glu_backward_colsum_og(bufs[f"x{k + 1}"], bufs[f"b{k}.g"], dx, dc2, B, T, scratch))
                 else:
                     grads[f"b{k}.c2b"] = c2b(ops.glu_backward_colsum(bufs[f"b{k}.c2"], dx, dc2, B, T, scratch))
             da1, tstats = dgrad(dc2, f"b{k}.c2w", P[f"b{k}.c2w"], 2 * d.D2p, d.D2p, tmp("da", d.D2p), 3, dil[2],
@@ -834,8 +657,7 @@ class EncoderEngine:
                 sync = self.group is not None and ctx.training
                 dgam, dbet = ops.bn_gelu_backward(da1, bufs[f"b{k}.h{j}"], mean, rstd, P[bnp + "w"], P[bnp + "b"], dh, B, T,
                                                   scratch, count=float(B) * T * world if ctx.training else float("inf"),
-                                                  allreduce=self._allreduce if sync else None, tile_stats=tstats,
-                                                  dy_is_dg=bool(self.bn_backward_store_dg and tstats is not None))
+                                                  allreduce=self._allreduce if sync else None, tile_stats=tstats)
                 # under DP the sums are already global on every rank; the gradient all-reduce (SUM) follows
                 if sync:
                     # (one launch for both rows, on the weight-gradient stream: only the optimiser reads these)
@@ -852,7 +674,7 @@ class EncoderEngine:
                 grads[f"b{k}.c{j}b"] = null_bias[2 * k + j] if ctx.training else bias_grad(ops.colsum(dh, B, T, scratch), d.D2)
                 res = dh if (j == 1 or k > 0) else None
                 out = tmp("da", d.D2p) if j == 1 else tmp("dxB" if flip == 0 else "dxA", ci_p)
-                if k == 0 and j == 0 and ctx.composed is not None and self.skip_x0_gradient:
+                if k == 0 and j == 0 and ctx.composed is not None:
                     # the composed SubjectBlock takes its weight gradient straight from dh0 and X (below): the gradient with
                     # respect to x0 is never needed, this data-gradient conv is not run
                     da1, tstats, dh0 = None, None, dh
@@ -870,14 +692,6 @@ class EncoderEngine:
                    f"b{k}.c0w", f"b{k}.c0b", f"b{k}.bn0w", f"b{k}.bn0b"])
 
         # ---- SubjectBlock
-        dhs = dx                                            # (rows, D1p)
-        def subj_wgrad():
-            r = ctx.subj_slices
-            slabs = ops.wgrad_gemm(dhs, bufs["h_c"], B=B, T=T, KS=1, dil=0, perm=ctx.subj_perm, seg_start=ctx.subj_seg,
-                                   nseg=r * d.S, flat_rows=self.wgrad_flat_rows)   # (r*S, 1, D1p, D1p), slice-major
-            if r > 1:
-                slabs = ops.reduce_slabs(slabs.view(r, -1)).view(d.S, 1, d.D1p, d.D1p)
-            return ops.unpack_conv_wgrad(slabs, d.S, d.D1, d.D1, 1, d.D1p, d.D1p)
         if ctx.composed is not None:
             Wd, T1aug, Ws = ctx.composed
             r = ctx.subj_slices
@@ -885,20 +699,13 @@ class EncoderEngine:
             #   dL/dW_tot[s] = sum_tap W0[tap]^T M[s][tap],   M[s][tap] = sum_{b in s, t} dh0[b, t] (x) X[b, t + (tap - 1) dil]
             # = the per-subject kernel-3 weight gradient of (dh0, X) followed by one batched (D1 x 3 D2) . (3 D2 x C+1) product:
             # neither conv0's data gradient (a 320 -> 320 kernel-3 conv) nor a weight gradient over dx0 is computed.
-            if self.skip_x0_gradient:
-                M = ops.wgrad_gemm(dh0, bufs["Xt"], B=B, T=T, KS=3, dil=block_dilations(0)[0], perm=ctx.subj_perm,
-                                   seg_start=ctx.subj_seg, nseg=r * d.S, flat_rows=self.wgrad_flat_rows)     # (r*S, 3, D2p, Cp); column C: the folded bias
-                if r > 1:
-                    M = ops.reduce_slabs(M.view(r, -1))
-                if w0cat_ready is not None:
-                    self._wait("W0cat copy (side stream)", main, w0cat_ready)
-                G = ops.param_gemm(W0cat.view(d.D1, 3 * d.D2p), M.view(d.S, 3 * d.D2p, d.Cp)[:, :, : d.C + 1])   # (S, D1, C + 1)
-            else:
-                slabs = ops.wgrad_gemm(dhs, bufs["Xt"], B=B, T=T, KS=1, dil=0, perm=ctx.subj_perm, seg_start=ctx.subj_seg,
-                                       nseg=r * d.S, flat_rows=self.wgrad_flat_rows)   # (r*S, 1, D1p, Cp): dL/dW_tot[s], column C = dL/db_tot[s]
-                if r > 1:
-                    slabs = ops.reduce_slabs(slabs.view(r, -1))
-                G = slabs.view(d.S, d.D1p, d.Cp)[:, : d.D1, : d.C + 1]                            # (S, D1, C + 1) view
+            M = ops.wgrad_gemm(dh0, bufs["Xt"], B=B, T=T, KS=3, dil=block_dilations(0)[0], perm=ctx.subj_perm,
+                               seg_start=ctx.subj_seg, nseg=r * d.S, flat_rows=True)     # (r*S, 3, D2p, Cp); column C: the folded bias
+            if r > 1:
+                M = ops.reduce_slabs(M.view(r, -1))
+            if w0cat_ready is not None:
+                self._wait("W0cat copy (side stream)", main, w0cat_ready)
+            G = ops.param_gemm(W0cat.view(d.D1, 3 * d.D2p), M.view(d.S, 3 * d.D2p, d.Cp)[:, :, : d.C + 1])   # (S, D1, C + 1)
             # The chain to the last gradient of the step is M -> G -> W_subj^T G -> dT1 -> dWd -> dz; the products that only
             # the optimiser reads (subj_w, sb_w, sb_b) leave it for the weight-gradient stream (tail_products_on_side)
             off_chain = on_side if self.tail_products_on_side else (lambda fn: fn())
@@ -913,11 +720,19 @@ class EncoderEngine:
             grads["z"] = ops.sa_weights_backward(dWd, ctx.W_sa, ctx.mask, P["cosT"], P["sinT"], P["z"].shape[1],
                                                  bwd_table=P.get("sa_tab_b"))
             flush(["subj_w", "sb_w", "sb_b", "z"])
-            finish_deferred_sums()
             join_side()
             for work in pending:
                 work.wait()
             return grads
+        dhs = dx                                            # (rows, D1p)
+
+        def subj_wgrad():
+            r = ctx.subj_slices
+            slabs = ops.wgrad_gemm(dhs, bufs["h_c"], B=B, T=T, KS=1, dil=0, perm=ctx.subj_perm, seg_start=ctx.subj_seg,
+                                   nseg=r * d.S, flat_rows=True)   # (r*S, 1, D1p, D1p), slice-major
+            if r > 1:
+                slabs = ops.reduce_slabs(slabs.view(r, -1)).view(d.S, 1, d.D1p, d.D1p)
+            return ops.unpack_conv_wgrad(slabs, d.S, d.D1, d.D1, 1, d.D1p, d.D1p)
         grads["subj_w"] = on_side(subj_wgrad)
         dh_c, _ = dgrad(dhs, "subj_w", P["subj_w"], d.D1p, d.D1p, tmp("dh_c", d.D1p), 1, 0, widx=ctx.widx)
         grads["sb_w"] = wgrad(dh_c, bufs["h_sa"], 1, 0, d.D1, d.D1)
@@ -930,7 +745,6 @@ class EncoderEngine:
         grads["z"] = ops.sa_weights_backward(dWd, ctx.W_sa, ctx.mask, P["cosT"], P["sinT"], P["z"].shape[1],
                                              bwd_table=P.get("sa_tab_b"))
         flush(["subj_w", "sb_w", "sb_b", "z"])
-        finish_deferred_sums()
         join_side()
         for work in pending:
             work.wait()                       # makes the current stream wait for RCCL's; no host sync

@@ -36,7 +36,7 @@ def run(dtype, d, P, X, Y, subj, streams: bool, dp: bool):
     lossf.global_negatives = dp
     e = enc.engine
     assert (e.group is not None) == dp
-    e.wgrad_side_stream = e.pack_on_side_stream = e.bias_sums_on_side = streams
+    e.wgrad_side_stream = e.pack_on_side_stream = streams
     sda_loss.PREFETCH_ON_SIDE_STREAM = streams
     params = list(enc.parameters()) + list(lossf.parameters())
     opt = FusedAdam(params, lr=3e-4)
