@@ -531,6 +531,11 @@ class EncoderEngine:
             Cout_p, Cin_p = dy.shape[1], x.shape[1]
             tile_m = 160 if Cout_p % 160 == 0 else (128 if Cout_p % 128 == 0 else 64)
             perm, seg, nseg = self._uniform_segments(B, (Cout_p // tile_m) * (Cin_p // 64), dev)
+            if side is not None and not self.reuse_workspace:
+                # without the persistent workspace, dy is a buffer of this backward that is freed as soon as the loop moves on,
+                # and the next main-stream allocation may take its memory before the side stream has read it
+                dy.record_stream(side)
+                x.record_stream(side)
 
             def chain():
                 slabs = ops.wgrad_gemm(dy, x, B=B, T=T, KS=KS, dil=dil, perm=perm, seg_start=seg, nseg=nseg,

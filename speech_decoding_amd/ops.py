@@ -93,10 +93,11 @@ class UploadCache:
     most of these tables repeat (one dropout mask per sensor; descriptor tables; recurring batches), so a hit
     returns the device tensor uploaded earlier and nothing is enqueued."""
 
-    def __init__(self, capacity: int = 1024):
+    def __init__(self, capacity: int = 1024, upload=None):
         import collections
         self.capacity = capacity
         self.items = collections.OrderedDict()
+        self._upload = upload or upload_small     # (array, device) -> tensor; the keying and eviction rules do not depend on it
 
     def upload(self, key, array, device) -> torch.Tensor:
         import numpy as np
@@ -106,7 +107,7 @@ class UploadCache:
         if hit is not None:
             self.items.move_to_end(k)
             return hit
-        dev = upload_small(array, device)
+        dev = self._upload(array, device)
         self.items[k] = dev
         if len(self.items) > self.capacity:
             self.items.popitem(last=False)
