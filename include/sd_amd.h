@@ -448,6 +448,21 @@ int sda_splitk_epilogue(const float* partial, int ksplit, const float* bias, con
 int sda_w2v_mean4(const void* a, const void* b, const void* c, const void* d, float* out, int T, int C, int Cp,
                   int dtype, void* stream);
 
+/* ---- MSELoss (speech_decoding/utils/loss.py:15-25): loss = sum_{b,f,t} (y - z)^2 / b_div.  Each operand is described by
+ * (pointer, cp, dtype): cp > 0 = a row-layout buffer of cp channels (a multiple of SDA_CH_ALIGN, >= F; both operands the same cp
+ * when both are row layout), cp = 0 = a plain contiguous (B, F, T) tensor.  Row-layout buffers 16-byte aligned.  Accumulation in
+ * fp32 per element run, fp64 across runs, a fixed reduction order: the same bits every call. ---- */
+#define SDA_MSE_PARTIALS 2048
+/* loss[0] fp32 = the sum / b_div (b_div: the batch size the mean divides by, the GLOBAL batch under data parallelism);
+ * scratch holds SDA_MSE_PARTIALS doubles */
+int sda_mse_forward(const void* z, int z_cp, int z_dtype, const void* y, int y_cp, int y_dtype, int B, int F, int T, int b_div,
+                    double* scratch, float* loss, void* stream);
+/* dz = 2 * (dloss[0] / b_div) * (z - y) in z's form and dtype, dy = -that in y's form and dtype (either may be NULL, not both;
+ * dloss is read on the device).  Row-layout outputs get every valid row, pad channels as zeros; their pad rows and slack are not
+ * touched (sda_zero_pad_rows) */
+int sda_mse_backward(const void* z, int z_cp, int z_dtype, const void* y, int y_cp, int y_dtype, int B, int F, int T, int b_div,
+                     const float* dloss, void* dz, void* dy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

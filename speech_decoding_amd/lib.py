@@ -131,7 +131,10 @@ SIGNATURES = {
     "sda_gather_samples": (i32, [vp, vp, vp, i32, i64, vp]),
     "sda_clip_merge_rows": (i32, [vp, i32, i32, vp, vp, vp]),
     "sda_copy3d": (i32, [vp, i64, i64, i64, vp, i64, i64, i64, i32, i32, i32, vp]),
+    "sda_mse_forward": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "sda_mse_backward": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
 }
+MSE_PARTIALS = 2048      # SDA_MSE_PARTIALS: doubles of sda_mse_forward's scratch
 
 _lib = None
 

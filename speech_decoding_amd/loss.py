@@ -5,6 +5,9 @@ Z (B, F, T); loss = (CE(logits) + CE(logitsᵀ)) / 2 with logits = x̂ ŷᵀ · 
 similarity GEMM, the softmax statistics, the gradient coefficient matrix and the embedding gradient
 all run in libsdamd.so.  Under torch.distributed (one process per GPU) the speech rows are all-gathered
 so the negatives span the GLOBAL batch; each rank owns the columns of its local brain embeddings.
+
+Also `MSELoss` (loss.py:15-25), the reference's regression objective, on the sda_mse_* kernels, and its two clamped helpers
+`torch_exp` / `torch_log` (loss.py:8-13, plain torch).
 """
 from __future__ import annotations
 
@@ -366,3 +369,91 @@ def retrieval_ranks(Y: torch.Tensor, Z: torch.Tensor, global_candidates: bool = 
         import torch.distributed as dist
         dist.all_reduce(cnt, group=group)
     return cnt[col0: col0 + B]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# MSELoss (speech_decoding/utils/loss.py:15-25) and the reference's two clamped helpers (loss.py:8-13)
+# ------------------------------------------------------------------------------------------------------------------------------
+def torch_exp(x: torch.Tensor) -> torch.Tensor:
+    """exp of x clamped from above at 10 (no overflow for large logits).  Plain torch, off the hot path."""
+    return torch.clamp(x, max=10.0).exp()
+
+
+def torch_log(x: torch.Tensor) -> torch.Tensor:
+    """log of x clamped from below at 1e-10 (finite at 0).  Plain torch, off the hot path."""
+    return torch.clamp(x, min=1e-10).log()
+
+
+def _mse_operand(t: torch.Tensor, B: int, F: int, T: int, name: str):
+    """(operand, is_rows): the row-layout buffer behind a rows_view (zero copy), else the plain tensor made contiguous."""
+    if t.dtype in ops.COMPUTE_DTYPES:
+        base = _rows_base(t, B, F, T, t.dtype)
+        if base is not None:
+            return base, True
+    if not t.is_cuda:
+        raise L.SdaError(f"MSELoss: {name} must live on the MI355X device (there is no CPU path)")
+    ops.dt_code(t.dtype)                      # fp32 / bf16 / fp16 only
+    return t.detach().contiguous(), False
+
+
+class _MseFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, module: "MSELoss", Y, Z):
+        if Y.dim() != 3 or tuple(Y.shape) != tuple(Z.shape):
+            raise ValueError(f"MSELoss: Y and Z must both be (B, F, T) of one shape, got {tuple(Y.shape)} and {tuple(Z.shape)}")
+        B, F, T = Z.shape
+        Zo, z_rows = _mse_operand(Z, B, F, T, "Z (brain embeddings)")
+        Yo, y_rows = _mse_operand(Y, B, F, T, "Y (speech embeddings)")
+        if Yo.device != Zo.device:
+            raise L.SdaError(f"MSELoss: Y is on {Yo.device}, Z on {Zo.device}")
+        group = _dist_group() if module.global_batch else None
+        B_global = B
+        if group is not None:
+            import torch.distributed as dist
+            B_global = B * dist.get_world_size(group)
+        # the local share sum_local / B_global: summed over ranks it is the global mean, and its gradient summed over ranks
+        # is the single-process gradient on the global batch
+        loss = ops.mse_forward(Zo, Yo, B, F, T, B_global)
+        if group is not None:
+            dist.all_reduce(loss.reshape(1), group=group)
+        ctx.set_materialize_grads(False)
+        ctx.operands = (Zo, z_rows, Yo, y_rows)
+        ctx.dims = (B, F, T, B_global)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        want_y, want_z = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if dloss is None or not (want_y or want_z):
+            return None, None, None
+        Zo, z_rows, Yo, y_rows = ctx.operands
+        B, F, T, B_global = ctx.dims
+
+        def new_grad(src, rows):
+            # a buffer of its own per backward; the kernel writes every valid row, pad channels included
+            return ops.new_rows_uninit(B, T, src.shape[1], src.dtype, src.device) if rows else torch.empty_like(src)
+
+        dZ = new_grad(Zo, z_rows) if want_z else None
+        dY = new_grad(Yo, y_rows) if want_y else None
+        ops.mse_backward(Zo, Yo, B, F, T, B_global, dloss.detach().to(torch.float32).reshape(1).contiguous(), dZ, dY)
+        if dZ is not None and z_rows:
+            dZ = ops.rows_view(dZ, B, F, T)
+        if dY is not None and y_rows:
+            dY = ops.rows_view(dY, B, F, T)
+        return None, dY, dZ
+
+
+class MSELoss(nn.Module):
+    """forward(Y, Z) = ((Y - Z) ** 2).sum(dim=(1, 2)).mean(): summed over features and time, averaged over the batch, as a
+    0-dim fp32 tensor.  Y (speech) and Z (brain) may each be an encoder output in row layout or a plain (B, F, T) tensor of
+    fp32 / bf16 / fp16; both get gradients when they require them.  Under torch.distributed with `global_batch` (the default)
+    the mean is over the GLOBAL batch: the forward returns it (one all-reduce), the backward gives this rank's share, so the
+    summed gradients are those of one process on the whole batch.  Shapes must match exactly (no broadcasting)."""
+
+    def __init__(self):
+        super().__init__()
+        L.load()
+        self.global_batch = True
+
+    def forward(self, Y, Z):
+        return _MseFn.apply(self, Y, Z)

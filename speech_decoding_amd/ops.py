@@ -204,6 +204,36 @@ def rows_sumsq(x: torch.Tensor, B: int, row_elems: int, pitch: int) -> torch.Ten
     return out
 
 
+def _mse_operand(t: torch.Tensor, B: int, F: int, T: int):
+    """(pointer, cp, dtype code) of an MSE operand: a row-layout buffer (rows_alloc, Cp) or a contiguous (B, F, T) tensor."""
+    _need_cuda(t)
+    if t.dim() == 2 and t.shape[0] >= L.rows_alloc(B, T) and t.is_contiguous():
+        return _p(t), t.shape[1], dt_code(t.dtype)
+    if tuple(t.shape) == (B, F, T) and t.is_contiguous():
+        return _p(t), 0, dt_code(t.dtype)
+    raise L.SdaError(f"mse: operand of shape {tuple(t.shape)} is neither a row-layout buffer nor a contiguous {(B, F, T)} tensor")
+
+
+def mse_forward(z: torch.Tensor, y: torch.Tensor, B: int, F: int, T: int, b_div: int) -> torch.Tensor:
+    """sum (y - z)^2 / b_div as a 0-dim fp32 device tensor; z, y: row-layout buffers or contiguous (B, F, T) tensors."""
+    zo, yo = _mse_operand(z, B, F, T), _mse_operand(y, B, F, T)
+    out = torch.empty((), dtype=torch.float32, device=z.device)
+    scratch = torch.empty(L.MSE_PARTIALS, dtype=torch.float64, device=z.device)
+    L.check(L.load().sda_mse_forward(*zo, *yo, B, F, T, b_div, _p(scratch), _p(out), _st()), "mse_forward")
+    return out
+
+
+def mse_backward(z: torch.Tensor, y: torch.Tensor, B: int, F: int, T: int, b_div: int, dloss: torch.Tensor,
+                 dz: Optional[torch.Tensor], dy: Optional[torch.Tensor]):
+    """dz = 2 (dloss / b_div) (z - y) in z's form and dtype, dy = -that in y's form and dtype (either may be None); dloss: one fp32
+    element on the device.  A row-layout output needs zeroed pad rows and slack (new_rows_uninit)."""
+    zo, yo = _mse_operand(z, B, F, T), _mse_operand(y, B, F, T)
+    for out, src in ((dz, z), (dy, y)):
+        if out is not None and (out.shape != src.shape or out.dtype != src.dtype or not out.is_contiguous()):
+            raise L.SdaError("mse_backward: a gradient must have its operand's shape, dtype and layout")
+    L.check(L.load().sda_mse_backward(*zo, *yo, B, F, T, b_div, _p(dloss), _p(dz), _p(dy), _st()), "mse_backward")
+
+
 def rows_sumsq_from_row_parts(parts: torch.Tensor, B: int, T: int) -> torch.Tensor:
     """Per-sample sum of squares from the per-row partial sums conv_gemm(row_sumsq=parts) wrote."""
     out = torch.empty(B, dtype=torch.float32, device=parts.device)

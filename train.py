@@ -8,6 +8,7 @@ reference's `train.py`, own implementation.
 
 What is kept from the reference loop (train.py:148-259):
   * models: BrainEncoder + Classifier + CLIPLoss, Adam over encoder parameters and the loss temperature;
+    `loss=mse` trains on MSELoss instead (the reference's regression objective; Adam over the encoder alone);
   * per batch: Z = encoder(X, subject_idxs); loss = CLIPLoss(Y, Z); top-1/top-10 from Classifier(Z, Y);
   * update cadence: Gwilliams2022 steps on every batch, Brennan2018 ONCE per epoch with the last batch's
     loss (train.py:200-209);
@@ -31,7 +32,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from speech_decoding.models import BrainEncoder, Classifier       # noqa: E402  (train.py:22 import path)
-from speech_decoding.utils.loss import CLIPLoss                    # noqa: E402  (train.py:24)
+from speech_decoding.utils.loss import CLIPLoss, MSELoss           # noqa: E402  (train.py:24)
 from speech_decoding_amd import load_config                        # noqa: E402
 from speech_decoding_amd.distributed import allreduce_gradients, broadcast_parameters, shard_range  # noqa: E402
 
@@ -128,10 +129,15 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
     if feeds_local_shards and "pack_resident_embeddings" in locals():
         pack_resident_embeddings.pack_embeddings(brain_encoder.compute_dtype)      # Y batches arrive as the loss's packed operand
     classifier = Classifier(args)
-    loss_func = CLIPLoss(args).to(device)
+    loss_kind = str(args.get("loss", "clip")).lower()
+    if loss_kind not in ("clip", "mse"):
+        raise ValueError(f"loss={loss_kind}: expected clip or mse")
+    clip = loss_kind == "clip"
+    loss_func = (CLIPLoss(args) if clip else MSELoss()).to(device)
     loss_func.train()
     broadcast_parameters(brain_encoder)
-    params = list(brain_encoder.parameters()) + list(loss_func.parameters())
+    # MSELoss has no parameters of its own: Adam steps the encoder alone
+    params = list(brain_encoder.parameters()) + (list(loss_func.parameters()) if clip else [])
     optimizer = torch.optim.Adam(params, lr=float(args.lr))
     wandb = None
     if args.get("use_wandb", False) and rank == 0:
@@ -152,7 +158,10 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
         optimizer.zero_grad()
         scaler.scale(loss).backward(gradient=one)
         if world > 1:        # (SUM of the still-scaled gradients: every rank then sees the same overflow, or none)
-            allreduce_gradients(list(loss_func.parameters()) if brain_encoder.grads_are_reduced else params)
+            if not brain_encoder.grads_are_reduced:
+                allreduce_gradients(params)
+            elif clip:       # the temperature's gradient; MSELoss has none
+                allreduce_gradients(list(loss_func.parameters()))
         # fp16 only: an activation gradient that overflowed to inf / NaN must not reach Adam — the finiteness check is a
         # host read-back per step of ONE device flag written by one fused launch (fp16 is configs[4]'s dtype; bf16 / fp32
         # never take it), the step is skipped and the scale halved (amp.LossScaler.update, GradScaler's rule).  A skipped
@@ -191,7 +200,7 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
         while ahead is not None:
             X, Y, subject_idxs = ahead
             ahead = next(batches, None)
-            if first:
+            if first and clip:
                 loss_func.prefetch(Y, brain_encoder.compute_dtype)
                 first = False
             Z = brain_encoder(X, subject_idxs)
@@ -203,7 +212,7 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
                 ranks = classifier.ranks(Z, Y)                   # Classifier.forward's ranks, kept on the device
             tr_loss.append(loss.detach())
             tr_ranks.append(ranks)
-            if ahead is not None:
+            if ahead is not None and clip:
                 loss_func.prefetch(ahead[1], brain_encoder.compute_dtype)
             if args.dataset == "Gwilliams2022":
                 backward_and_step(loss)
@@ -229,18 +238,21 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
         row = {"epoch": epoch, "train_loss": np.mean(tr_loss), "test_loss": np.mean(te_loss),
                "trainTop1acc": np.mean(tr_top1), "trainTop10acc": np.mean(tr_top10),
                "testTop1acc": np.mean(te_top1), "testTop10acc": np.mean(te_top10),
-               "lrate": optimizer.param_groups[0]["lr"], "temp": loss_func.temp.item()}
+               "lrate": optimizer.param_groups[0]["lr"]}
+        if clip:
+            row["temp"] = loss_func.temp.item()
         history.append(row)
         if rank == 0:
             log(f"Ep {epoch}/{args.epochs} | ", f"train l: {row['train_loss']:.3f} | ", f"test l: {row['test_loss']:.3f} | ",
                 f"trainTop10acc: {row['trainTop10acc']:.3f} | ", f"testTop10acc: {row['testTop10acc']:.3f} | ",
-                f"lr: {row['lrate']:.5f}", f"temp: {row['temp']:.3f}")
+                f"lr: {row['lrate']:.5f}", *([f"temp: {row['temp']:.3f}"] if clip else []))
             if wandb is not None:
                 wandb.log(row)
             torch.save(brain_encoder.state_dict(), "model_last.pt")
     if owns_group:                       # a group this function created is also ended here, in order (distributed.shutdown)
         from speech_decoding_amd.distributed import shutdown
-        loss_func.drain()
+        if clip:
+            loss_func.drain()
         shutdown()
     # hand the thread back on the stream it came with (everything queued on the training stream is waited for first)
     caller_stream.wait_stream(torch.cuda.current_stream(device))
