@@ -8,7 +8,7 @@
  *     speech_decoding/models.py:152-166  ConvBlock.forward             -> sda_conv_gemm, sda_bn_*, sda_glu_*
  *     speech_decoding/models.py:191-196  BrainEncoder.forward          -> sda_conv_gemm (GELU epilogue)
  *     speech_decoding/utils/loss.py:58-79 CLIPLoss.forward (fast path) -> sda_rows_sumsq, sda_conv_gemm (split-K),
- *                                                                         sda_clip_logits_stats, sda_clip_grad,
+ *                                                                         sda_clip_logits_stats, sda_clip_grad(_y),
  *                                                                         sda_wgrad_gemm (typed output)
  *     speech_decoding/models.py:208-248  Classifier.forward            -> sda_clip_ranks
  * and their autograd backward.  Every entry point takes plain device pointers, sizes and a
@@ -93,7 +93,9 @@ int sda_pack_rows(const float* src, void* dst, int B, int C, int T, int Cp, int 
 int sda_pack_rows_ones(const float* src, void* dst, int B, int C, int T, int Cp, int ones_channel, int dtype, void* stream);
 /* RL -> (B, C, T) fp32 contiguous */
 int sda_unpack_rows(const void* src, float* dst, int B, int C, int T, int Cp, int dtype, void* stream);
-/* (B, C, T) of `dtype`... not provided: gradients enter/leave in RL. */
+/* RL of `dtype` -> (B, C, T) contiguous of `dst_dtype` (fp32 / bf16 / fp16): the loss's speech-embedding gradient in the
+ * argument's own dtype (one rounding when dst_dtype is narrower than dtype) */
+int sda_unpack_rows_typed(const void* src, void* dst, int B, int C, int T, int Cp, int dtype, int dst_dtype, void* stream);
 
 /* per-sample sum of squares over an RL tensor viewed as B rows of `row_elems` contiguous elements with
  * pitch `pitch` (elements). out[b] fp32. `scratch` holds B*64 floats. */
@@ -350,6 +352,24 @@ int sda_clip_logits_stats(const float* S, long s_pitch, const float* ysq, const 
 int sda_clip_grad(const float* logits, const float* row_lse, const float* col_lse, const float* ysq,
                   const float* zsq, const float* temp, float inv_norm, int col0, void* G, long g_pitch,
                   float* rscale, float* cscale, float* colpart, float* scalars, int Bm, int Bn, int dtype, void* stream);
+/* The coefficients of the loss's gradient with respect to the SPEECH embeddings (the first argument), the dZ product with the
+ * two roles exchanged:  dY_i = cscale_y_i * sum_j Gy[j][i] * Z_j - rscale_y_i * Y_i.  On one logits block (rows = speech i,
+ * columns = this block's brain j; same logits / row_lse / col_lse / col0 as sda_clip_grad, D_ij from the same expression):
+ * Gy[j][i] = D_ij * zmax / |Z_j| as `dtype`, [Bn + 1][gy_pitch] with the row Bn and every unused column written as zeros;
+ * zmax = max over the nz norms zsq_all (all brain rows the dY GEMM contracts over: the gathered ones under data parallelism).
+ * Column c holds speech row (c / seg_pitch) * seg + c % seg (c % seg_pitch < seg; seg_pitch a multiple of 64, gy_pitch a
+ * multiple of seg_pitch): seg = Bm, seg_pitch = gy_pitch = pad64(Bm) on one GPU, one 64-aligned group per rank's rows under
+ * data parallelism.  part [ceil(Bn / 64)][Bm] fp32: per-row partial sums of D_ij * logits_ij over 64-column groups. */
+int sda_clip_grad_y(const float* logits, const float* row_lse, const float* col_lse, const float* zsq,
+                    const float* zsq_all, int nz, int col0, void* Gy, long gy_pitch, int seg, int seg_pitch,
+                    float* part, int Bm, int Bn, int dtype, void* stream);
+/* rows [row0, row0 + nrows) of the dY factors: rscale_y[r] = inv_norm * sum_p part[p][i] / |Y_i|^2 and cscale_y[r] = inv_norm *
+ * exp(temp) / (zmax |Y_i|), i = row0 + r, from nparts rows of [Bg] partials (the blocks of every rank in rank order, summed in
+ * that order: the same bits on every rank and every call).  Then sda_clip_dz(Gy, g_pitch, Z, Y, dY, cscale_y, rscale_y, ...)
+ * with Bm = the brain rows contracted over and Bn = nrows gives dY. */
+int sda_clip_grad_y_finish(const float* part, int nparts, int Bg, const float* ysq, const float* zsq_all, int nz,
+                           const float* temp, float inv_norm, int row0, int nrows, float* rscale_y, float* cscale_y,
+                           void* stream);
 /* The embedding gradient of the loss on one GPU as a streaming kernel (loss_gemm.hip):
  *     out[j][k] = out_scale[0] * (cscale[j] * sum_{i < Bm} G[i][j] * Y[i][k] - rscale[j] * Z[j][k]),   j < Bn, k < row_elems
  * G [Bm][g_pitch], Y [Bm][row_elems], Z and out [Bn][row_elems] of `dtype` (16-bit types only), cscale / rscale fp32 [Bn]

@@ -137,8 +137,8 @@ __global__ __launch_bounds__(256) void pack_rows_vec_kernel(const float* __restr
   }
 }
 
-template <typename E>
-__global__ __launch_bounds__(256) void unpack_rows_kernel(const E* __restrict__ src, float* __restrict__ dst,
+template <typename E, typename O = float>
+__global__ __launch_bounds__(256) void unpack_rows_kernel(const E* __restrict__ src, O* __restrict__ dst,
                                                           int C, int T, int Cp) {
   __shared__ float tile[64][65];
   const int b = blockIdx.z, c0 = blockIdx.y * 64, t0 = blockIdx.x * 64;
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void unpack_rows_kernel(const E* __restrict__ 
   __syncthreads();
   for (int cc = ty; cc < 64; cc += 4) {
     const int c = c0 + cc, t = t0 + tx;
-    if (c < C && t < T) dst[((size_t)b * C + c) * T + t] = tile[tx][cc];
+    if (c < C && t < T) Elem<O>::st(dst + ((size_t)b * C + c) * T + t, tile[tx][cc]);
   }
 }
 
@@ -1015,6 +1015,24 @@ extern "C" int sda_unpack_rows(const void* src, float* dst, int B, int C, int T,
   dim3 grid((T + 63) / 64, Cp / 64, B);
   SDA_DISPATCH(dtype, hipLaunchKernelGGL(unpack_rows_kernel<E>, grid, dim3(256), 0, st, (const E*)src, dst, C, T, Cp));
   return check_launch("unpack_rows");
+}
+
+// the same transpose into a (B, C, T) tensor of dst_dtype: one rounding where the stored value does not fit the output type
+extern "C" int sda_unpack_rows_typed(const void* src, void* dst, int B, int C, int T, int Cp, int dtype, int dst_dtype,
+                                     void* stream) {
+  if (!src || !dst || Cp % 64 || C > Cp || B < 1) { set_error("unpack_rows_typed: bad arguments"); return -1; }
+  hipStream_t st = (hipStream_t)stream;
+  dim3 grid((T + 63) / 64, Cp / 64, B);
+  if (dst_dtype == SDA_F32)
+    SDA_DISPATCH(dtype, hipLaunchKernelGGL((unpack_rows_kernel<E, float>), grid, dim3(256), 0, st, (const E*)src, (float*)dst, C, T, Cp));
+  else if (dst_dtype == SDA_BF16)
+    SDA_DISPATCH(dtype, hipLaunchKernelGGL((unpack_rows_kernel<E, uint16_t>), grid, dim3(256), 0, st, (const E*)src, (uint16_t*)dst, C,
+                                           T, Cp));
+  else if (dst_dtype == SDA_F16)
+    SDA_DISPATCH(dtype, hipLaunchKernelGGL((unpack_rows_kernel<E, half_t>), grid, dim3(256), 0, st, (const E*)src, (half_t*)dst, C, T,
+                                           Cp));
+  else { set_error("unpack_rows_typed: unknown output dtype %d", dst_dtype); return -1; }
+  return check_launch("unpack_rows_typed");
 }
 
 extern "C" int sda_rows_sumsq_from_stats(const float* stats, int tiles_per_sample, int Cp, float* out, int B, void* stream) {

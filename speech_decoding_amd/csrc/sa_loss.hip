@@ -241,6 +241,72 @@ __global__ __launch_bounds__(256) void clip_grad_kernel(const float* __restrict_
   }
 }
 
+// The speech-side twin of clip_grad_kernel: the coefficients of dY_i = cscale_y_i * sum_j Gy[j][i] Z_j - rscale_y_i Y_i.
+// One workgroup per (64 columns of Gy, 64 brain rows j): D_ij comes from the same expression on the same inputs as in
+// clip_grad_kernel (one softmax for dZ and dY), is scaled to its O(1) part  Gy[j][i] = D_ij * (zmax / |Z_j|)  and leaves
+// through an LDS transpose, so both the logits reads (along j) and the Gy writes (along i) are whole rows.  Column c of Gy
+// holds speech row i = (c / seg_pitch) * seg + c % seg (zero where c % seg_pitch >= seg or i >= Bm): one 64-aligned column
+// group per rank's rows under data parallelism, the plain layout (seg = Bm) on one GPU.  Row Bn is the zero row the dZ GEMM
+// family expects behind the contraction.  part[jt][i] = sum over the workgroup's j of D_ij * L_ij (ordered wave sums).
+template <typename E>
+__global__ __launch_bounds__(256) void clip_grad_y_kernel(const float* __restrict__ logits, const float* __restrict__ row_lse,
+                                                          const float* __restrict__ col_lse, const float* __restrict__ zsq,
+                                                          const float* __restrict__ zsq_all, int nz, int col0,
+                                                          E* __restrict__ Gy, long gy_pitch, int seg, int seg_pitch,
+                                                          float* __restrict__ part, int Bm, int Bn) {
+  __shared__ float sh[4];
+  __shared__ float tile[64][65];                   // [column of Gy][j]
+  const int c0 = blockIdx.x * 64, jt = blockIdx.y, j0 = jt * 64, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nparts = (Bn + 63) / 64;
+  float zmax2 = 0.f;
+  for (int k = tid; k < nz; k += 256) zmax2 = fmaxf(zmax2, zsq_all[k]);
+  const float zmax = sqrtf(block_max(zmax2, sh));
+  const int j = j0 + lane;
+  const bool jv = j < Bn;
+  const float cl = jv ? col_lse[j] : 0.f;
+  const float zf = jv ? zmax / sqrtf(zsq[j]) : 0.f;
+  for (int k = 0; k < 16; ++k) {
+    const int cc = w + 4 * k, c = c0 + cc, s = c / seg_pitch, o = c - s * seg_pitch, i = s * seg + o;
+    const bool iv = o < seg && i < Bm;             // (uniform over the wave)
+    float d = 0.f, dl = 0.f;
+    if (iv && jv) {
+      const float l = logits[(size_t)i * Bn + j];
+      d = expf(l - row_lse[i]) + expf(l - cl);
+      if (i == col0 + j) d -= 2.f;
+      dl = d * l;
+    }
+    tile[cc][lane] = d * zf;
+    dl = wave_sum(dl);
+    if (iv && jt < nparts && lane == 0) part[(size_t)jt * Bm + i] = dl;
+  }
+  __syncthreads();
+  for (int k = 0; k < 16; ++k) {
+    const int jj = w + 4 * k, jr = j0 + jj;
+    if (jr <= Bn) Elem<E>::st(Gy + (size_t)jr * gy_pitch + c0 + lane, jr < Bn ? tile[lane][jj] : 0.f);
+  }
+}
+
+// rows [row0, row0 + nrows) of the dY epilogue factors from the partials of sda_clip_grad_y: nparts rows of [Bg] floats, the
+// blocks of all ranks in rank order (world = 1 on one GPU), summed in that order — the same bits on every rank.
+__global__ __launch_bounds__(256) void clip_grad_y_finish_kernel(const float* __restrict__ part, int nparts, int Bg,
+                                                                 const float* __restrict__ ysq, const float* __restrict__ zsq_all,
+                                                                 int nz, const float* __restrict__ temp, float inv_norm,
+                                                                 int row0, int nrows, float* __restrict__ rscale_y,
+                                                                 float* __restrict__ cscale_y) {
+  __shared__ float sh[4];
+  const int tid = threadIdx.x, r = blockIdx.x * 256 + tid;
+  float zmax2 = 0.f;
+  for (int k = tid; k < nz; k += 256) zmax2 = fmaxf(zmax2, zsq_all[k]);
+  const float zmax = sqrtf(block_max(zmax2, sh));
+  if (r >= nrows) return;
+  const int i = row0 + r;
+  float s = 0.f;
+  for (int p = 0; p < nparts; ++p) s += part[(size_t)p * Bg + i];
+  const float dl = s * inv_norm;
+  rscale_y[r] = dl / ysq[i];
+  cscale_y[r] = inv_norm * expf(temp[0]) / (zmax * sqrtf(ysq[i]));
+}
+
 __global__ void clip_scalars_kernel(const float* __restrict__ colpart, float inv_norm, float* __restrict__ scalars, int Bn) {
   // one wave: lane-strided fp64 partial sums, then lane 0 adds the 64 partials in lane order (deterministic)
   __shared__ double pl[64], pd[64];
@@ -383,6 +449,41 @@ extern "C" int sda_clip_grad(const float* logits, const float* row_lse, const fl
   else { set_error("clip_grad: unknown dtype"); return -1; }
   hipLaunchKernelGGL(clip_scalars_kernel, dim3(1), dim3(64), 0, st, colpart, inv_norm, scalars, Bn);
   return check_launch("clip_grad");
+}
+
+extern "C" int sda_clip_grad_y(const float* logits, const float* row_lse, const float* col_lse, const float* zsq,
+                               const float* zsq_all, int nz, int col0, void* Gy, long gy_pitch, int seg, int seg_pitch,
+                               float* part, int Bm, int Bn, int dtype, void* stream) {
+  if (!logits || !row_lse || !col_lse || !zsq || !zsq_all || !Gy || !part || Bm < 1 || Bn < 1 || nz < Bn || seg < 1 ||
+      seg_pitch < seg || seg_pitch % 64 || gy_pitch < seg_pitch || gy_pitch % seg_pitch || (gy_pitch / seg_pitch) * seg < Bm) {
+    set_error("clip_grad_y: bad arguments (seg_pitch a multiple of 64, gy_pitch a multiple of seg_pitch covering Bm rows)");
+    return -1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)(gy_pitch / 64), (unsigned)(Bn / 64 + 1));
+  if (dtype == SDA_F32)
+    hipLaunchKernelGGL(clip_grad_y_kernel<float>, grid, dim3(256), 0, st, logits, row_lse, col_lse, zsq, zsq_all, nz, col0, (float*)Gy,
+                       gy_pitch, seg, seg_pitch, part, Bm, Bn);
+  else if (dtype == SDA_BF16)
+    hipLaunchKernelGGL(clip_grad_y_kernel<uint16_t>, grid, dim3(256), 0, st, logits, row_lse, col_lse, zsq, zsq_all, nz, col0,
+                       (uint16_t*)Gy, gy_pitch, seg, seg_pitch, part, Bm, Bn);
+  else if (dtype == SDA_F16)
+    hipLaunchKernelGGL(clip_grad_y_kernel<half_t>, grid, dim3(256), 0, st, logits, row_lse, col_lse, zsq, zsq_all, nz, col0,
+                       (half_t*)Gy, gy_pitch, seg, seg_pitch, part, Bm, Bn);
+  else { set_error("clip_grad_y: unknown dtype"); return -1; }
+  return check_launch("clip_grad_y");
+}
+
+extern "C" int sda_clip_grad_y_finish(const float* part, int nparts, int Bg, const float* ysq, const float* zsq_all, int nz,
+                                      const float* temp, float inv_norm, int row0, int nrows, float* rscale_y, float* cscale_y,
+                                      void* stream) {
+  if (!part || !ysq || !zsq_all || !temp || !rscale_y || !cscale_y || nparts < 1 || nz < 1 || nrows < 1 || row0 < 0 ||
+      row0 + nrows > Bg) {
+    set_error("clip_grad_y_finish: bad arguments"); return -1;
+  }
+  hipLaunchKernelGGL(clip_grad_y_finish_kernel, dim3((nrows + 255) / 256), dim3(256), 0, (hipStream_t)stream, part, nparts, Bg, ysq,
+                     zsq_all, nz, temp, inv_norm, row0, nrows, rscale_y, cscale_y);
+  return check_launch("clip_grad_y_finish");
 }
 
 extern "C" int sda_clip_ranks(const float* logits, const float* diag, int32_t* cnt, int Bm, int Bn, int col0, void* stream) {

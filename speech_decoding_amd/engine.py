@@ -791,6 +791,14 @@ class ClipCtx:
     row_elems: int
     dtemp: torch.Tensor
     cscale: Optional[torch.Tensor] = None     # per-column factor taken out of G (see sda_clip_grad): the dZ GEMM's acc_scale
+    # what the speech-side gradient (clip_backward_y) needs besides: the block's logits and softmax statistics, the norms
+    logits: Optional[torch.Tensor] = None
+    row_lse: Optional[torch.Tensor] = None
+    col_lse: Optional[torch.Tensor] = None
+    ysq: Optional[torch.Tensor] = None
+    zsq: Optional[torch.Tensor] = None
+    temp: Optional[torch.Tensor] = None
+    inv_norm: float = 0.0
 
 
 def clip_forward(Yt: torch.Tensor, Zt: torch.Tensor, temp: torch.Tensor, *, Bm: int, Bn: int, T: int, col0: int = 0,
@@ -855,10 +863,18 @@ def clip_block_finish(st: ClipBlockStats, row_lse, diag, *, reduction: str = "me
     G, rscale, cscale, scalars = ops.clip_grad(logits, row_lse, col_lse, ysq, zsq, temp, inv_norm, col0, Yt.dtype)
     cnt = ops.clip_ranks(logits, diag, col0)
     ctx = ClipCtx(Bm=Bm, Bn=Bn, col0=col0, G=G, rscale=rscale, Yt=Yt, Zt=Zt, row_elems=row_elems, dtemp=scalars[1:2],
-                  cscale=cscale)
+                  cscale=cscale, logits=logits, row_lse=row_lse, col_lse=col_lse, ysq=ysq, zsq=zsq, temp=temp, inv_norm=inv_norm)
     return scalars[0:1], logits, cnt, ctx
 
 
 def clip_backward(ctx: ClipCtx, dZt: torch.Tensor, dloss: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dZ = dloss * (diag(c) G^T Y - diag(r) Z)  (gradient of the loss share w.r.t. the local brain embeddings)."""
     return ops.clip_dz(ctx.G, ctx.Yt, ctx.Zt, dZt, ctx.rscale, ctx.cscale, Bm=ctx.Bm, Bn=ctx.Bn, row_elems=ctx.row_elems, out_scale=dloss)
+
+
+def clip_backward_y(ctx: ClipCtx, dYt: torch.Tensor, dloss: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dY = dloss * (diag(c_y) Gy^T Z - diag(r_y) Y) on one GPU (the block is the whole matrix): the dZ product with the roles of
+    the two embeddings exchanged, on the same GEMM family (no new GEMM kernel)."""
+    Gy, part = ops.clip_grad_y(ctx.logits, ctx.row_lse, ctx.col_lse, ctx.zsq, ctx.zsq, ctx.col0, ctx.Zt.dtype)
+    rscale_y, cscale_y = ops.clip_grad_y_finish(part, ctx.ysq, ctx.zsq, ctx.temp, ctx.inv_norm, 0, ctx.Bm)
+    return ops.clip_dz(Gy, ctx.Zt, ctx.Yt, dYt, rscale_y, cscale_y, Bm=ctx.Bn, Bn=ctx.Bm, row_elems=ctx.row_elems, out_scale=dloss)

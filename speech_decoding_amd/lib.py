@@ -73,6 +73,7 @@ SIGNATURES = {
     "sda_pack_rows": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "sda_pack_rows_ones": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "sda_unpack_rows": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "sda_unpack_rows_typed": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "sda_rows_sumsq": (i32, [vp, vp, vp, i32, i64, i64, i32, vp]),
     "sda_rows_sumsq_from_stats": (i32, [vp, i32, i32, vp, i32, vp]),
     "sda_rows_sumsq_from_row_parts": (i32, [vp, i32, vp, i32, i32, vp]),
@@ -119,6 +120,8 @@ SIGNATURES = {
     "sda_sa_weights_backward": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "sda_clip_logits_stats": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "sda_clip_grad": (i32, [vp, vp, vp, vp, vp, vp, f32, i32, vp, i64, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "sda_clip_grad_y": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, i64, i32, i32, vp, i32, i32, i32, vp]),
+    "sda_clip_grad_y_finish": (i32, [vp, i32, i32, vp, vp, i32, vp, f32, i32, i32, vp, vp, vp]),
     "sda_collate_rows": (i32, [vp, vp, i64, i32, i32, f32, i32, vp]),
     "sda_collate_windows": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
     "sda_clip_ranks": (i32, [vp, vp, vp, i32, i32, i32, vp]),

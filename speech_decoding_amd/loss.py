@@ -4,7 +4,8 @@ forward(x, y, fast=True, return_logits=False): x = speech embeddings Y (B, F, T)
 Z (B, F, T); loss = (CE(logits) + CE(logitsᵀ)) / 2 with logits = x̂ ŷᵀ · exp(temp).  The norms, the
 similarity GEMM, the softmax statistics, the gradient coefficient matrix and the embedding gradient
 all run in libsdamd.so.  Under torch.distributed (one process per GPU) the speech rows are all-gathered
-so the negatives span the GLOBAL batch; each rank owns the columns of its local brain embeddings.
+so the negatives span the GLOBAL batch; each rank owns the columns of its local brain embeddings.  Gradients reach x, y and
+temp, as in the reference; x's is computed only when x requires one.
 
 Also `MSELoss` (loss.py:15-25), the reference's regression objective, on the sda_mse_* kernels, and its two clamped helpers
 `torch_exp` / `torch_log` (loss.py:8-13, plain torch).
@@ -144,13 +145,15 @@ def _dist_group():
 
 
 def gather_speech_rows(Yt_local: torch.Tensor, B: int, T: int, group, async_op: bool = False,
-                       state: Optional[LossState] = None, slot: Optional[RingSlot] = None):
+                       state: Optional[LossState] = None, slot: Optional[RingSlot] = None, ring_key: str = "loss.Yall",
+                       sq: Optional[torch.Tensor] = None):
     """All-gather the packed speech rows of every rank (RCCL all_gather over xGMI; samples are contiguous
     blocks of Tp rows, so the gather lands directly in RL order) together with their squared norms (computed
-    once, on the rank that owns the rows).  Returns (Yt, ysq, Bm, col0, B_global, works, slot): `slot` is the ring
-    slot that owns the rows the backward will read (the local pack without a group, the gathered buffer with one)."""
+    once, on the rank that owns the rows, unless `sq` hands them in).  Returns (Yt, ysq, Bm, col0, B_global, works, slot):
+    `slot` is the ring slot that owns the rows the backward will read (the local pack without a group, the gathered buffer
+    with one).  The same helper gathers the brain rows for the speech-side gradient (ring_key "loss.Zall")."""
     row_elems = L.rows_tp(T) * Yt_local.shape[1]
-    ysq_local = ops.rows_sumsq(Yt_local, B, row_elems, row_elems)
+    ysq_local = sq if sq is not None else ops.rows_sumsq(Yt_local, B, row_elems, row_elems)
     if group is None:
         return Yt_local, ysq_local, B, 0, B, [], slot
     import torch.distributed as dist
@@ -159,7 +162,7 @@ def gather_speech_rows(Yt_local: torch.Tensor, B: int, T: int, group, async_op: 
     from .distributed import emulated_world
     if world == 1 and emulated_world() > 1:
         return _gather_emulated(Yt_local, ysq_local, B, T, group, emulated_world(), async_op, state or _DEFAULT_STATE)
-    slot = _ring_rows(state or _DEFAULT_STATE, "loss.Yall", B * world, Yt_local.shape[1], T, Yt_local.dtype, Yt_local.device)
+    slot = _ring_rows(state or _DEFAULT_STATE, ring_key, B * world, Yt_local.shape[1], T, Yt_local.dtype, Yt_local.device)
     Yt = slot.buf
     ysq = torch.empty(B * world, dtype=torch.float32, device=Yt_local.device)
     from .distributed import side_group
@@ -252,18 +255,34 @@ def _take_prefetched(state: LossState, Y, dtype):
     return None
 
 
+_RECYCLED = ("CLIPLoss.backward: the packed {what} rows of this forward were recycled by later forwards of the same CLIPLoss "
+             "(more than `ring_depth` forwards before this backward); raise loss_func._state.ring_depth or call backward earlier")
+
+
 class _ClipFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module: "CLIPLoss", Y, Z, temp):
         import torch.distributed as dist
         B, F, T = Z.shape
-        if Y.requires_grad:
-            raise L.SdaError("CLIPLoss: the speech embeddings (first argument) are data on this path and get no gradient "
-                             "(train.py:191 passes precomputed wav2vec2 features); detach them")
         dtype = Z.dtype if Z.dtype in ops.COMPUTE_DTYPES else torch.float32
         Zt = as_rows(Z, B, F, T, dtype, "y (brain embeddings)")
         group = _dist_group() if module.global_negatives else None
         state = module._state
+        want_y = ctx.needs_input_grad[1]            # (False under no_grad even for a leaf that requires a gradient)
+        y_rows = False
+        if want_y:
+            # the gradient leaves in the argument's own form: the row-layout buffer of a rows view in the compute dtype, else a
+            # (B, F, T) tensor of the argument's dtype
+            y_rows = _rows_base(Y, B, F, T, dtype) is not None
+            if not y_rows and not Y.is_cuda:
+                raise L.SdaError("CLIPLoss: x (speech embeddings) must live on the MI355X device (there is no CPU path)")
+            if not y_rows and Y.dtype not in ops.COMPUTE_DTYPES:
+                raise L.SdaError(f"CLIPLoss: a speech embedding that requires a gradient must be fp32, bf16 or fp16, got {Y.dtype}")
+            if group is not None and dist.get_world_size(group) == 1:
+                from .distributed import emulated_world
+                if emulated_world() > 1:
+                    raise L.SdaError("CLIPLoss: the emulated world (stand-in rows for the other ranks) has no gradient for the "
+                                     "speech embeddings; detach x or run real ranks")
         pre = _take_prefetched(state, Y, dtype)
         if pre is not None:
             Yt, ysq, Bm, col0, Bg, slot = pre
@@ -272,6 +291,13 @@ class _ClipFn(torch.autograd.Function):
             Yt, ysq, Bm, col0, Bg, _, slot = gather_speech_rows(Yt_local, B, T, group, state=state, slot=slot)
         loss, logits, cnt, cctx = E.clip_forward(Yt, Zt, temp.detach(), Bm=Bm, Bn=B, T=T, col0=col0,
                                                  reduction=module.reduction, B_global=Bg, dist_group=group, ysq=ysq)
+        ctx.z_gather = None
+        if want_y and group is not None:
+            # the speech-side gradient contracts over the brain rows of ALL ranks: gather them (and their norms) now, behind
+            # the rest of the step; backward waits for it
+            Zall, zsq_all, _, _, _, works, zslot = gather_speech_rows(Zt, B, T, group, async_op=True, state=state,
+                                                                      ring_key="loss.Zall", sq=cctx.zsq)
+            ctx.z_gather = (Zall, zsq_all, works, zslot)
         if group is not None:
             # one collective for both: the rank counts (exact in fp32) and the loss share -> global loss for
             # reporting (backward uses the local share)
@@ -282,6 +308,7 @@ class _ClipFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)            # no zero-filled gradient for the (non-differentiable) logits output
         ctx.y_slot = slot
         ctx.z_requires_grad = Z.requires_grad
+        ctx.y_requires_grad, ctx.y_rows, ctx.y_dtype = want_y, y_rows, Y.dtype
         _cache_ranks(Y, Z, cnt[col0: col0 + B])
         ctx.mark_non_differentiable(logits)
         return loss.reshape(()), logits
@@ -290,22 +317,58 @@ class _ClipFn(torch.autograd.Function):
     def backward(ctx, dloss, _dlogits):
         c = ctx.cctx
         B, F, T = ctx.shape
-        dZ = None
+        dZ = dY = None
         if dloss is None:                           # (the loss itself took no part in what was differentiated)
             return None, None, None, None
         scale = dloss.to(torch.float32)
+        if (ctx.z_requires_grad or ctx.y_requires_grad) and ctx.y_slot is not None and not ctx.y_slot.valid():
+            raise L.SdaError(_RECYCLED.format(what="speech"))
         if ctx.z_requires_grad:
-            if ctx.y_slot is not None and not ctx.y_slot.valid():
-                raise L.SdaError("CLIPLoss.backward: the packed speech rows of this forward were recycled by later forwards "
-                                 "of the same CLIPLoss (more than `ring_depth` forwards before this backward); raise "
-                                 "loss_func._state.ring_depth or call backward earlier")
             # a buffer of its own per backward (two pending backwards must not share one): the GEMM rewrites every sample's
             # rows, pad rows included (exact zeros), so only the slack behind the last sample needs a fill
             dZt = ops.new_rows_uninit(B, T, c.Zt.shape[1], ctx.dtype, c.Zt.device)
             E.clip_backward(c, dZt, scale.reshape(1).contiguous())     # dloss folded into the GEMM epilogue
             dZ = ops.rows_view(dZt, B, F, T)
+        if ctx.y_requires_grad:
+            dYt = _clip_dy(ctx, scale.reshape(1).contiguous())
+            dY = ops.rows_view(dYt, B, F, T) if ctx.y_rows else ops.unpack_rows_typed(dYt, B, F, T, ctx.y_dtype)
         dtemp = ops.scalar_mul(c.dtemp, scale.reshape(1))
-        return None, None, dZ, dtemp
+        return None, dY, dZ, dtemp
+
+
+def _clip_dy(ctx, scale: torch.Tensor) -> torch.Tensor:
+    """The speech-side gradient of this rank's own rows as a fresh row-layout buffer (the buffer contract of the encoder's
+    outputs: pad rows, slack and pad channels zero).  One process: engine.clip_backward_y.  Data parallelism: the coefficient
+    block of every rank is all-gathered (Gy rows of the brain samples, partial row sums), and this rank contracts its own
+    speech columns against the gathered brain rows — the rows one process would compute on the global batch."""
+    c = ctx.cctx
+    B, F, T = ctx.shape
+    dYt = ops.new_rows_uninit(B, T, c.Yt.shape[1], ctx.dtype, c.Yt.device)
+    if ctx.group is None:
+        E.clip_backward_y(c, dYt, scale)
+        return dYt
+    import torch.distributed as dist
+    from .distributed import side_group
+    world, rank = dist.get_world_size(ctx.group), dist.get_rank(ctx.group)
+    Zall, zsq_all, works, zslot = ctx.z_gather
+    for work in works:
+        work.wait()
+    if not zslot.valid():
+        raise L.SdaError(_RECYCLED.format(what="brain"))
+    Bg, sp = c.Bm, L.pad_channels(B)
+    Gy, part = ops.clip_grad_y(c.logits, c.row_lse, c.col_lse, c.zsq, zsq_all, c.col0, ctx.dtype, seg=B, seg_pitch=sp,
+                               groups=world)
+    Gall = torch.empty((Bg + 1, world * sp), dtype=ctx.dtype, device=Gy.device)
+    ops.fill_zero_(Gall[Bg])                        # the zero row behind the contraction
+    pall = torch.empty((world * part.shape[0], Bg), dtype=torch.float32, device=Gy.device)
+    bulk = side_group("gather", ctx.group)
+    dist.all_gather_into_tensor(Gall[:Bg], Gy[:B], group=bulk)
+    dist.all_gather_into_tensor(pall, part, group=bulk)
+    rscale_y, cscale_y = ops.clip_grad_y_finish(pall, c.ysq, zsq_all, c.temp, c.inv_norm, rank * B, B)
+    Yown = c.Yt[rank * B * L.rows_tp(T):]           # this rank's rows of the gathered speech buffer
+    ops.clip_dz(Gall[:, rank * sp:(rank + 1) * sp], Zall, Yown, dYt, rscale_y, cscale_y, Bm=Bg, Bn=B, row_elems=c.row_elems,
+                out_scale=scale)
+    return dYt
 
 
 class CLIPLoss(nn.Module):

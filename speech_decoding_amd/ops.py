@@ -143,6 +143,15 @@ def zeros(shape, dtype, device) -> torch.Tensor:
     return out
 
 
+def fill_zero_(t: torch.Tensor) -> torch.Tensor:
+    """Zero a contiguous device tensor in place (sda_fill_zero)."""
+    if not t.is_contiguous():
+        raise L.SdaError("fill_zero_: a contiguous tensor")
+    if t.numel():
+        L.check(L.load().sda_fill_zero(t.data_ptr(), t.numel() * t.element_size(), _st()), "fill_zero")
+    return t
+
+
 def gather_samples(table: torch.Tensor, idx: torch.Tensor, B: int, T: int) -> torch.Tensor:
     """table: row-layout buffer holding N samples back to back ((N * Tp [+ slack], Cp), pad rows zero); idx: B int64 sample
     indices on the device.  Returns a fresh row-layout buffer (rows_alloc(B, T), Cp) whose sample b is table sample idx[b]."""
@@ -194,6 +203,15 @@ def unpack_rows(src: torch.Tensor, B: int, Cc: int, T: int) -> torch.Tensor:
     _need_cuda(src)
     out = torch.empty((B, Cc, T), dtype=torch.float32, device=src.device)
     L.check(L.load().sda_unpack_rows(_p(src), _p(out), B, Cc, T, src.shape[1], dt_code(src.dtype), _st()), "unpack_rows")
+    return out
+
+
+def unpack_rows_typed(src: torch.Tensor, B: int, Cc: int, T: int, dtype) -> torch.Tensor:
+    """RL buffer -> a fresh contiguous (B, C, T) tensor of `dtype` (fp32 / bf16 / fp16), one HBM pass."""
+    _need_cuda(src)
+    out = torch.empty((B, Cc, T), dtype=dtype, device=src.device)
+    L.check(L.load().sda_unpack_rows_typed(_p(src), _p(out), B, Cc, T, src.shape[1], dt_code(src.dtype), dt_code(dtype), _st()),
+            "unpack_rows_typed")
     return out
 
 
@@ -702,13 +720,14 @@ def reduce_slabs(slabs: torch.Tensor) -> torch.Tensor:
 
 
 def matmul_tn_typed(G, Ym, out, sub, rscale, *, M_rows, N_valid, K_cols, pitch, out_scale=None, acc_scale=None):
-    """out[j][k] = out_scale * (acc_scale[j] * sum_i G[i][j] * Ym[i][k] - rscale[j] * sub[j][k])   (typed rows with `pitch`)."""
+    """out[j][k] = out_scale * (acc_scale[j] * sum_i G[i][j] * Ym[i][k] - rscale[j] * sub[j][k])   (typed rows with `pitch`).
+    G may be a column slice of a wider matrix: its row stride is the pitch read, its width the columns served."""
     a = L.WgradArgs()
     a.acc_scale = _p(acc_scale)
     a.dy, a.x, a.g, a.out_e, a.sub, a.rscale, a.out_scale = _p(G), _p(Ym), None, _p(out), _p(sub), _p(rscale), _p(out_scale)
     a.perm, a.seg_start = None, None
     a.nseg, a.B, a.T, a.Cout_p, a.Cin_p, a.KS, a.dil = 1, 1, M_rows, G.shape[1], K_cols, 1, 0
-    a.dy_pitch, a.x_pitch, a.out_pitch = G.shape[1], pitch, pitch
+    a.dy_pitch, a.x_pitch, a.out_pitch = G.stride(0), pitch, pitch
     if G.shape[0] < M_rows + 1:
         raise L.SdaError("matmul_tn_typed: G needs one trailing all-zero row")
     a.row0, a.sample_rows, a.rows_limit, a.dy_zero_row = 0, 0, M_rows, M_rows
@@ -719,9 +738,12 @@ def matmul_tn_typed(G, Ym, out, sub, rscale, *, M_rows, N_valid, K_cols, pitch, 
 
 def clip_dz(G, Yt, Zt, out, rscale, cscale, *, Bm, Bn, row_elems, out_scale=None):
     """out[j][k] = out_scale * (cscale[j] * sum_i G[i][j] Yt[i][k] - rscale[j] Zt[j][k]) — the loss's embedding gradient.
-    One GPU's shapes (Bm <= 256, 16-bit) run on the streaming kernel (loss_gemm.hip); anything else on wgrad_gemm's typed output."""
+    One GPU's shapes (Bm <= 256, 16-bit) run on the streaming kernel (loss_gemm.hip); anything else on wgrad_gemm's typed output.
+    G may be a column slice of a wider coefficient matrix (a rank's own speech columns of the all-gathered dY coefficients)."""
+    if G.stride(1) != 1:
+        raise L.SdaError("clip_dz: the coefficient matrix needs unit column stride")
     if L.load().sda_clip_dz_supported(Bm, Bn, row_elems, dt_code(Yt.dtype)):
-        L.check(L.load().sda_clip_dz(_p(G), G.shape[1], _p(Yt), _p(Zt), _p(out), _p(cscale), _p(rscale), _p(out_scale), Bm, Bn, row_elems,
+        L.check(L.load().sda_clip_dz(_p(G), G.stride(0), _p(Yt), _p(Zt), _p(out), _p(cscale), _p(rscale), _p(out_scale), Bm, Bn, row_elems,
                                      dt_code(Yt.dtype), _st()), "clip_dz")
         return out
     return matmul_tn_typed(G, Yt, out, Zt, rscale, M_rows=Bm, N_valid=Bn, K_cols=row_elems, pitch=row_elems, out_scale=out_scale,
@@ -806,6 +828,30 @@ def clip_grad(logits, row_lse, col_lse, ysq, zsq, temp, inv_norm, col0, dtype):
                                    _p(G), G.shape[1], _p(rscale), _p(cscale), _p(colpart), _p(scalars), Bm, Bn, dt_code(dtype), _st()),
             "clip_grad")
     return G, rscale, cscale, scalars
+
+
+def clip_grad_y(logits, row_lse, col_lse, zsq, zsq_all, col0, dtype, *, seg=None, seg_pitch=None, groups=1):
+    """Coefficients of the speech-side gradient on one logits block (sda_clip_grad_y): Gy [Bn + 1][groups * seg_pitch] of `dtype`
+    (column group g holds speech rows g * seg ... g * seg + seg - 1) and the per-row partials [ceil(Bn / 64)][Bm] fp32."""
+    Bm, Bn = logits.shape
+    seg = Bm if seg is None else seg
+    seg_pitch = L.pad_channels(seg) if seg_pitch is None else seg_pitch
+    dev = logits.device
+    Gy = torch.empty((Bn + 1, groups * seg_pitch), dtype=dtype, device=dev)     # every element is written by the kernel
+    part = torch.empty(((Bn + 63) // 64, Bm), dtype=torch.float32, device=dev)
+    L.check(L.load().sda_clip_grad_y(_p(logits), _p(row_lse), _p(col_lse), _p(zsq), _p(zsq_all), zsq_all.numel(), col0, _p(Gy),
+                                     Gy.shape[1], seg, seg_pitch, _p(part), Bm, Bn, dt_code(dtype), _st()), "clip_grad_y")
+    return Gy, part
+
+
+def clip_grad_y_finish(part, ysq, zsq_all, temp, inv_norm, row0, nrows):
+    """part: [nparts][Bg] partials of every block in rank order -> (rscale_y, cscale_y) of speech rows [row0, row0 + nrows)."""
+    nparts, Bg = part.shape
+    rscale = torch.empty(nrows, dtype=torch.float32, device=part.device)
+    cscale = torch.empty(nrows, dtype=torch.float32, device=part.device)
+    L.check(L.load().sda_clip_grad_y_finish(_p(part), nparts, Bg, _p(ysq), _p(zsq_all), zsq_all.numel(), _p(temp), float(inv_norm),
+                                            row0, nrows, _p(rscale), _p(cscale), _st()), "clip_grad_y_finish")
+    return rscale, cscale
 
 
 def clip_ranks(logits, diag, col0):
