@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp16|fp32] [--batch B_per_gpu]
                     [--dump-outputs DIR]   (the last timed step's outputs as DIR/<name>.npy, for build-to-build comparison)
+                    [--full]               (also the extra legs after the timed region: see Timing below)
 
 One step = BrainEncoder forward + CLIPLoss + top-k ranks + backward + (N > 1: gradient all-reduce) + Adam
 on one synthetic Gwilliams2022-shaped batch (208 sensors x 360 samples, 27 subjects, F = 1024,
@@ -18,10 +19,16 @@ of them resident stand-ins for the all-gather's delivery; every collective issue
 Under `torch.distributed.run` (RANK/WORLD_SIZE set) it runs as one rank.
 
 Timing: W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize fences with NO instrumentation
-inside; `value` = global segments / max-over-ranks time.  The roofline leg (HIP-event pairs around every launch of the
-GEMM-class kernels, on the stream they are launched on) runs AFTER the timed region on a few extra steps, so it cannot
-change `value`.  Prints ONE JSON line on rank 0 with `roofline` (dominant kernel) and, at N = 1, `cpu_baseline`
-(the CPU oracle timed on this box's host cores, BASELINE.md §3 procedure on a bounded sample).
+inside; `value` = global segments / max-over-ranks time.  Prints ONE JSON line on rank 0.  After the timed region a plain
+run only dumps the outputs (if asked), measures the held-out retrieval accuracy (one eval-mode forward) and checks that the
+parameters are finite.
+
+`--full` adds the extra legs, all AFTER the timed region so that none of them can change `value`: `host_synced` (the same
+step with per-step host read-backs), `with_feed` (config 2 at N = 1: the step fed by the resident input path), `roofline`
+(HIP-event pairs around every launch of the GEMM-class kernels, on the stream they are launched on, over a few extra steps)
+and, at N = 1 on config 2, `cpu_baseline` (the CPU oracle timed on this box's host cores, BASELINE.md §3 procedure on a
+bounded sample).  The `--no-*` switches leave single legs out of a `--full` run.  `--coll-timer-steps` (N > 1 or
+`--emulate-world`) runs whenever it is given.
 """
 import argparse
 import json
@@ -58,12 +65,14 @@ def parse_args():
                     "every collective issued for real through RCCL at world size 1.  A compute-side bound, not a scaling curve")
     ap.add_argument("--emulate-no-copy", action="store_true", help="--emulate-world: leave the stand-in rows in place instead of "
                     "re-delivering them (a 1.3 GB device copy beside the forward) every step")
-    ap.add_argument("--no-feed-leg", action="store_true", help="skip the extra loop fed by ResidentSegmentFeed + ShardedRandomSampler")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
-    ap.add_argument("--timer-steps", type=int, default=3, help="instrumented steps run after the timed region")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run the extra legs: host_synced, with_feed, "
+                    "roofline and (N = 1) cpu_baseline; without it the run does only what the headline figure needs")
+    ap.add_argument("--no-feed-leg", action="store_true", help="--full: skip the extra loop fed by ResidentSegmentFeed + ShardedRandomSampler")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle's timing")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="--full: skip the roofline leg")
+    ap.add_argument("--timer-steps", type=int, default=3, help="--full: instrumented steps of the roofline leg")
     ap.add_argument("--no-prefetch-ahead", action="store_true", help="N > 1: gather each step's speech rows at its own start")
-    ap.add_argument("--no-host-sync-leg", action="store_true", help="skip the extra loop that reads loss/ranks back every step")
+    ap.add_argument("--no-host-sync-leg", action="store_true", help="--full: skip the extra loop that reads loss/ranks back every step")
     ap.add_argument("--coll-timer-steps", type=int, default=0, help="N > 1: extra steps (after the timed region) with HIP-event "
                     "brackets around every collective; adds `collectives_us_per_step` to the JSON line")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed region, write what its LAST step computed "
@@ -444,7 +453,7 @@ def main():
 
     nxt = a.warmup + a.steps                                 # step indices stay contiguous across the legs: under N > 1 the
     dt_sync = None                                           # speech rows of step i + 1 were prefetched by step i
-    if not a.no_host_sync_leg:                               # same step with the reference loop's per-step host readbacks
+    if a.full and not a.no_host_sync_leg:                    # same step with the reference loop's per-step host readbacks
         n_sync = max(3, min(10, a.steps))
         dt_sync, _ = timed(n_sync, nxt, host_sync=True)
         dt_sync /= n_sync
@@ -455,7 +464,7 @@ def main():
     # made by ONE kernel (window gather + baseline correction + robust scaling + clamp) plus the speech rows' gather from the
     # resident embedding table — on a stream of its own, one batch ahead of the step that consumes it, like a data loader.
     dt_feed = None
-    if a.config == 2 and world == 1 and emu == 1 and not a.no_feed_leg:
+    if a.full and a.config == 2 and world == 1 and emu == 1 and not a.no_feed_leg:
         from speech_decoding_amd.data import ShardedRandomSampler, synthetic_resident_dataset
         n_feed = max(3, min(20, a.steps))
         # (as in the real dataset every task is heard by many subjects: ceil(S / 4) recordings per task, so that a batch spans
@@ -530,7 +539,7 @@ def main():
         del feed, pending
 
     timer = None
-    if not a.no_kernel_timer and a.timer_steps > 0:          # roofline leg, outside the timed region
+    if a.full and not a.no_kernel_timer and a.timer_steps > 0:   # roofline leg, outside the timed region
         timer = ops.KernelTimer(("conv_gemm", "wgrad_gemm"))
         fence()
         ops.TIMER = timer
@@ -599,7 +608,7 @@ def main():
             out["kernel_tflops"] = {f"{k[0]}<{k[1]},{k[2]},{k[3]}>": round(v[1] / (v[2] * 1e-3) / 1e12, 1) for k, v in summ.items() if v[2] > 0}
         if coll is not None:
             out["collectives_us_per_step"] = coll
-        if world == 1 and emu == 1 and a.config == 2 and not a.no_cpu_baseline:
+        if a.full and world == 1 and emu == 1 and a.config == 2 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(B)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

@@ -32,7 +32,7 @@ def test_bench_spawns_two_ranks_and_prints_one_json_line():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-           "--batch", "32", "--timer-steps", "1", "--coll-timer-steps", "2"]
+           "--batch", "32", "--timer-steps", "1", "--coll-timer-steps", "2", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     log_dir = os.path.join(ROOT, "gpurun_out")
     if os.path.isdir(log_dir):
@@ -57,7 +57,7 @@ def test_bench_spawns_two_ranks_and_prints_one_json_line():
 
 def test_bench_single_gpu_line_carries_the_contract_fields():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--batch", "32",
-           "--timer-steps", "1", "--no-host-sync-leg"]
+           "--timer-steps", "1", "--no-host-sync-leg", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     (line,) = _json_lines(out.stdout)
@@ -70,13 +70,31 @@ def test_bench_single_gpu_line_carries_the_contract_fields():
     assert r["bound"] == "mfma" and r["unit"] == "TFLOP/s" and r["frac"] == pytest.approx(r["achieved"] / r["peak"], rel=1e-3)
 
 
+def test_bench_plain_run_leaves_the_extra_legs_to_full():
+    """Without `--full` the run does what the headline needs and nothing after it: the contract fields, the held-out accuracy
+    and the final loss, but no host-synced, feed, roofline or CPU-baseline leg."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "32"]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    (line,) = _json_lines(out.stdout)
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                "dtype", "data", "config", "top10_acc", "top1_acc", "final_loss", "host_enqueue_ms_per_step"):
+        assert key in line, key
+    assert line["metric"].startswith("train segments/sec") and line["unit"] == "segments/s" and line["dtype"] == "bf16"
+    assert line["value"] == pytest.approx(32 * 2 / (line["ms_per_step"] * 2e-3), rel=1e-3)
+    for key in ("host_synced", "with_feed", "roofline", "kernel_time_ms_per_step", "kernel_tflops", "cpu_baseline",
+                "collectives_us_per_step"):
+        assert key not in line, key
+
+
 def test_bench_emulated_world_config_and_feed_legs():
     """Round-5 modes: `--emulate-world` (ONE JSON line although RCCL prints a banner on stdout; global batch, workload text and
     collective brackets of the emulated world), `--config 4` (per-GPU shape of configs[3]) and the `with_feed` leg."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SDA_DP_SINGLE_RANK"):
         env.pop(k, None)
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--timer-steps", "1", "--no-host-sync-leg"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--timer-steps", "1", "--no-host-sync-leg",
+            "--full"]
     out = subprocess.run(base + ["--batch", "32", "--emulate-world", "4", "--coll-timer-steps", "1"], env=env, capture_output=True,
                          text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]

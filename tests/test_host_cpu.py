@@ -323,3 +323,18 @@ def test_bench_dump_sample_is_seeded_and_bounded():
     assert np.array_equal(bench._dump_sample(small, 4096, "ranks"), np.arange(10, dtype=np.float32))
     assert bench._dump_sample(torch.ones(5, dtype=torch.float64), 4096, "x").dtype == np.float64
     assert bench._dump_sample(torch.ones(4, dtype=torch.complex64), 4096, "c").shape == (8,)
+
+
+def test_bench_extra_legs_are_behind_full(monkeypatch):
+    """bench.py: a plain run does only what the headline needs; host_synced, with_feed, roofline and cpu_baseline run with
+    `--full`, where the `--no-*` switches still leave single legs out."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.parse_args().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"])
+    a = bench.parse_args()
+    assert a.full and a.no_cpu_baseline and not a.no_kernel_timer
