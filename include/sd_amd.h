@@ -483,6 +483,17 @@ int sda_mse_forward(const void* z, int z_cp, int z_dtype, const void* y, int y_c
 int sda_mse_backward(const void* z, int z_cp, int z_dtype, const void* y, int y_cp, int y_dtype, int B, int F, int T, int b_div,
                      const float* dloss, void* dz, void* dy, void* stream);
 
+/* The encoder's gradient with respect to its input (ABI 4): for c < C, t < T
+ *     out[b][c][t] = sum_{d < Kp} W[w_b][d][c] * G[b * (T + SDA_ROW_PAD) + SDA_ROW_PAD + t][d],   w_b = widx ? widx[b] : 0
+ * G: row-layout data gradient at the output of the SubjectBlock's first linear map, `dtype`, row pitch g_pitch elements
+ * (>= Kp, 16-byte rows); W: the (nW, Kp, Cp) matrix the forward applied, `dtype`, contracted over its ROW index (read as a
+ * transposed MFMA operand: no transposed copy); Kp % 32 == 0, Cp % 64 == 0, C <= Cp; widx: B device ints in [0, nW), required
+ * when nW > 1.  out: a contiguous (B, C, T) tensor of out_dtype (fp32 / bf16 / fp16), fp32 accumulation, every element written
+ * once: no zero fill and no row-layout intermediate.  W's bias column (C) and pad columns are never read into the output.
+ * Null pointers, bad sizes or misaligned operands return -1 (sda_last_error) and launch nothing. */
+int sda_input_grad(const void* G, long g_pitch, const void* W, const int* widx, int nW, int Kp, int Cp, int B, int C, int T,
+                   int dtype, void* out, int out_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,9 @@ class EncoderCtx:
     packed_T_ready: Optional[torch.cuda.Event] = None     # side-stream packing of packed_T has finished
     glu_fused: bool = False                               # F.glu ran in conv2's epilogue: bufs hold the gate, not [value | gate]
     composed: Optional[tuple] = None                      # composed SubjectBlock: (Wd, T1aug, Ws) fp32 factors kept for backward
+    param_grads: bool = True                              # backward computes the parameters' gradients (False: a frozen encoder)
+    x_dtype: Optional[torch.dtype] = None                 # X requires a gradient: dX comes back in this dtype ...
+    W_x: Optional[torch.Tensor] = None                    # ... through the matrix the forward applied to X (its own copy)
 
 
 class EncoderEngine:
@@ -246,7 +249,10 @@ class EncoderEngine:
 
     # ------------------------------------------------------------------ forward
     def forward(self, P: Dict[str, torch.Tensor], X: torch.Tensor, subject_idxs, *, training: bool,
-                mask: Optional[torch.Tensor], need_grad: bool, momentum: float = 0.1, eps: float = 1e-5) -> EncoderCtx:
+                mask: Optional[torch.Tensor], need_grad: bool, momentum: float = 0.1, eps: float = 1e-5,
+                need_dx: bool = False, param_grads: bool = True) -> EncoderCtx:
+        """need_dx: the backward also returns the gradient of X (needs need_grad); param_grads = False (a frozen encoder, with
+        need_dx): the backward runs the data-gradient chain only, and this forward builds nothing the weight gradients read."""
         d, dt = self.d, self.dtype
         B, Cc, T = X.shape
         assert Cc == d.C, f"expected {d.C} channels, got {Cc}"          # models.py:78
@@ -257,6 +263,10 @@ class EncoderEngine:
         self._touch_shape(space, B, T)
         ctx = EncoderCtx(B=B, T=T, gen=self._gen, training=training)
         ctx.glu_fused = self.glu_fused
+        if need_dx and not need_grad:
+            raise L.SdaError("EncoderEngine.forward: need_dx needs need_grad")
+        ctx.param_grads = bool(param_grads or not need_dx)
+        ctx.x_dtype = X.dtype if need_dx else None
         bufs, pk = ctx.bufs, ctx.packed
 
         def rows(name, Cp):
@@ -275,7 +285,7 @@ class EncoderEngine:
             raise IndexError("subject index out of range")                # ModuleList semantics, models.py:115
         up = ops.UPLOADER.upload                # pinned staging: no implicit host<->stream synchronisation
         ctx.widx = up(("widx", space), sidx.astype(np.int32), dev)
-        if need_grad:
+        if need_grad and ctx.param_grads:
             # per-subject weight gradient: samples sorted by subject, one K-segment per (slice j, subject s) in
             # j-major order.  With many subjects one slice each is enough (the S segments already fill the GPU);
             # with few (S = 1 in configs 1/4) every subject's samples are cut into r slices so that the launch still
@@ -352,7 +362,11 @@ class EncoderEngine:
             ops.copy3d(T1aug[:, d.C:], P["sb_b"][:, None])
             key = ("wtot", str(dev), dt)
             Wtot = self._const.get(key)
-            if Wtot is None:
+            if need_dx:
+                # the backward contracts dx0 with THIS matrix: a copy of the forward's own, which a later forward (a no-grad one
+                # between this forward and its backward included) cannot rewrite
+                Wtot = ctx.W_x = ops.zeros((d.S, 1, d.D1p, d.Cp), dt, dev)
+            elif Wtot is None:
                 Wtot = self._const[key] = torch.zeros((d.S, 1, d.D1p, d.Cp), dtype=dt, device=dev)
             ops.param_gemm(Ws, T1aug, out=Wtot[:, 0, : d.D1, : d.C + 1])                      # rounded to the compute dtype on the way out
             if need_grad:
@@ -363,6 +377,7 @@ class EncoderEngine:
                               alg_dims=(d.C, d.D1))
             bufs["x0"] = x
         else:
+            ctx.W_x = Wp if need_dx else None          # (sa_weights_forward returns a fresh matrix per forward)
             if packed_ready is not None:
                 self._wait("packed operands (forward)", main, packed_ready)
             h_sa = ops.conv_gemm(Xt, Wp, rows("h_sa", d.D1p), B=B, T=T, KS=1, dil=0, alg_dims=(d.C, d.D1))
@@ -452,6 +467,8 @@ class EncoderEngine:
 
     # ------------------------------------------------------------------ backward
     def backward(self, P: Dict[str, torch.Tensor], ctx: EncoderCtx, dZt: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """The parameters' gradients by name (none for a frozen encoder: ctx.param_grads False) and, when the forward had
+        need_dx, grads["X"] = dL/dX as a contiguous (B, C, T) tensor of X's dtype."""
         if ctx.gen != self._gen and self.reuse_workspace:
             raise L.SdaError("the activation workspace of this forward was overwritten by a later forward of the same "
                              "encoder; call backward before the next training-mode forward, or set "
@@ -462,6 +479,7 @@ class EncoderEngine:
         if getattr(ctx, "packed_T_ready", None) is not None:
             self._wait("packed operands (backward)", torch.cuda.current_stream(dev), ctx.packed_T_ready)
         grads: Dict[str, torch.Tensor] = {}
+        pg = ctx.param_grads                  # False: the data-gradient chain only (no weight gradient, bias sum or collective of them)
         scratch = ops.reduce_scratch(max(d.Fp, 2 * d.D2p, d.F1p), dev)
         pending = []                          # (work, names) of in-flight gradient all-reduces
         overlap = self.group is not None and self.overlap_grad_allreduce
@@ -469,7 +487,7 @@ class EncoderEngine:
         def flush(names):
             """Pack the named gradients into one flat bucket, start its SUM all-reduce asynchronously and
             re-point the gradients at views of the bucket (no copy back)."""
-            if not overlap:
+            if not overlap or not pg:
                 return
             import torch.distributed as dist
             from .distributed import side_group
@@ -528,6 +546,8 @@ class EncoderEngine:
                 self._wait("weight-gradient stream joined", main, ev)
 
         def wgrad(dy, x, KS, dil, Cout, Cin, **glu):
+            if not pg:
+                return None
             Cout_p, Cin_p = dy.shape[1], x.shape[1]
             tile_m = 160 if Cout_p % 160 == 0 else (128 if Cout_p % 128 == 0 else 64)
             perm, seg, nseg = self._uniform_segments(B, (Cout_p // tile_m) * (Cin_p // 64), dev)
@@ -546,7 +566,7 @@ class EncoderEngine:
         ntile = B * ops.n_t_tiles(T)
 
         W0cat = None
-        if ctx.composed is not None:
+        if ctx.composed is not None and pg:
             # block 0's conv0 weights as [d][tap][o] (o zero-padded to D2p; the padding is written once), the left operand of the
             # composed SubjectBlock's gradient at the END of backward: a parameter-only copy, so it is made here, on the
             # weight-gradient stream while that has nothing to do, not in the serial tail of the step
@@ -597,7 +617,10 @@ class EncoderEngine:
 
         # ---- final projections
         du2 = tmp("du2", d.Fp)
-        grads["f2b"] = bias_grad(ops.gelu_backward_colsum(bufs["u2"], dZt, du2, B, T, scratch), d.F)
+        if pg:
+            grads["f2b"] = bias_grad(ops.gelu_backward_colsum(bufs["u2"], dZt, du2, B, T, scratch), d.F)
+        else:
+            ops.gelu_backward(bufs["u2"], dZt, du2, B, T)
         # the 1x1 data gradients on conv1_flat.hip's 256-row flat tiles
         du1 = tmp("du1", d.F1p)
         if d.F1p % 160 == 0 or d.F1p % 128 == 0:
@@ -607,11 +630,15 @@ class EncoderEngine:
             ops.conv_gemm(du2, ctx.packed_T["f2w"], du1, B=B, T=T, KS=1, dil=0, gelu_bwd_u=bufs["u1"], stats=gst,
                           alg_dims=(d.F, d.F1), flags=L.CONV_FLAT_TILES)
             grads["f2w"] = wgrad(du2, bufs["g1"], 1, 0, d.F, d.F1)
-            grads["f1b"] = on_side(lambda: bias_grad(ops.reduce_stats(gst)[:d.F1p], d.F1))
+            if pg:
+                grads["f1b"] = on_side(lambda: bias_grad(ops.reduce_stats(gst)[:d.F1p], d.F1))
         else:
             dg1, _ = dgrad(du2, "f2w", P["f2w"], d.Fp, d.F1p, tmp("dg1", d.F1p), 1, 0)
             grads["f2w"] = wgrad(du2, bufs["g1"], 1, 0, d.F, d.F1)
-            grads["f1b"] = bias_grad(ops.gelu_backward_colsum(bufs["u1"], dg1, du1, B, T, scratch), d.F1)
+            if pg:
+                grads["f1b"] = bias_grad(ops.gelu_backward_colsum(bufs["u1"], dg1, du1, B, T, scratch), d.F1)
+            else:
+                ops.gelu_backward(bufs["u1"], dg1, du1, B, T)
         # Where the forward kept (out, gate) of every F.glu, the conv that produces the gradient entering a block's GLU (this
         # 1x1 data gradient for block 4, conv0's data gradient of block k + 1 for block k) applies the GLU backward in its
         # epilogue: `glu_pending` = (dc2, per-tile column sums) for the block about to be processed, and dx is never stored
@@ -630,7 +657,7 @@ class EncoderEngine:
         # the gradient of the ten biases that feed a training-mode BatchNorm (identically zero): rows of ONE fresh zero buffer
         # per backward — autograd hands these views to the parameters' .grad, so a buffer kept across steps would alias
         # engine-owned memory into .grad (an in-place clip with a non-finite factor would poison every later step)
-        null_bias = ops.zeros((10, d.D2), torch.float32, dev) if ctx.training else None
+        null_bias = ops.zeros((10, d.D2), torch.float32, dev) if ctx.training and pg else None
         flip = 0
         for k in range(4, -1, -1):
             cin, cin_p = (d.D1, d.D1p) if k == 0 else (d.D2, d.D2p)
@@ -639,10 +666,16 @@ class EncoderEngine:
             c2b = lambda cs: bias_grad(cs, 2 * d.D2, **glu)          # noqa: E731  (a kernel when D2 is not a multiple of 64)
             if glu_pending is not None:
                 dc2, gst = glu_pending
-                grads[f"b{k}.c2b"] = c2b(ops.reduce_stats(gst))   # [sum d value | sum d gate] over all rows
+                if pg:
+                    grads[f"b{k}.c2b"] = c2b(ops.reduce_stats(gst))   # [sum d value | sum d gate] over all rows
             else:
                 dc2 = tmp(f"dc2.{k}", 2 * d.D2p)      # per-layer buffers: a side-stream wgrad may still read them
-                if ctx.glu_fused:
+                if not pg:
+                    if ctx.glu_fused:
+                        ops.glu_backward_og(bufs[f"x{k + 1}"], bufs[f"b{k}.g"], dx, dc2, B, T)
+                    else:
+                        ops.glu_backward(bufs[f"b{k}.c2"], dx, dc2, B, T)
+                elif ctx.glu_fused:
                     grads[f"b{k}.c2b"] = c2b(ops.glu_backward_colsum_og(bufs[f"x{k + 1}"], bufs[f"b{k}.g"], dx, dc2, B, T, scratch))
                 else:
                     grads[f"b{k}.c2b"] = c2b(ops.glu_backward_colsum(bufs[f"b{k}.c2"], dx, dc2, B, T, scratch))
@@ -664,25 +697,31 @@ class EncoderEngine:
                                                   scratch, count=float(B) * T * world if ctx.training else float("inf"),
                                                   allreduce=self._allreduce if sync else None, tile_stats=tstats)
                 # under DP the sums are already global on every rank; the gradient all-reduce (SUM) follows
-                if sync:
+                if sync and pg:
                     # (one launch for both rows, on the weight-gradient stream: only the optimiser reads these)
                     both = dgam._base if dgam._base is not None else torch.stack([dgam, dbet])
                     if side is not None:
                         both.record_stream(side)
                     scaled = on_side(lambda both=both: both / world)
                     dgam, dbet = scaled[0], scaled[1]
-                grads[bnp + "w"], grads[bnp + "b"] = dgam[: d.D2], dbet[: d.D2]
+                if pg:
+                    grads[bnp + "w"], grads[bnp + "b"] = dgam[: d.D2], dbet[: d.D2]
                 src = bufs[f"b{k}.a0"] if j == 1 else x_in
                 ci, ci_p = (d.D2, d.D2p) if j == 1 else (cin, cin_p)
                 # conv0/conv1 feed a training-mode BatchNorm, which removes any per-channel constant: the bias
                 # gradient is identically zero (the reference's autograd reports rounding noise there)
-                grads[f"b{k}.c{j}b"] = null_bias[2 * k + j] if ctx.training else bias_grad(ops.colsum(dh, B, T, scratch), d.D2)
+                if pg:
+                    grads[f"b{k}.c{j}b"] = null_bias[2 * k + j] if ctx.training else bias_grad(ops.colsum(dh, B, T, scratch), d.D2)
                 res = dh if (j == 1 or k > 0) else None
                 out = tmp("da", d.D2p) if j == 1 else tmp("dxB" if flip == 0 else "dxA", ci_p)
                 if k == 0 and j == 0 and ctx.composed is not None:
                     # the composed SubjectBlock takes its weight gradient straight from dh0 and X (below): the gradient with
-                    # respect to x0 is never needed, this data-gradient conv is not run
-                    da1, tstats, dh0 = None, None, dh
+                    # respect to x0 is needed only for X's gradient, and this data-gradient conv runs only then
+                    dh0 = dh
+                    if ctx.x_dtype is not None:
+                        da1, tstats = dgrad(dh, f"b{k}.c{j}w", P[f"b{k}.c{j}w"], d.D2p, ci_p, out, 3, dil[j])
+                    else:
+                        da1, tstats = None, None
                 elif j == 0 and k > 0 and glu_in_epilogue:     # its output is the gradient entering block k - 1's GLU
                     glu_pending = dgrad(dh, f"b{k}.c{j}w", P[f"b{k}.c{j}w"], d.D2p, ci_p, tmp(f"dc2.{k - 1}", 2 * d.D2p), 3, dil[j],
                                         res=res, glu_bwd=(bufs[f"x{k}"], bufs[f"b{k - 1}.g"]))
@@ -698,6 +737,13 @@ class EncoderEngine:
 
         # ---- SubjectBlock
         if ctx.composed is not None:
+            if ctx.x_dtype is not None:
+                # dX[b] = Wtot[s_b]^T dx0[b]: columns < C of the forward's own matrix (the bias column C and the pad columns
+                # are not read out), stored straight into a plain (B, C, T) tensor of X's dtype
+                grads["X"] = ops.input_grad(dx, ctx.W_x, ctx.widx, B, d.C, T, ctx.x_dtype)
+            if not pg:
+                join_side()
+                return grads
             Wd, T1aug, Ws = ctx.composed
             r = ctx.subj_slices
             # x0 = W_tot[s] X feeds block 0's conv0 and nothing else, and h0 = sum_tap W0[tap] x0[t + (tap - 1) dil], so
@@ -738,11 +784,19 @@ class EncoderEngine:
             if r > 1:
                 slabs = ops.reduce_slabs(slabs.view(r, -1)).view(d.S, 1, d.D1p, d.D1p)
             return ops.unpack_conv_wgrad(slabs, d.S, d.D1, d.D1, 1, d.D1p, d.D1p)
-        grads["subj_w"] = on_side(subj_wgrad)
+        if pg:
+            grads["subj_w"] = on_side(subj_wgrad)
         dh_c, _ = dgrad(dhs, "subj_w", P["subj_w"], d.D1p, d.D1p, tmp("dh_c", d.D1p), 1, 0, widx=ctx.widx)
-        grads["sb_w"] = wgrad(dh_c, bufs["h_sa"], 1, 0, d.D1, d.D1)
-        grads["sb_b"] = bias_grad(ops.colsum(dh_c, B, T, scratch), d.D1)
+        if pg:
+            grads["sb_w"] = wgrad(dh_c, bufs["h_sa"], 1, 0, d.D1, d.D1)
+            grads["sb_b"] = bias_grad(ops.colsum(dh_c, B, T, scratch), d.D1)
         dh_sa, _ = dgrad(dh_c, "sb_w", P["sb_w"], d.D1p, d.D1p, tmp("dh_sa", d.D1p), 1, 0)
+        if ctx.x_dtype is not None:
+            # dX[b] = Wp^T dh_sa[b]: Wp is the forward's packed W_sa * mask (one matrix for every sample)
+            grads["X"] = ops.input_grad(dh_sa, ctx.W_x, None, B, d.C, T, ctx.x_dtype)
+        if not pg:
+            join_side()
+            return grads
         Cout_p, Cin_p = d.D1p, d.Cp
         tile_m = 160 if Cout_p % 160 == 0 else (128 if Cout_p % 128 == 0 else 64)
         perm, seg, nseg = self._uniform_segments(B, (Cout_p // tile_m) * (Cin_p // 64), dev)

@@ -155,9 +155,10 @@ class ConvBlock(nn.Module):
 
 class _EncoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, module: "BrainEncoder", X, subject_idxs, mask, need_grad, *params):
+    def forward(ctx, module: "BrainEncoder", X, subject_idxs, mask, need_grad, x_grad, param_grads, *params):
         P = module._param_dict(params)
-        ectx = module.engine.forward(P, X, subject_idxs, training=module.training, mask=mask, need_grad=need_grad)
+        ectx = module.engine.forward(P, X, subject_idxs, training=module.training, mask=mask, need_grad=need_grad,
+                                     need_dx=x_grad, param_grads=param_grads)
         ctx.module, ctx.ectx, ctx.P = module, ectx, P
         ctx.nparams = len(params)
         B, _, T = X.shape
@@ -169,8 +170,10 @@ class _EncoderFn(torch.autograd.Function):
         P = ctx.P
         dZt = _loss.as_rows(dZ, ectx.B, module.F, ectx.T, module.engine.dtype, "dZ")
         g = module.engine.backward(P, ectx, dZt)
-        out = [g.get(name) for name in module._param_names]
-        return (None, None, None, None, None, *out)
+        need = ctx.needs_input_grad[7:]
+        out = [g.get(name) if n else None for name, n in zip(module._param_names, need)]
+        dX = g.get("X") if ctx.needs_input_grad[1] else None
+        return (None, dX, None, None, None, None, None, *out)
 
 
 class BrainEncoder(nn.Module):
@@ -259,6 +262,9 @@ class BrainEncoder(nn.Module):
     def forward(self, X: torch.Tensor, subject_idxs) -> torch.Tensor:
         sa = self.subject_block.spatial_attention
         assert X.shape[1] == sa.loc.shape[0]                                      # models.py:78
+        if torch.is_grad_enabled() and X.requires_grad and X.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise L.SdaError(f"BrainEncoder: X of dtype {X.dtype} requires a gradient; its gradient is computed for float32, "
+                             "bfloat16 and float16 inputs only")
         if not X.is_cuda:
             raise L.SdaError("BrainEncoder needs X on the MI355X device (there is no CPU path)")
         mask = None
@@ -294,8 +300,12 @@ class BrainEncoder(nn.Module):
                                              "brain_encoder.drop_centre_sync = 'broadcast'")
                     self._centre_draws += 1
         params = self._ordered_params()
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)   # (grad mode is off inside Function.forward)
-        return _EncoderFn.apply(self, X, subject_idxs, mask, need_grad, *params)
+        grad_mode = torch.is_grad_enabled()                  # (grad mode is off inside Function.forward)
+        param_grads = grad_mode and any(p.requires_grad for p in params)
+        x_grad = grad_mode and X.requires_grad
+        # X requiring a gradient with every parameter frozen (saliency maps, a trained encoder behind a learnable front end):
+        # the backward runs the data-gradient chain only
+        return _EncoderFn.apply(self, X, subject_idxs, mask, param_grads or x_grad, x_grad, param_grads, *params)
 
 
 class Classifier(nn.Module):

@@ -215,6 +215,24 @@ def unpack_rows_typed(src: torch.Tensor, B: int, Cc: int, T: int, dtype) -> torc
     return out
 
 
+def input_grad(G: torch.Tensor, W: torch.Tensor, widx: Optional[torch.Tensor], B: int, Cc: int, T: int, dtype) -> torch.Tensor:
+    """dX[b][c][t] = sum_d W[w_b][d][c] G[row(b, t)][d] (sda_input_grad): G a row-layout buffer of the compute dtype, W the
+    (nW, 1, Kp, Cp) or (nW, Kp, Cp) matrix the forward applied, widx B device int32 indices (None: one matrix).  Returns a fresh
+    contiguous (B, C, T) tensor of `dtype` (fp32 / bf16 / fp16)."""
+    _need_cuda(G, W)
+    Wv = W.reshape(W.shape[0], W.shape[-2], W.shape[-1]) if W.dim() == 4 and W.shape[1] == 1 else W
+    if Wv.dim() != 3 or not Wv.is_contiguous() or Wv.dtype != G.dtype:
+        raise L.SdaError("input_grad: W must be a contiguous (nW, Kp, Cp) tensor of G's dtype")
+    if G.dim() != 2 or not G.is_contiguous() or G.shape[0] < L.rows_alloc(B, T) or G.shape[1] < Wv.shape[1]:
+        raise L.SdaError("input_grad: G must be a row-layout buffer at least Kp channels wide")
+    if widx is not None and (widx.dtype != torch.int32 or widx.numel() != B or not widx.is_cuda):
+        raise L.SdaError("input_grad: widx must hold B int32 indices on the device")
+    out = torch.empty((B, Cc, T), dtype=dtype, device=G.device)
+    L.check(L.load().sda_input_grad(_p(G), G.shape[1], _p(Wv), _p(widx), Wv.shape[0], Wv.shape[1], Wv.shape[2], B, Cc, T,
+                                    dt_code(G.dtype), _p(out), dt_code(dtype), _st()), "input_grad")
+    return out
+
+
 def rows_sumsq(x: torch.Tensor, B: int, row_elems: int, pitch: int) -> torch.Tensor:
     out = torch.empty(B, dtype=torch.float32, device=x.device)
     scratch = torch.empty(B * 64, dtype=torch.float32, device=x.device)
@@ -664,6 +682,16 @@ def glu_backward_colsum_og(out, gate, dy, dx, B, T, scratch):
     L.check(L.load().sda_glu_backward_colsum_og(_p(out), _p(gate), _p(dy), _p(dx), _p(cs), _p(scratch), B, T, Ch,
                                                 dt_code(dy.dtype), _st()), "glu_backward_colsum_og")
     return cs
+
+
+def glu_backward_og(out, gate, dy, dx, B, T):
+    """glu_backward_colsum_og's dx alone (a backward that wants no bias gradient): with no colsum the kernel leaves its per-row
+    partial sums in a scratch buffer and launches no final reduction."""
+    Ch = dy.shape[1]
+    scratch = torch.empty(L.load().sda_reduce_scratch_rows(B, T) * 2 * Ch, dtype=torch.float32, device=dy.device)
+    L.check(L.load().sda_glu_backward_colsum_og(_p(out), _p(gate), _p(dy), _p(dx), None, _p(scratch), B, T, Ch,
+                                                dt_code(dy.dtype), _st()), "glu_backward_og")
+    return dx
 
 
 def gelu_backward_colsum(u, dz, du, B, T, scratch):

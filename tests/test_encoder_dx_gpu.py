@@ -1,0 +1,298 @@
+"""BrainEncoder's gradient with respect to its input X on the MI355X: the reference's own numbers (tests/golden/encoder_dx.npz) in
+train and eval mode for both SubjectBlock forms, every compute dtype x X dtype against float64 autograd on the same rounded
+operands at full widths, dropped sensors, the frozen encoder's data-gradient-only backward, unchanged bits and launches when X
+needs no gradient, a no-grad forward between forward and backward, and joint Adam steps of a front end with the encoder."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from oracle import brain_oracle as O                                      # noqa: E402
+from tests import golden_io as G                                           # noqa: E402
+from tests.parity import operands_as_device_sees_them, rel_l2, round_to   # noqa: E402
+
+DEV = "cuda:0"
+DT = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+GRAD_REL_L2 = {"fp32": 1e-4, "bf16": 6e-2, "fp16": 8e-3}        # every gradient 6e-2 / 8e-3 in the 16-bit modes
+OUT_REL_L2 = {"fp32": 0.0, "bf16": 6e-3, "fp16": 1e-3}          # + the rounding of dX to X's own dtype
+TOY = dict(C=20, S=3, D1=32, D2=48, F=64, K=4, T=70, B=6)
+WIDE = {"208": dict(C=208, S=27, D1=270, D2=320, F=1024, K=32, T=96, B=4), "60": dict(C=60, S=1, D1=270, D2=320, F=1024, K=32, T=96, B=4)}
+
+
+class Args(dict):
+    __getattr__ = dict.__getitem__
+
+
+def build_encoder(P, d, loc, dtype="fp32", training=True):
+    from speech_decoding.models import BrainEncoder
+    args = Args(num_subjects=d["S"], D1=d["D1"], D2=d["D2"], F=d["F"], K=d["K"], dataset="Gwilliams2022", d_drop=0.1,
+                root_dir=".", preprocs={"last4layers": False}, sensor_positions=loc.numpy(), compute_dtype=dtype)
+    enc = BrainEncoder(args)
+    enc.load_state_dict(P)
+    return enc.to(DEV).train(training)
+
+
+def clip(temp=2.0):
+    from speech_decoding.utils.loss import CLIPLoss
+    return CLIPLoss(Args(reduction="mean", init_temperature=temp)).to(DEV)
+
+
+def setup(d, seed=2, dtype="fp32", training=True):
+    loc = O.synthetic_positions(d["C"], seed=1)
+    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=seed, loc=loc)
+    X, Y, subj = O.synthetic_batch(d["B"], d["C"], d["T"], d["F"], d["S"], seed=3)
+    return loc, P, X, Y, subj, build_encoder(P, d, loc, dtype, training)
+
+
+def step(enc, X, Y, subj, centre=4, xdtype=torch.float32, x_grad=True, scale=1.0, crit=None):
+    """One forward + CLIP loss + backward; returns (loss, Z, dX as fp64 unscaled or None, X leaf)."""
+    enc.set_drop_centre(centre)
+    Xl = X.to(DEV).to(xdtype).requires_grad_(x_grad)
+    Z = enc(Xl, subj)
+    loss = (crit or clip())(Y.to(DEV), Z)
+    (loss * scale if scale != 1.0 else loss).backward()
+    dX = None
+    if x_grad:
+        assert Xl.grad is not None and Xl.grad.dtype == xdtype and Xl.grad.shape == X.shape and Xl.grad.is_contiguous()
+        dX = Xl.grad.double().cpu() / scale
+    return loss.detach(), Z.detach(), dX, Xl
+
+
+def oracle_dx(P, X, Y, subj, loc, centre, training, temp=2.0):
+    Q = {k: (v.to(torch.complex128) if v.is_complex() else v.double()) if (v.is_floating_point() or v.is_complex()) else v
+         for k, v in P.items()}
+    Xd = X.double().requires_grad_(True)
+    Z = O.brain_encoder_forward(Q, Xd, subj, training=training, loc=loc.double(), drop_centre=centre if training else None)
+    loss, _ = O.clip_loss(Y.double(), Z, torch.tensor([temp], dtype=torch.float64))
+    (dX,) = torch.autograd.grad(loss, [Xd])
+    return dX
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# 1. the reference's numbers
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["train", "eval"])
+@pytest.mark.parametrize("i", [0, 1])
+def test_golden_fixture_fp32(i, mode):
+    npz = G.load("encoder_dx.npz")
+    C, S, D1, D2, F, K, T, B = (int(v) for v in npz[f"s{i}/dims"])
+    d = dict(C=C, S=S, D1=D1, D2=D2, F=F, K=K, T=T, B=B)
+    loc_seed, param_seed, _ = (int(v) for v in npz["seeds"])
+    loc = O.synthetic_positions(C, seed=loc_seed)
+    P = O.seeded_params(C, S, D1, D2, F, K, seed=param_seed, loc=loc)
+    if mode == "eval":
+        P.update(G.state_from(npz, f"s{i}/eval/state/"))
+    enc = build_encoder(P, d, loc, training=mode == "train")
+    assert enc.engine.composed == (i == 0)
+    X, Y = torch.from_numpy(npz[f"s{i}/X"]), torch.from_numpy(npz[f"s{i}/Y"])
+    subj = torch.from_numpy(npz[f"s{i}/subject_idxs"])
+    loss, Z, dX, _ = step(enc, X, Y, subj, centre=int(npz[f"s{i}/drop_centre"]), crit=clip(float(npz["temp"])))
+    want = torch.from_numpy(npz[f"s{i}/{mode}/dX"]).double()
+    zref = torch.from_numpy(npz[f"s{i}/{mode}/Z"])
+    assert abs(float(loss) - float(npz[f"s{i}/{mode}/loss"])) <= 1e-4 * abs(float(npz[f"s{i}/{mode}/loss"]))
+    assert float((Z.float().cpu() - zref).abs().max()) <= 1e-4 * float(zref.abs().max())
+    err = float((dX - want).abs().max())
+    assert err <= 1e-3 * float(want.abs().max()), (i, mode, err, float(want.abs().max()))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# 2. compute dtype x X dtype, full widths with real padding
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("xdt", ["fp32", "bf16", "fp16"])
+@pytest.mark.parametrize("dtype", ["fp32", "bf16", "fp16"])
+@pytest.mark.parametrize("tag", ["208", "60"])
+def test_dtypes_at_full_width_against_float64(tag, dtype, xdt):
+    d = WIDE[tag]
+    loc, P, X, Y, subj, enc = setup(d, seed=0, dtype=dtype)
+    assert enc.engine.composed                                 # 208 -> 256 and 60 -> 64: the composed SubjectBlock
+    from speech_decoding_amd.amp import LossScaler
+    # fp16 anywhere: the static loss scale of the fp16 path keeps the gradients out of fp16's subnormal range
+    scale = LossScaler.for_dtype(torch.float16).scale_value if "fp16" in (dtype, xdt) else 1.0
+    _, _, dX, _ = step(enc, X, Y, subj, centre=5, xdtype=DT[xdt], scale=scale)
+    Xr = round_to(round_to(X, xdt), dtype)
+    want = oracle_dx(operands_as_device_sees_them(P, dtype), Xr, round_to(Y, dtype), subj, loc, 5, True)
+    assert float(want.abs().max()) > 0
+    bound = GRAD_REL_L2[dtype] + OUT_REL_L2[xdt]
+    assert rel_l2(dX, want) <= bound, (tag, dtype, xdt, rel_l2(dX, want), bound)
+
+
+def test_three_conv_form_bf16_against_float64():
+    d = dict(TOY, C=64)
+    loc, P, X, Y, subj, enc = setup(d, dtype="bf16")
+    assert not enc.engine.composed
+    _, _, dX, _ = step(enc, X, Y, subj, xdtype=torch.bfloat16)
+    want = oracle_dx(operands_as_device_sees_them(P, "bf16"), round_to(X, "bf16"), round_to(Y, "bf16"), subj, loc, 4, True)
+    assert rel_l2(dX, want) <= GRAD_REL_L2["bf16"] + OUT_REL_L2["bf16"]
+
+
+def test_config2_batch_256_bf16():
+    """Config ② (C=208, S=27, D1=270, D2=320, F=1024, T=360) at B = 256 in bf16, eval mode so that samples are independent:
+    a loss that is linear in Z gives every sample its own gradient, and the oracle checks four of them."""
+    d = dict(C=208, S=27, D1=270, D2=320, F=1024, K=32, T=360, B=256)
+    loc = O.synthetic_positions(d["C"], seed=0)
+    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=0, loc=loc)
+    X, _, subj = O.synthetic_batch(d["B"], d["C"], d["T"], d["F"], d["S"], seed=1234)
+    R = torch.randn(d["B"], d["F"], d["T"], generator=torch.Generator().manual_seed(8))
+    enc = build_encoder(P, d, loc, "bf16", training=False)
+    Xl = X.to(DEV).to(torch.bfloat16).requires_grad_(True)
+    Z = enc(Xl, subj)
+    (Z.float() * R.to(DEV)).sum().backward()
+    assert Xl.grad.dtype == torch.bfloat16 and Xl.grad.shape == X.shape and bool(torch.isfinite(Xl.grad).all())
+    Pr = operands_as_device_sees_them(P, "bf16")
+    Q = {k: v.to(torch.complex128) if v.is_complex() else (v.double() if v.is_floating_point() else v) for k, v in Pr.items()}
+    for b in (0, 77, 200, 255):
+        Xd = round_to(X[b:b + 1], "bf16").double().requires_grad_(True)
+        Zb = O.brain_encoder_forward(Q, Xd, subj[b:b + 1], training=False, loc=loc.double())
+        (want,) = torch.autograd.grad((Zb * R[b:b + 1].double()).sum(), [Xd])
+        assert rel_l2(Xl.grad[b:b + 1].double().cpu(), want) <= GRAD_REL_L2["bf16"] + OUT_REL_L2["bf16"], b
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# 3. SpatialDropout: dropped sensors get exactly zero
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("C", [20, 64])
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_dropped_sensors_get_exact_zero(C, dtype):
+    d = dict(TOY, C=C)
+    loc, P, X, Y, subj, enc = setup(d, dtype=dtype)
+    centre = next(c for c in range(C) if int((O.dropout_mask(loc, c, 0.1) == 0).sum()) >= 2)
+    _, _, dX, _ = step(enc, X, Y, subj, centre=centre)
+    dropped = O.dropout_mask(loc, centre, 0.1) == 0
+    assert bool((dX[:, dropped] == 0).all())
+    assert float(dX[:, ~dropped].abs().max()) > 0
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# 4. frozen encoder: the data-gradient-only backward
+# ------------------------------------------------------------------------------------------------------------------------------
+WEIGHT_GRADIENT_WRAPPERS = ("wgrad_gemm", "reduce_slabs", "reduce_unpack_wgrad", "unpack_conv_wgrad", "unpack_vector", "param_gemm",
+                            "sa_weights_backward", "colsum", "gelu_backward_colsum", "glu_backward_colsum", "glu_backward_colsum_og",
+                            "reduce_stats")
+
+
+@pytest.mark.parametrize("C", [20, 64])
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("mode", ["train", "eval"])
+def test_frozen_encoder_same_dx_and_no_weight_gradient_work(mode, dtype, C, monkeypatch):
+    from speech_decoding_amd import ops
+    d = dict(TOY, C=C)
+    loc, P, X, Y, subj, enc = setup(d, dtype=dtype, training=mode == "train")
+    _, _, dx_full, _ = step(enc, X, Y, subj)
+    for p in enc.parameters():
+        p.requires_grad_(False)
+        p.grad = None
+    calls = []
+    enc.set_drop_centre(4)
+    Xl = X.to(DEV).requires_grad_(True)
+    loss = clip()(Y.to(DEV), enc(Xl, subj))
+    for name in WEIGHT_GRADIENT_WRAPPERS:
+        real = getattr(ops, name)
+        monkeypatch.setattr(ops, name, lambda *a, _n=name, _f=real, **k: (calls.append(_n), _f(*a, **k))[1])
+    loss.backward()
+    monkeypatch.undo()
+    assert calls == []
+    assert torch.equal(Xl.grad.double().cpu(), dx_full)
+    assert all(p.grad is None for p in enc.parameters())
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# 5. X without a gradient: nothing changes
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("C", [20, 64])
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_x_without_grad_same_bits_and_no_new_launch(C, dtype, monkeypatch):
+    from speech_decoding_amd import ops
+    d = dict(TOY, C=C)
+    runs = []
+    for x_grad in (True, False):
+        loc, P, X, Y, subj, enc = setup(d, dtype=dtype)
+        crit = clip()
+        if not x_grad:
+            def boom(*a, **k):
+                raise AssertionError("sda_input_grad launched for an X that needs no gradient")
+            monkeypatch.setattr(ops, "input_grad", boom)
+        loss, Z, _, _ = step(enc, X, Y, subj, x_grad=x_grad, crit=crit)
+        grads = {n: p.grad.detach().clone() for n, p in enc.named_parameters()}
+        grads["temp"] = crit.temp.grad.detach().clone()
+        stats = {k: v.clone() for k, v in enc.state_dict().items() if "running" in k}
+        runs.append((loss, Z.clone(), grads, stats))
+    (l1, z1, g1, s1), (l2, z2, g2, s2) = runs
+    assert torch.equal(l1, l2) and torch.equal(z1, z2)
+    for k in g1:
+        assert torch.equal(g1[k], g2[k]), k
+    for k in s1:
+        assert torch.equal(s1[k], s2[k]), k
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# 6. a no-grad forward between forward and backward
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("C", [20, 64])
+def test_no_grad_forward_in_between_leaves_dx_unchanged(C):
+    d = dict(TOY, C=C)
+    loc, P, X, Y, subj, enc = setup(d)
+    _, _, want, _ = step(enc, X, Y, subj)
+    enc.set_drop_centre(4)
+    Xl = X.to(DEV).requires_grad_(True)
+    loss = clip()(Y.to(DEV), enc(Xl, subj))
+    enc.eval()
+    with torch.no_grad():
+        X2, _, subj2 = O.synthetic_batch(d["B"], d["C"], d["T"], d["F"], d["S"], seed=99)
+        enc(X2.to(DEV), subj2)
+    enc.train()
+    loss.backward()
+    assert torch.equal(Xl.grad.double().cpu(), want)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# 7. joint training: a front end upstream of the encoder
+# ------------------------------------------------------------------------------------------------------------------------------
+def test_joint_front_end_adam_steps_match_cpu_float64():
+    d = TOY
+    loc = O.synthetic_positions(d["C"], seed=1)
+    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=2, loc=loc)
+    X, Y, subj = O.synthetic_batch(d["B"], d["C"], d["T"], d["F"], d["S"], seed=3)
+    torch.manual_seed(0)
+    front = torch.nn.Conv1d(d["C"], d["C"], 1)
+    front64 = torch.nn.Conv1d(d["C"], d["C"], 1)
+    front64.load_state_dict(front.state_dict())
+    front64 = front64.double()
+    w0 = front.weight.detach().clone()
+    enc = build_encoder(P, d, loc)
+    front = front.to(DEV)
+    crit = clip(2.0)
+    lr = 3e-4
+    opt = torch.optim.Adam(list(front.parameters()) + list(enc.parameters()) + list(crit.parameters()), lr=lr)
+    leaves = {k: (v.detach().to(torch.complex128) if v.is_complex() else v.detach().double()).clone().requires_grad_(True)
+              for k, v in P.items() if (v.is_floating_point() or v.is_complex())
+              and not k.endswith(("running_mean", "running_var", ".cos", ".sin"))}
+    Q = {k: (v.to(torch.complex128) if v.is_complex() else v.double()) if (v.is_floating_point() or v.is_complex()) else v
+         for k, v in P.items()}
+    t64 = torch.tensor([2.0], dtype=torch.float64, requires_grad=True)
+    opt64 = torch.optim.Adam(list(front64.parameters()) + list(leaves.values()) + [t64], lr=lr)
+    Xd, Yd = X.to(DEV), Y.to(DEV)
+    for s in range(3):
+        enc.set_drop_centre(4)
+        loss = crit(Yd, enc(front(Xd), subj))
+        opt.zero_grad()
+        loss.backward()
+        assert front.weight.grad is not None and float(front.weight.grad.abs().max()) > 0
+        opt.step()
+        Q.update(leaves)
+        Z64 = O.brain_encoder_forward(Q, front64(X.double()), subj, training=True, loc=loc.double(), drop_centre=4)
+        l64, _ = O.clip_loss(Y.double(), Z64, t64)
+        opt64.zero_grad()
+        l64.backward()
+        opt64.step()
+        assert abs(float(loss) - float(l64)) <= (1e-4 if s == 0 else 2e-3) * abs(float(l64)), (s, float(loss), float(l64))
+    lim = 3 * 4 * lr                                         # Adam moves noise-gradient entries by about lr per step
+    for (n, p), p64 in zip(front.named_parameters(), front64.parameters()):
+        assert float((p.detach().cpu().double() - p64.detach()).abs().max()) < lim, n
+    sd = enc.state_dict()
+    for k, v in leaves.items():
+        got, ref = sd[k].cpu(), v.detach()
+        if ref.is_complex():
+            got, ref = torch.view_as_real(got), torch.view_as_real(ref)
+        assert float((got.double() - ref).abs().max()) < lim, k
+    moved = (front.weight.detach().cpu() - w0).abs()          # the front end moved: X's gradient reached it
+    assert float(moved.max()) > 2 * lr
