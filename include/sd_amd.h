@@ -96,6 +96,10 @@ int sda_unpack_rows(const void* src, float* dst, int B, int C, int T, int Cp, in
 /* RL of `dtype` -> (B, C, T) contiguous of `dst_dtype` (fp32 / bf16 / fp16): the loss's speech-embedding gradient in the
  * argument's own dtype (one rounding when dst_dtype is narrower than dtype) */
 int sda_unpack_rows_typed(const void* src, void* dst, int B, int C, int T, int Cp, int dtype, int dst_dtype, void* stream);
+/* (B, C, T) contiguous of `src_dtype` (fp32 / bf16 / fp16) -> RL rows of Cp elements of `dtype`, one pass (no widened fp32 copy):
+ * the contract of sda_pack_rows — valid rows written with their channel padding zero-filled, pad rows NOT touched (the
+ * destination is zero-initialised).  Host pointers, unknown dtypes and Cp < C are refused before any launch. */
+int sda_pack_rows_typed(const void* src, void* dst, int B, int C, int T, int Cp, int src_dtype, int dtype, void* stream);
 
 /* per-sample sum of squares over an RL tensor viewed as B rows of `row_elems` contiguous elements with
  * pitch `pitch` (elements). out[b] fp32. `scratch` holds B*64 floats. */

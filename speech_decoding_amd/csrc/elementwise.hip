@@ -154,6 +154,65 @@ __global__ __launch_bounds__(256) void unpack_rows_kernel(const E* __restrict__ 
   }
 }
 
+// (B, C, T) of storage type S (fp32 / bf16 / fp16) -> RL rows of E in one pass: a 16-bit input is widened in registers, not
+// through an fp32 copy in HBM.  Widening is exact and the one rounding is to E, so the bits equal sda_pack_rows of the same
+// values.  A workgroup owns 64 channels x 64 time steps of one sample; valid rows get all Cp channels (the padding ones zero),
+// pad rows are not touched.
+template <typename S, typename E>
+__global__ __launch_bounds__(256) void pack_rows_typed_kernel(const S* __restrict__ src, E* __restrict__ dst, int C, int T, int Cp) {
+  __shared__ float tile[64][65];
+  const int b = blockIdx.z, c0 = blockIdx.y * 64, t0 = blockIdx.x * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  for (int cc = ty; cc < 64; cc += 4) {
+    const int c = c0 + cc, t = t0 + tx;
+    tile[cc][tx] = (c < C && t < T) ? Elem<S>::ld(src + ((size_t)b * C + c) * T + t) : 0.f;
+  }
+  __syncthreads();
+  for (int rr = ty; rr < 64; rr += 4) {
+    const int t = t0 + rr;
+    if (t < T) Elem<E>::st(dst + ((size_t)b * rows_tp(T) + PAD + t) * Cp + c0 + tx, tile[tx][rr]);
+  }
+}
+
+// The same for T % (16 / sizeof(S)) == 0 and a 16-byte aligned source: every load and store is 16 bytes.  Loads run along t
+// (a channel's 64 steps are 4 lanes x 64 B of bf16 / fp16 or 16 lanes x 16 B of fp32, so a wave reads whole 128 / 256-byte
+// runs), stores along c (8 channels of a 16-bit E per lane: a wave writes 8 rows x 128 B).
+template <typename S, typename E>
+__global__ __launch_bounds__(256) void pack_rows_typed_vec_kernel(const S* __restrict__ src, E* __restrict__ dst, int C, int T,
+                                                                  int Cp) {
+  __shared__ float tile[64][65];
+  constexpr int N = Vec16<S>::N, PER_RUN = 64 / N;          // source elements per load, loads per channel run of the tile
+  const int b = blockIdx.z, c0 = blockIdx.y * 64, t0 = blockIdx.x * 64;
+#pragma unroll
+  for (int k = 0; k < 64 * PER_RUN / 256; ++k) {
+    const int idx = threadIdx.x + 256 * k, cc = idx / PER_RUN, tn = (idx % PER_RUN) * N;
+    const int c = c0 + cc, t = t0 + tn;
+    float v[N];
+    if (c < C && t < T) {                              // (T % N == 0: the N steps are inside or outside together)
+      Vec16<S>::load(src + ((size_t)b * C + c) * T + t, v);
+    } else {
+#pragma unroll
+      for (int j = 0; j < N; ++j) v[j] = 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) tile[cc][tn + j] = v[j];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int item = threadIdx.x + 256 * k, chunk = item & 7, rr = item >> 3;
+    const int t = t0 + rr;
+    if (t < T) {
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = tile[chunk * 8 + j][rr];
+      E* out = dst + ((size_t)b * rows_tp(T) + PAD + t) * Cp + c0 + chunk * 8;
+      if constexpr (sizeof(E) == 4) { Vec16<E>::store(out, v); Vec16<E>::store(out + 4, v + 4); }
+      else Vec16<E>::store(out, v);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // per-sample sum of squares (loss.py:64-65 norms), two-stage
 // ------------------------------------------------------------------------------------------------
@@ -1033,6 +1092,43 @@ extern "C" int sda_unpack_rows_typed(const void* src, void* dst, int B, int C, i
                                            Cp));
   else { set_error("unpack_rows_typed: unknown output dtype %d", dst_dtype); return -1; }
   return check_launch("unpack_rows_typed");
+}
+
+// true for memory the current process allocated on a device (or managed memory); false for host memory, or with no device.
+// A failed query leaves a runtime error behind, which is cleared here so that the next launch check does not report it.
+static bool device_memory(const void* p) {
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
+}
+
+template <typename S>
+static int launch_pack_rows_typed(const S* src, void* dst, int B, int C, int T, int Cp, int dtype, hipStream_t st) {
+  dim3 grid((T + 63) / 64, Cp / 64, B);
+  if (T % Vec16<S>::N == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+    SDA_DISPATCH(dtype, hipLaunchKernelGGL((pack_rows_typed_vec_kernel<S, E>), grid, dim3(256), 0, st, src, (E*)dst, C, T, Cp));
+  } else {
+    SDA_DISPATCH(dtype, hipLaunchKernelGGL((pack_rows_typed_kernel<S, E>), grid, dim3(256), 0, st, src, (E*)dst, C, T, Cp));
+  }
+  return check_launch("pack_rows_typed");
+}
+
+extern "C" int sda_pack_rows_typed(const void* src, void* dst, int B, int C, int T, int Cp, int src_dtype, int dtype,
+                                   void* stream) {
+  if (!src || !dst || B < 1 || C < 1 || T < 1 || Cp % 64 || C > Cp || B > 65535) {
+    set_error("pack_rows_typed: bad arguments (need 1 <= C <= Cp, Cp a multiple of 64)"); return -1;
+  }
+  if (src_dtype < SDA_F32 || src_dtype > SDA_F16 || dtype < SDA_F32 || dtype > SDA_F16) {
+    set_error("pack_rows_typed: unknown dtype (source %d, destination %d)", src_dtype, dtype); return -1;
+  }
+  if (!device_memory(src) || !device_memory(dst)) { set_error("pack_rows_typed: src and dst must be device memory"); return -1; }
+  hipStream_t st = (hipStream_t)stream;
+  if (src_dtype == SDA_F32) return launch_pack_rows_typed((const float*)src, dst, B, C, T, Cp, dtype, st);
+  if (src_dtype == SDA_BF16) return launch_pack_rows_typed((const uint16_t*)src, dst, B, C, T, Cp, dtype, st);
+  return launch_pack_rows_typed((const half_t*)src, dst, B, C, T, Cp, dtype, st);
 }
 
 extern "C" int sda_rows_sumsq_from_stats(const float* stats, int tiles_per_sample, int Cp, float* out, int B, void* stream) {

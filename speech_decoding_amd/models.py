@@ -1,9 +1,13 @@
 """MI355X-native `BrainEncoder` / `Classifier` with the reference's constructor and forward signatures
-(speech_decoding/models.py:169-248) and state_dict keys.
+(speech_decoding/models.py:169-248) and state_dict keys, and the reference's submodules
+`SpatialAttention`, `SubjectBlock` and `ConvBlock`, which also run on their own.
 
-The modules below only HOLD parameters (so `.parameters()`, `.to()`, `.state_dict()`, Adam all work as
-with the reference); the forward and backward computations run in libsdamd.so through
-`engine.EncoderEngine` as ONE autograd node.  There is no PyTorch fallback for the math.
+All of them hold their parameters as the reference does (so `.parameters()`, `.to()`, `.state_dict()`, Adam all work as
+with the reference).  `BrainEncoder.forward` runs the whole encoder in libsdamd.so through `engine.EncoderEngine` as ONE
+autograd node: it does not call its submodules, so forward hooks registered on them do not fire inside `enc(X, s)`.
+Called on their own (`SpatialAttention(X)`, `SubjectBlock(X, subject_idxs)`, `ConvBlock(X)`), the three submodules run
+the stage schedules of `blocks.py`, one autograd node per call, and hand back a fresh row-layout buffer as a (B, C_out, T)
+view in their compute dtype.  There is no PyTorch fallback for the math.
 """
 from __future__ import annotations
 
@@ -19,6 +23,7 @@ from . import ops
 from .engine import EncoderDims, EncoderEngine, block_dilations
 from .layout import ch_locations_2d
 from . import loss as _loss
+from . import blocks as _blocks
 
 
 def _opt(args, key, default=None):
@@ -44,8 +49,103 @@ def _dp_group():
     return active_group()
 
 
+def _check_input(X, who: str, channels: int):
+    """The (B, C, T) device-tensor contract of the standalone submodules: the reference's shape checks first, then the device
+    (there is no CPU path, as elsewhere in the product) and the dtype."""
+    if not torch.is_tensor(X) or X.dim() != 3:
+        raise ValueError(f"{who}: X must be a (B, C, T) tensor")
+    if who == "ConvBlock":
+        if X.shape[1] != channels:
+            raise RuntimeError(f"ConvBlock: expected input to have {channels} channels, but got {X.shape[1]}")
+    else:
+        assert X.shape[1] == channels                                             # models.py:78
+    if not X.is_cuda:
+        raise L.SdaError(f"{who} needs X on the MI355X device (there is no CPU path)")
+    if X.dtype not in ops.COMPUTE_DTYPES:
+        raise L.SdaError(f"{who}: X of dtype {X.dtype}; the module takes float32, bfloat16 or float16")
+
+
+def _subject_indices(subject_idxs, B: int, S: int) -> np.ndarray:
+    """subject_idxs validated as the encoder validates them (a CPU int tensor in the reference, train.py:189)."""
+    sidx = torch.as_tensor(subject_idxs).detach().to("cpu").to(torch.int64).numpy()
+    if sidx.shape != (B,):
+        raise ValueError("subject_idxs must have shape (B,)")
+    if (sidx < 0).any() or (sidx >= S).any():
+        raise IndexError("subject index out of range")                # ModuleList semantics, models.py:115
+    return sidx
+
+
+class _SpatialAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, module, X, mask, need_grad, z):
+        y, c = _blocks.spatial_attention_forward(module, X, mask, need_grad)
+        ctx.module, ctx.bctx = module, c
+        ctx.dtype = module.compute_dtype
+        B, _, T = X.shape
+        return ops.rows_view(y, B, module.z.shape[0], T)
+
+    @staticmethod
+    def backward(ctx, dY):
+        module = ctx.module
+        dYt = _blocks.grad_rows(dY, module.z.shape[0], ctx.dtype)
+        dX, dz = _blocks.sa_backward(module, ctx.bctx, dYt, ctx.needs_input_grad[1], ctx.needs_input_grad[4])
+        return None, dX, None, None, dz
+
+
+class _SubjectBlockFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, module, X, sidx, mask, need_grad, want_subj, z, sb_w, sb_b, subj_w):
+        y, c = _blocks.subject_block_forward(module, X, sidx, mask, need_grad, want_subj)
+        if c is not None:
+            c.params = [sb_w, subj_w]                      # re-packed by the backward
+            c.versions = [p._version for p in c.params]
+        ctx.module, ctx.bctx = module, c
+        ctx.dtype = module.compute_dtype
+        B, _, T = X.shape
+        return ops.rows_view(y, B, module.D1, T)
+
+    @staticmethod
+    def backward(ctx, dY):
+        module, n = ctx.module, ctx.needs_input_grad
+        if ctx.dtype != module.compute_dtype:
+            raise L.SdaError("SubjectBlock: the compute dtype changed between forward and backward")
+        dYt = _blocks.grad_rows(dY, module.D1, ctx.dtype)
+        g = _blocks.subject_block_backward(module, ctx.bctx, dYt, dict(X=n[1], z=n[6], sb_w=n[7], sb_b=n[8], subj_w=n[9]))
+        return (None, g.get("X"), None, None, None, None, g.get("z"), g.get("sb_w"), g.get("sb_b"), g.get("subj_w"))
+
+
+class _ConvBlockFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, module, X, need_grad, *params):
+        y, c = _blocks.conv_block_forward(module, X, need_grad)
+        if c is not None:
+            c.params = list(params)
+            c.versions = [p._version for p in params]
+        ctx.module, ctx.bctx = module, c
+        ctx.dtype = module.compute_dtype
+        B, _, T = X.shape
+        return ops.rows_view(y, B, module.D2, T)
+
+    @staticmethod
+    def backward(ctx, dY):
+        module, c, n = ctx.module, ctx.bctx, ctx.needs_input_grad
+        if ctx.dtype != module.compute_dtype:
+            raise L.SdaError("ConvBlock: the compute dtype changed between forward and backward")
+        dYt = _blocks.grad_rows(dY, module.D2, ctx.dtype)
+        want = dict(zip(_blocks.CB_PARAMS, n[3:]), X=n[1])
+        g = _blocks.conv_block_backward(module, c, dYt, want)
+        dX = None
+        if "X" in g:
+            # an RL-view input (the output of another module) gets its gradient as an RL view of the same layout, which that
+            # module's backward consumes without a pack; a plain input gets a contiguous tensor of its own dtype
+            dX = (ops.rows_view(g["X"], c.B, module.in_channels, c.T) if c.x_rows
+                  else ops.unpack_rows_typed(g["X"], c.B, module.in_channels, c.T, c.x_dtype))
+        return (None, dX, None, *[g.get(name) for name in _blocks.CB_PARAMS])
+
+
 class SpatialAttention(nn.Module):
-    """Parameter holder for models.py:14-65: complex `z` (D1, K²) ~ U[0,1)+iU[0,1), buffers cos/sin (K², C)."""
+    """models.py:14-86: complex `z` (D1, K²) ~ U[0,1)+iU[0,1), buffers cos/sin (K², C), SpatialDropout in training mode.
+    `SpatialAttention(args)(X) -> (B, D1, T)` on HIP kernels (blocks.py), in the compute dtype of `args`."""
 
     def __init__(self, args):
         super().__init__()
@@ -60,6 +160,30 @@ class SpatialAttention(nn.Module):
         self.loc = loc                                                  # plain attribute, as in the reference
         self.d_drop = float(args.d_drop)
         self._tables_T = None
+        self.compute_dtype = resolve_dtype(args)
+        self._fixed_centre: Optional[int] = None
+
+    def set_compute_dtype(self, dtype: torch.dtype):
+        self.compute_dtype = dtype
+        return self
+
+    def set_drop_centre(self, centre: Optional[int]):
+        """Testing hook: pin SpatialDropout's centre instead of drawing it from np.random (models.py:81)."""
+        self._fixed_centre = centre
+
+    def dropout_mask(self, device) -> Optional[torch.Tensor]:
+        """SpatialDropout (models.py:77-86): in training mode one centre per call from NumPy's global RNG (or the pinned one),
+        as a row of the device-resident mask table; None (no dropout, no draw) in eval mode."""
+        if not self.training:
+            return None
+        centre = self._fixed_centre if self._fixed_centre is not None else int(np.random.randint(self.loc.shape[0]))
+        return self.device_masks(device)[centre]
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        _check_input(X, "SpatialAttention", self.loc.shape[0])
+        mask = self.dropout_mask(X.device)
+        need_grad = torch.is_grad_enabled() and (X.requires_grad or self.z.requires_grad)
+        return _SpatialAttentionFn.apply(self, X, mask, need_grad, self.z)
 
     def _tables_key(self):
         # rebuilt when the buffers move or are written in place (load_state_dict copies into them)
@@ -131,26 +255,61 @@ class SubjectLayers(nn.Module):
 
 
 class SubjectBlock(nn.Module):
+    """models.py:89-117: SpatialAttention, a shared 1x1 conv with bias, a per-subject 1x1 conv without bias.
+    `SubjectBlock(args)(X, subject_idxs) -> (B, D1, T)` on HIP kernels (blocks.py), in the compute dtype of `args`."""
+
     def __init__(self, args):
         super().__init__()
         D1 = int(args.D1)
+        self.num_subjects, self.D1, self.K = int(args.num_subjects), D1, int(args.K)
         self.spatial_attention = SpatialAttention(args)
         self.conv = nn.Conv1d(D1, D1, kernel_size=1, stride=1)
         self.subject_layer = SubjectLayers(int(args.num_subjects), D1)
+        self.compute_dtype = self.spatial_attention.compute_dtype
+
+    def set_compute_dtype(self, dtype: torch.dtype):
+        self.compute_dtype = dtype
+        self.spatial_attention.set_compute_dtype(dtype)
+        return self
+
+    def forward(self, X: torch.Tensor, subject_idxs) -> torch.Tensor:
+        sa = self.spatial_attention
+        _check_input(X, "SubjectBlock", sa.loc.shape[0])
+        sidx = _subject_indices(subject_idxs, X.shape[0], self.num_subjects)
+        mask = sa.dropout_mask(X.device)                     # the one draw of this call, through its SpatialAttention
+        params = [sa.z, self.conv.weight, self.conv.bias, self.subject_layer.weight]
+        grad_mode = torch.is_grad_enabled()
+        need_grad = grad_mode and (X.requires_grad or any(p.requires_grad for p in params))
+        want_subj = need_grad and self.subject_layer.weight.requires_grad
+        return _SubjectBlockFn.apply(self, X, sidx, mask, need_grad, want_subj, *params)
 
 
 class ConvBlock(nn.Module):
-    """Parameter holder for models.py:120-150."""
+    """models.py:120-166.  `ConvBlock(k, D1, D2)(X) -> (B, D2, T)` on HIP kernels (blocks.py).  With no `args` to read, its
+    compute dtype is resolve_dtype({}) (fp32 unless SDA_COMPUTE_DTYPE is set); `set_compute_dtype` changes it, and a
+    BrainEncoder sets its own on its blocks."""
 
     def __init__(self, k: int, D1: int, D2: int):
         super().__init__()
         cin = D1 if k == 0 else D2
+        self.k, self.D2, self.in_channels = k, D2, cin
+        self.compute_dtype = resolve_dtype({})
         d0, d1, d2 = block_dilations(k)
         self.conv0 = nn.Conv1d(cin, D2, kernel_size=3, padding="same", dilation=d0)
         self.batchnorm0 = nn.BatchNorm1d(D2)
         self.conv1 = nn.Conv1d(D2, D2, kernel_size=3, padding="same", dilation=d1)
         self.batchnorm1 = nn.BatchNorm1d(D2)
         self.conv2 = nn.Conv1d(D2, 2 * D2, kernel_size=3, padding="same", dilation=d2)
+
+    def set_compute_dtype(self, dtype: torch.dtype):
+        self.compute_dtype = dtype
+        return self
+
+    def forward(self, X: torch.Tensor) -> torch.Tensor:
+        _check_input(X, "ConvBlock", self.in_channels)
+        params = _blocks.cb_params(self)
+        need_grad = torch.is_grad_enabled() and (X.requires_grad or any(p.requires_grad for p in params))
+        return _ConvBlockFn.apply(self, X, need_grad, *params)
 
 
 class _EncoderFn(torch.autograd.Function):
@@ -203,6 +362,13 @@ class BrainEncoder(nn.Module):
         self.drop_centre_sync = "seed"        # under data parallelism: "seed" (identical np.random on all ranks, checked) | "broadcast"
         self._centre_draws = 0
         self._param_names = self._build_names()
+        self._set_children_dtype()
+
+    def _set_children_dtype(self):
+        """The submodules, when called on their own, compute in the encoder's dtype."""
+        self.subject_block.set_compute_dtype(self.compute_dtype)
+        for blk in self.conv_blocks:
+            blk.set_compute_dtype(self.compute_dtype)
 
     # ---- parameter plumbing -------------------------------------------------------------
     def _build_names(self) -> List[str]:
@@ -252,6 +418,7 @@ class BrainEncoder(nn.Module):
 
     def set_compute_dtype(self, dtype: torch.dtype):
         self.compute_dtype = dtype
+        self._set_children_dtype()
         return self
 
     def set_drop_centre(self, centre: Optional[int]):

@@ -199,6 +199,21 @@ def pack_rows(src: torch.Tensor, dst: torch.Tensor, ones_channel: Optional[int] 
                 "pack_rows_ones")
 
 
+def pack_rows_typed(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """Contiguous (B, C, T) fp32 / bf16 / fp16 -> RL buffer `dst` of its own dtype in one pass (sda_pack_rows_typed): a 16-bit
+    input is not widened to an fp32 copy first.  Valid rows and their channel padding are written, pad rows are not: `dst`
+    comes from new_rows / new_rows_uninit."""
+    _need_cuda(src, dst)
+    if src.dim() != 3 or not src.is_contiguous():
+        raise L.SdaError("pack_rows_typed: src must be a contiguous (B, C, T) tensor")
+    B, Cc, T = src.shape
+    if dst.dim() != 2 or not dst.is_contiguous() or dst.shape[0] < L.rows_alloc(B, T):
+        raise L.SdaError("pack_rows_typed: dst must be a row-layout buffer for (B, T)")
+    L.check(L.load().sda_pack_rows_typed(_p(src), _p(dst), B, Cc, T, dst.shape[1], dt_code(src.dtype), dt_code(dst.dtype), _st()),
+            "pack_rows_typed")
+    return dst
+
+
 def unpack_rows(src: torch.Tensor, B: int, Cc: int, T: int) -> torch.Tensor:
     _need_cuda(src)
     out = torch.empty((B, Cc, T), dtype=torch.float32, device=src.device)
