@@ -24,7 +24,6 @@ from .loss import _rows_base
 
 FWD_FLAGS = L.CONV_PAIR_TILES            # the forward k = 3 convs of the encoder: two tiles per workgroup share a weight slab
 BWD_FLAGS = L.CONV_WAVE_PRIO             # the data-gradient convs of the encoder's backward
-WGRAD_TARGET_WGS = 256                   # workgroups per weight-gradient launch (split over sample segments)
 
 
 # ------------------------------------------------------------------------------------------------------------- operands
@@ -56,21 +55,16 @@ def _new(B: int, T: int, Cp: int, dtype, dev) -> torch.Tensor:
     return ops.new_rows_uninit(B, T, Cp, dtype, dev)
 
 
-def _tile_m(Cout_p: int) -> int:
-    return 160 if Cout_p % 160 == 0 else (128 if Cout_p % 128 == 0 else 64)
-
-
-def _segments(B: int, ntiles: int, dev):
-    """Sample segments of a weight-gradient launch: consecutive samples, a multiple of 8 segments (one per XCD round)."""
-    nseg = 8 * max(1, round(WGRAD_TARGET_WGS / (8 * max(1, ntiles))))
-    nseg = int(min(B, nseg)) if B >= 8 else int(max(1, min(B, nseg)))
-    edges = np.floor(np.linspace(0, B, nseg + 1)).astype(np.int32)
-    return ops.UPLOADER.upload("blocks.seg", edges, dev), nseg
+def _segments(B: int, dy, x):
+    """Sample segments of the weight-gradient launch of (dy, x): consecutive samples, a multiple of 8 segments (one per XCD round)."""
+    # (64-column tiles for kernel size 1 as well, not the kernel's 128-column tile there: kept for bit-stability)
+    nseg = ops.uniform_segment_count(B, ops.wgrad_ntiles(dy.shape[1], x.shape[1], 64))
+    return ops.UPLOADER.upload("blocks.seg", ops.uniform_segment_edges(B, nseg), dy.device), nseg
 
 
 def _wgrad(dy, x, B, T, KS, dil, Cout, Cin, glu_half=0, glu_half_p=0) -> torch.Tensor:
     """Parameter-layout weight gradient (Cout, Cin, KS) fp32 of a conv with output gradient dy and input x (RL buffers)."""
-    seg, nseg = _segments(B, (dy.shape[1] // _tile_m(dy.shape[1])) * (x.shape[1] // 64), dy.device)
+    seg, nseg = _segments(B, dy, x)
     slabs = ops.wgrad_gemm(dy, x, B=B, T=T, KS=KS, dil=dil, seg_start=seg, nseg=nseg, alg_dims=(Cin, Cout), flat_rows=True)
     return ops.reduce_unpack_wgrad(slabs, Cout, Cin, KS, glu_half=glu_half, glu_half_p=glu_half_p)
 
@@ -117,7 +111,7 @@ def sa_backward(sa, c: SACtx, dY: torch.Tensor, want_x: bool, want_z: bool):
     dX = ops.input_grad(dY, c.Wp, None, c.B, Cc, c.T, c.x_dtype) if want_x else None
     dz = None
     if want_z:
-        seg, nseg = _segments(c.B, (dY.shape[1] // _tile_m(dY.shape[1])) * (c.Xt.shape[1] // 64), dY.device)
+        seg, nseg = _segments(c.B, dY, c.Xt)
         dWd = ops.reduce_slabs(ops.wgrad_gemm(dY, c.Xt, B=c.B, T=c.T, KS=1, dil=0, seg_start=seg, nseg=nseg))
         cosT, sinT = sa.transposed_tables()
         _, tab_b = sa.gemm_tables()
@@ -177,10 +171,9 @@ def subject_block_forward(sb, X: torch.Tensor, sidx: np.ndarray, mask, need_grad
         return y, None
     c = SBCtx(SACtx(B, T, Xt, W, Wp, mask, X.dtype), h_sa, h_c, widx)
     if want_subj_grad:
-        # samples sorted by subject, each subject's run cut into r slices so that the launch keeps ~WGRAD_TARGET_WGS workgroups
-        ntiles = (D1p // _tile_m(D1p)) * (D1p // 64)
-        present = max(1, int(np.unique(sidx).size))
-        r = int(max(1, min(max(1, B // present), round(WGRAD_TARGET_WGS / max(1, ntiles * present)))))
+        # samples sorted by subject, each subject's run cut into r slices so that the launch keeps ~ops.WGRAD_TARGET_WGS workgroups
+        # (64-column tiles; the engine's three-conv SubjectBlock counts 128 where D1p allows: kept apart for bit-stability)
+        r = ops.subject_slices(B, max(1, int(np.unique(sidx).size)), ops.wgrad_ntiles(D1p, D1p, 64))
         perm, seg = subject_segments(sidx, S, r)
         c.subj = (ops.UPLOADER.upload("blocks.subj_perm", perm, dev), ops.UPLOADER.upload("blocks.subj_seg", seg, dev), r)
     return y, c
@@ -316,7 +309,7 @@ def conv_block_backward(cb, c: CBCtx, dY: torch.Tensor, want: Dict[str, bool]) -
     dc2 = _new(B, T, 2 * D2p, dt, dev)
     if want["c2b"]:
         cs = ops.glu_backward_colsum(c.c2, dY, dc2, B, T, scratch)           # [sum d value | sum d gate], D2p apart
-        g["c2b"] = cs[: 2 * D2] if D2p == D2 else ops.unpack_vector(cs, 2 * D2, D2, D2p)
+        g["c2b"] = ops.bias_grad(cs, 2 * D2, glu_half=D2, glu_half_p=D2p)
     else:
         ops.glu_backward(c.c2, dY, dc2, B, T)
     if want["c2w"]:

@@ -6,6 +6,7 @@ import ctypes as C
 import os
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import lib as L
@@ -722,6 +723,50 @@ def colsum(x, B, T, scratch):
     return out
 
 
+# ---- launch planning of the weight gradients.  These numbers decide slab counts and therefore summation order (result bits):
+# the encoder's step (engine.py), the stand-alone blocks (blocks.py) and the tools all take them from here.
+WGRAD_TARGET_WGS = 256      # workgroups per weight-gradient launch, split over sample segments: one per CU, a sharp optimum
+                            # (160 +0.37 ms, 512 +0.2)
+
+
+def wgrad_tile_m(Cout_p: int) -> int:
+    """Row tile sda_wgrad_gemm picks for Cout_p output channels (mirrors dispatch_wgrad in wgrad_gemm.hip)."""
+    return 160 if Cout_p % 160 == 0 else (128 if Cout_p % 128 == 0 else 64)
+
+
+def wgrad_ntiles(Cout_p: int, Cin_p: int, tile_n: int = 64) -> int:
+    """Output tiles of one segment AS THE CALLER'S PLANNING COUNTS THEM: row tiles x (Cin_p / tile_n).  The kernel's own column
+    tile is 64 for kernel size 3 and 128 for kernel size 1 (Cin_p % 128 == 0); most call sites count 64 for both."""
+    return (Cout_p // wgrad_tile_m(Cout_p)) * (Cin_p // tile_n)
+
+
+def uniform_segment_count(B: int, ntiles: int) -> int:
+    """Sample segments of a weight-gradient launch with `ntiles` tiles per segment."""
+    # segments are dealt round-robin to the 8 XCDs (wgrad_gemm's block order), so use a multiple of 8
+    nseg = 8 * max(1, round(WGRAD_TARGET_WGS / (8 * max(1, ntiles))))
+    return int(min(B, nseg)) if B >= 8 else int(max(1, min(B, nseg)))
+
+
+def uniform_segment_edges(B: int, nseg: int) -> np.ndarray:
+    """int32 [nseg + 1] edges of `nseg` nearly equal runs of consecutive samples (no permutation: the kernel then needs no index
+    load in its chunk loop)."""
+    return np.floor(np.linspace(0, B, nseg + 1)).astype(np.int32)
+
+
+def subject_slices(B: int, present: int, ntiles: int) -> int:
+    """Slices r each subject's samples are cut into for the per-subject weight gradient (`present` subjects in the batch, `ntiles`
+    tiles per segment): with many subjects one slice each fills the GPU; with few, r slices keep ~WGRAD_TARGET_WGS workgroups."""
+    return int(max(1, min(max(1, B // present), round(WGRAD_TARGET_WGS / max(1, ntiles * present)))))
+
+
+def bias_grad(cs, C, glu_half=0, glu_half_p=0):
+    """Padded column sums -> bias gradient: a view when the unpadded vector is a prefix of the padded one (no GLU
+    split, or GLU halves without padding between them); the un-packing kernel otherwise."""
+    if glu_half == 0 or glu_half_p == glu_half:
+        return cs[:C]
+    return unpack_vector(cs, C, glu_half, glu_half_p)
+
+
 def wgrad_gemm(dy, x, *, B, T, KS, dil, perm=None, seg_start=None, nseg=1, alg_dims=None, flat_rows=False):
     """fp32 slabs (nseg, KS, Cout_p, Cin_p) of dy^T x over the RL rows of the samples in each segment.
     alg_dims = (Cin, Cout) unpadded, only used to count algorithmic FLOPs when the timer is on.
@@ -741,7 +786,7 @@ def wgrad_gemm(dy, x, *, B, T, KS, dil, perm=None, seg_start=None, nseg=1, alg_d
         raise L.SdaError("wgrad_gemm: nseg > 1 needs seg_start")
     if TIMER is not None and "wgrad_gemm" in TIMER.families:   # events go on the CURRENT stream (the side stream in backward)
         cin, cout = alg_dims if alg_dims is not None else (x.shape[1], dy.shape[1])
-        tile_m = 160 if dy.shape[1] % 160 == 0 else (128 if dy.shape[1] % 128 == 0 else 64)
+        tile_m = wgrad_tile_m(dy.shape[1])
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         L.check(L.load().sda_wgrad_gemm(C.byref(a), _st()), "wgrad_gemm")

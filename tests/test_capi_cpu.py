@@ -130,7 +130,7 @@ def test_no_kernel_of_the_library_spills_heavily(tmp_path):
     """Register spills inside a K loop cost a third of a kernel's speed and look like box-to-box noise in a step time (round 4:
     conv3_flat's rebuilt K loop spilled ~300 registers in its fp32 instantiation for half a round before anyone looked).  Reads
     the gfx950 code objects' metadata out of the built library: every kernel stays under 64 spilled registers, except the
-    instantiations listed here — which no default path launches (engine.flat_tiles_forward_fp32 = False)."""
+    instantiations listed here (none since round 5: the fp32 forward runs conv3_flat's 128-row instantiation by default)."""
     import re
     import shutil
     import subprocess

@@ -97,6 +97,7 @@ def test_layout_normalisation():
 
 
 def test_uniform_and_subject_segments():
+    from speech_decoding_amd import ops
     from speech_decoding_amd.engine import EncoderDims, EncoderEngine, block_dilations
     assert [block_dilations(k) for k in range(5)] == [(1, 2, 2), (4, 8, 2), (16, 1, 2), (2, 4, 2), (8, 16, 2)]
     eng = EncoderEngine(EncoderDims(208, 27, 270, 320, 1024, 32))
@@ -105,8 +106,23 @@ def test_uniform_and_subject_segments():
         seg = seg.numpy()
         assert seg[0] == 0 and seg[-1] == B and len(seg) == nseg + 1 and (np.diff(seg) >= 0).all()
         assert perm is None                                   # consecutive samples: no permutation table
+        assert (nseg, seg.tolist()) == (ops.uniform_segment_count(B, ntiles), ops.uniform_segment_edges(B, nseg).tolist())
     d = eng.d
     assert (d.Cp, d.D1p, d.D2p, d.F1p, d.Fp) == (256, 320, 320, 640, 1024)
+    # Slices per subject of the per-subject weight gradient, (B, subjects present) -> r, as each call site planned them before
+    # the arithmetic moved to ops.py (they decide slab counts, so result bits): the engine's composed SubjectBlock counts
+    # D2p x Cp tiles of the k = 3 gradient, its three-conv form and blocks.py D1p x D1p tiles of the 1 x 1 one
+    for C, cases in [(60, {(64, 1): (64, 26), (512, 1): (128, 26)}),                                  # BASELINE configs 1, 4
+                     (208, {(256, 27): (1, 1), (256, 7): (5, 4), (256, 1): (32, 26)}),                # config 2
+                     (306, {(512, 100): (1, 1), (512, 25): (1, 1), (512, 1): (26, 26)})]:             # config 5
+        Cp = -(-C // 64) * 64
+        for (B, present), (r_composed, r_three) in cases.items():
+            assert ops.subject_slices(B, present, ops.wgrad_ntiles(d.D2p, Cp, 64)) == r_composed
+            assert ops.subject_slices(B, present, ops.wgrad_ntiles(d.D1p, d.D1p, 128 if d.D1p % 128 == 0 else 64)) == r_three    # engine
+            assert ops.subject_slices(B, present, ops.wgrad_ntiles(d.D1p, d.D1p, 64)) == r_three                                 # blocks
+    # where D1p is a multiple of 128 the two three-conv call sites count different column tiles, on purpose (bit-stability)
+    assert ops.subject_slices(64, 1, ops.wgrad_ntiles(256, 256, 128)) == 64 and ops.subject_slices(64, 1, ops.wgrad_ntiles(256, 256, 64)) == 32
+    assert [ops.wgrad_tile_m(c) for c in (320, 640, 256, 1024, 192)] == [160, 160, 128, 128, 64]
 
 
 @pytest.mark.parametrize("S,r,B", [(27, 1, 256), (1, 26, 512), (3, 2, 8), (4, 5, 13), (2, 3, 2)])

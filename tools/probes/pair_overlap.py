@@ -9,7 +9,6 @@ wall time per (one launch of each) against the sum and the maximum of the two al
     U  = reduce_unpack_wgrad (slab sum of a weight gradient)"""
 import sys, os, math
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-import numpy as np
 import torch
 from speech_decoding_amd import ops, lib as L
 
@@ -35,14 +34,14 @@ coef = torch.cat([gamma, beta, mean, rstd]).contiguous()
 scratch = ops.reduce_scratch(2 * C, dev)
 
 
-def seg_for(ntiles, wgs=256):
-    nseg = 8 * max(1, round(wgs / (8 * ntiles)))
-    return torch.from_numpy(np.floor(np.linspace(0, B, nseg + 1)).astype(np.int32)).to(dev), nseg
+def seg_for(ntiles):
+    nseg = ops.uniform_segment_count(B, ntiles)
+    return torch.from_numpy(ops.uniform_segment_edges(B, nseg)).to(dev), nseg
 
 
 def mk_w(cout):
     d = dy if cout == C else dy2
-    seg, nseg = seg_for((cout // 160) * (C // 64))
+    seg, nseg = seg_for(ops.wgrad_ntiles(cout, C, 64))
     return lambda: ops.wgrad_gemm(d, x, B=B, T=T, KS=3, dil=4, perm=None, seg_start=seg, nseg=nseg, flat_rows=True)
 
 

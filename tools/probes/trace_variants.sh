@@ -1,5 +1,5 @@
 # Diagnostic: kernel trace + stream-level timeline of one steady-state step for several engine-switch settings, one box.
-# Usage on the GPU box: [BENCH_ARGS="--emulate-world 8"] bash tools/probes/trace_variants.sh <tag> "" "SDA_ENGINE_fuse_glu_backward=True" ...
+# Usage on the GPU box: [BENCH_ARGS="--emulate-world 8"] bash tools/probes/trace_variants.sh <tag> "" "SDA_ENGINE_fuse_glu_forward=False" ...
 TAG=$1; shift
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 i=0
