@@ -387,6 +387,21 @@ int sda_clip_dz(const void* G, long g_pitch, const void* Y, const void* Z, void*
                 const float* out_scale, int Bm, int Bn, long row_elems, int dtype, void* stream);
 /* cnt[i] = #{local j : logits[i][j] beats diag[i]} (ties: lower global index wins) — Classifier ranks */
 int sda_clip_ranks(const float* logits, const float* diag, int32_t* cnt, int Bm, int Bn, int col0, void* stream);
+/* Decoding against a candidate bank (csrc/retrieval.hip): top-k selection over the raw fp32 dot products of n query rows
+ * against M candidates, one pass over the matrix.  score[i][j] = S[i][j] / max(sqrt(qsq[i]) * sqrt(csq[j]), 1e-8) (the
+ * similarity of models.py:223-232; a zero row scores 0), ordered by score descending, on equal scores the lower j first
+ * (sda_clip_ranks' tie rule):
+ *     indices[i][r], scores[i][r]  (r < k, [n][k] int64 / fp32) = the k best candidates of row i, best first
+ *     ranks[i] (int32)             = #{j : j beats labels[i]} under the same order over all M columns (0 = top-1); -1 where
+ *                                    labels[i] lies outside [0, M).  labels (device int64 [n]) and ranks are both given or both NULL.
+ * S is CHUNK-MAJOR: columns come in chunks of `chunk_cols` (a multiple of 64); chunk c is a dense [n][pad64(its columns)]
+ * matrix at float offset c * n * chunk_cols — the output of one similarity GEMM per bank chunk (sda_sim_gemm / sda_conv_gemm
+ * split-K + sda_reduce_slabs).  chunk_cols >= M is the plain [n][pad64(M)] matrix; padding columns are ignored.
+ * sda_retrieval_scores_floats gives the number of floats S holds (-1: bad arguments).  1 <= k <= min(64, M); S 16-byte
+ * aligned.  Null pointers and out-of-range sizes are refused before any launch.  Deterministic. */
+long sda_retrieval_scores_floats(int n, int M, int chunk_cols);
+int sda_retrieval_select(const float* S, const float* qsq, const float* csq, const int64_t* labels, int64_t* indices,
+                         float* scores, int32_t* ranks, int n, int M, int k, int chunk_cols, void* stream);
 /* data parallelism: merge of the per-rank row statistics of the loss (all = the all-gathered [world][3][Bg] table of
  * (row max, row sum exp(l - max), positive's logit or 0) over each rank's block of brain columns): lse[i] = log-sum-exp of global
  * speech row i over the columns of ALL ranks, diag[i] = its positive's logit (utils/loss.py:79's two cross-entropies at the

@@ -494,6 +494,16 @@ class Classifier(nn.Module):
         return _loss.retrieval_ranks(Y, Z, self.global_candidates)
 
     @torch.no_grad()
+    def decode(self, Z: torch.Tensor, bank, k: int = 10, labels=None):
+        """Decode brain segments against a speech bank: the QUERIES are the brain embeddings Z (N, F, T), the CANDIDATES the
+        speech segments of `bank` (a retrieval.SpeechBank); returns retrieval.retrieve(Z, bank, k, labels) — for each brain
+        segment the k best speech candidates and, with `labels`, the rank of the one it heard.  forward() looks the other
+        way (for each speech row, the brain columns of the batch); retrieve() serves either direction, it does not care which
+        side is which."""
+        from .retrieval import retrieve
+        return retrieve(Z, bank, k=k, labels=labels)
+
+    @torch.no_grad()
     def forward(self, Z: torch.Tensor, Y: torch.Tensor, test: bool = False):
         cnt = self.ranks(Z, Y).cpu().numpy()
         return float((cnt == 0).mean()), np.mean(cnt < 10)

@@ -562,41 +562,55 @@ def conv_stats_rows(B: int, T: int, KS: int, Cout_p: int, flags: int = 0) -> int
 SIM_GEMM_TILES256 = os.environ.get("SDA_SIM_GEMM", "1") != "0"
 
 
-def matmul_nt_splitk(xm: torch.Tensor, wm: torch.Tensor, M: int, N: int, K: int, pitch: int) -> torch.Tensor:
-    """S[i][j] = sum_k xm[i][k] * wm[j][k] (both K-contiguous rows with `pitch`), fp32 (M, pad64(N)) result.
-    Runs conv_gemm in split-K mode + ordered slab reduction (loss.py:68)."""
+def splitk_plan(dtype, M: int, N: int, K: int, pitch: int):
+    """(tiles256, ksplit) matmul_nt_splitk runs an (M x N) product over K with: sim_gemm.hip's 256 x 256 tiles (16-bit storage) or
+    conv_gemm's split-K matrix mode, and the number of K slices."""
     Np = L.pad_channels(N)
     if SIM_GEMM_TILES256 and K <= pitch:
         # 16-bit storage: 256 x 256 output tiles, every operand byte of a K slice through LDS once (csrc/sim_gemm.hip)
-        ks = L.load().sda_sim_gemm_ksplit(M, N, K, dt_code(xm.dtype))
+        ks = L.load().sda_sim_gemm_ksplit(M, N, K, dt_code(dtype))
         if ks > 0:
-            partial = torch.empty((ks, M, Np), dtype=torch.float32, device=xm.device)
-            L.check(L.load().sda_sim_gemm(_p(xm), _p(wm), _p(partial), M, N, Np, K, pitch, ks, dt_code(xm.dtype), _st()), "sim_gemm")
-            if ks == 1:
-                return partial[0]
-            out = torch.empty((M, Np), dtype=torch.float32, device=xm.device)
-            L.check(L.load().sda_reduce_slabs(_p(partial), _p(out), ks, M * Np, _st()), "reduce_slabs")
-            return out
-    slab = 32 if xm.dtype == torch.float32 else 64
+            return True, ks
+    slab = 32 if dtype == torch.float32 else 64
     nslab = K // slab
     tile_co = 160 if Np % 160 == 0 else (128 if Np % 128 == 0 else 64)
     tiles = ((M + 127) // 128) * (Np // tile_co)
     ksplit = max(1, min(nslab, (512 + tiles - 1) // tiles))
     if nslab <= 64:                 # a short contraction (SpatialAttention's weights: 2048 deep, 270 x 256 outputs): the slab sum
         ksplit = min(ksplit, 16)    # has few threads, each walking every slab — 64 slabs cost 30 us on the step's start chain
-    partial = torch.empty((ksplit, M, Np), dtype=torch.float32, device=xm.device)
-    a = L.ConvArgs()
-    a.x, a.w, a.bias, a.res, a.y, a.y_pre, a.widx, a.stats = _p(xm), _p(wm), None, None, None, None, None, None
-    a.partial = _p(partial)
-    a.B, a.T, a.Cin_p, a.Cout_p, a.KS, a.dil = 1, M, K, Np, 1, 0
-    a.x_pitch, a.w_pitch, a.x_row0, a.x_sample_rows, a.x_rows_limit = pitch, pitch, 0, 0, M
-    a.w_rows_limit, a.ksplit, a.flags, a.dtype = N, ksplit, 0, dt_code(xm.dtype)
-    L.check(L.load().sda_conv_gemm(C.byref(a), _st()), "conv_gemm(split-K)")
-    if ksplit == 1:
-        return partial[0]
-    out = torch.empty((M, Np), dtype=torch.float32, device=xm.device)
-    L.check(L.load().sda_reduce_slabs(_p(partial), _p(out), ksplit, M * Np, _st()), "reduce_slabs")
+    return False, ksplit
+
+
+def matmul_nt_splitk_into(xm: torch.Tensor, wm: torch.Tensor, M: int, N: int, K: int, pitch: int, tiles256: bool, ksplit: int,
+                          partial: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """matmul_nt_splitk with the plan, the K-slice scratch (ksplit * M * pad64(N) floats; unused when ksplit == 1) and the
+    destination (M * pad64(N) floats, contiguous) given by the caller.  Any 1 <= ksplit <= K slabs is served; the sum over the
+    slices is ordered, so one ksplit always gives the same bits."""
+    Np = L.pad_channels(N)
+    dst = out if ksplit == 1 else partial
+    if tiles256:
+        L.check(L.load().sda_sim_gemm(_p(xm), _p(wm), _p(dst), M, N, Np, K, pitch, ksplit, dt_code(xm.dtype), _st()), "sim_gemm")
+    else:
+        a = L.ConvArgs()
+        a.x, a.w, a.bias, a.res, a.y, a.y_pre, a.widx, a.stats = _p(xm), _p(wm), None, None, None, None, None, None
+        a.partial = _p(dst)
+        a.B, a.T, a.Cin_p, a.Cout_p, a.KS, a.dil = 1, M, K, Np, 1, 0
+        a.x_pitch, a.w_pitch, a.x_row0, a.x_sample_rows, a.x_rows_limit = pitch, pitch, 0, 0, M
+        a.w_rows_limit, a.ksplit, a.flags, a.dtype = N, ksplit, 0, dt_code(xm.dtype)
+        L.check(L.load().sda_conv_gemm(C.byref(a), _st()), "conv_gemm(split-K)")
+    if ksplit > 1:
+        L.check(L.load().sda_reduce_slabs(_p(partial), _p(out), ksplit, M * Np, _st()), "reduce_slabs")
     return out
+
+
+def matmul_nt_splitk(xm: torch.Tensor, wm: torch.Tensor, M: int, N: int, K: int, pitch: int) -> torch.Tensor:
+    """S[i][j] = sum_k xm[i][k] * wm[j][k] (both K-contiguous rows with `pitch`), fp32 (M, pad64(N)) result.
+    Runs conv_gemm in split-K mode + ordered slab reduction (loss.py:68)."""
+    Np = L.pad_channels(N)
+    tiles256, ksplit = splitk_plan(xm.dtype, M, N, K, pitch)
+    partial = torch.empty((ksplit, M, Np), dtype=torch.float32, device=xm.device)
+    out = partial[0] if ksplit == 1 else torch.empty((M, Np), dtype=torch.float32, device=xm.device)
+    return matmul_nt_splitk_into(xm, wm, M, N, K, pitch, tiles256, ksplit, partial, out)
 
 
 def bn_finalize(partial, ntiles, count, gamma, beta, running_mean, running_var, Cp, training, eps=1e-5, momentum=0.1,
@@ -947,6 +961,41 @@ def clip_ranks(logits, diag, col0):
     cnt = torch.empty(Bm, dtype=torch.int32, device=logits.device)
     L.check(L.load().sda_clip_ranks(_p(logits), _p(diag), _p(cnt), Bm, Bn, col0, _st()), "clip_ranks")
     return cnt
+
+
+def retrieval_scores_floats(n: int, M: int, chunk_cols: int) -> int:
+    """Floats of the chunk-major score matrix sda_retrieval_select reads for n query rows against M candidates."""
+    r = L.load().sda_retrieval_scores_floats(n, M, chunk_cols)
+    if r < 0:
+        L.check(-1, "retrieval_scores_floats")
+    return r
+
+
+def retrieval_select(S, qsq, csq, n: int, M: int, k: int, chunk_cols: Optional[int] = None, labels=None, indices=None, scores=None,
+                     ranks=None):
+    """Top-k of n query rows over the raw dot products S (chunk-major, see sd_amd.h; chunk_cols None = one [n][pad64(M)] matrix)
+    with the squared norms qsq [n], csq [M] -> (indices (n, k) int64, scores (n, k) fp32, ranks (n,) int32 or None).  `labels`:
+    n int64 candidate indices on the device.  The three outputs may be handed in (contiguous row blocks of larger results)."""
+    _need_cuda(S, qsq, csq, labels)
+    chunk_cols = L.pad_channels(M) if chunk_cols is None else chunk_cols
+    if S.dtype != torch.float32 or not S.is_contiguous() or S.numel() < retrieval_scores_floats(n, M, chunk_cols):
+        raise L.SdaError("retrieval_select: S must be a contiguous fp32 buffer of retrieval_scores_floats(n, M, chunk_cols) floats")
+    for t, cnt, name in ((qsq, n, "qsq"), (csq, M, "csq")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < cnt:
+            raise L.SdaError(f"retrieval_select: {name} must hold {cnt} contiguous fp32 values")
+    if labels is not None and (labels.dtype != torch.int64 or not labels.is_contiguous() or labels.numel() < n):
+        raise L.SdaError("retrieval_select: labels must hold n contiguous int64 indices")
+    dev = S.device
+    indices = torch.empty((n, k), dtype=torch.int64, device=dev) if indices is None else indices
+    scores = torch.empty((n, k), dtype=torch.float32, device=dev) if scores is None else scores
+    if labels is not None and ranks is None:
+        ranks = torch.empty(n, dtype=torch.int32, device=dev)
+    for t, dt, cnt in ((indices, torch.int64, n * k), (scores, torch.float32, n * k), (ranks, torch.int32, n)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous() or t.numel() < cnt or not t.is_cuda):
+            raise L.SdaError("retrieval_select: an output buffer has the wrong dtype, size or layout")
+    L.check(L.load().sda_retrieval_select(_p(S), _p(qsq), _p(csq), _p(labels), _p(indices), _p(scores),
+                                          _p(ranks) if labels is not None else None, n, M, k, chunk_cols, _st()), "retrieval_select")
+    return indices, scores, (ranks if labels is not None else None)
 
 
 # ---------------------------------------------------------------------------------------------------------------

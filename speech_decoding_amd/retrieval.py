@@ -1,0 +1,217 @@
+"""Decoding: which of M speech segments did this brain segment hear?
+
+The training path only ever ranks a square batch against itself (`Classifier.forward`, loss.retrieval_ranks).  This module
+is its forward-only counterpart for a trained encoder: a resident bank of candidate segments (`SpeechBank`) and `retrieve`,
+which scores N query segments against all M candidates and returns the k best of each, and, given the true candidates, their
+ranks over the whole bank.  The score is the reference's similarity (models.py:223-232), <q, c> / max(|q| |c|, 1e-8).
+
+Everything runs in libsdamd.so: the pack and the norms (sda_pack_rows, sda_rows_sumsq), the similarity GEMM of the loss
+(ops.matmul_nt_splitk's two kernels, rectangular) and one selection launch per block of queries (csrc/retrieval.hip).  The
+N x M score matrix is never held whole: see plan_blocks.  Which side is "query" is the caller's choice — brain segments against
+a speech bank (`Classifier.decode`) or the other way round; under torch.distributed every rank decodes its own queries
+against its own bank and no collective is issued.  No gradients: both entry points run under no_grad.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import lib as L
+from . import loss as _loss
+from . import ops
+
+MAX_K = 64          # the selection kernel keeps the 64 best candidates of a row
+
+
+class Retrieval(NamedTuple):
+    """indices (N, k) int64: bank rows of the k best candidates, best first (score descending, lower index first on equal
+    scores); scores (N, k) fp32: their cosine similarities; ranks (N,) int32 or None: candidates that beat the labelled one
+    over the whole bank (0 = top-1; -1 for a device label outside the bank).  All on the device."""
+    indices: torch.Tensor
+    scores: torch.Tensor
+    ranks: Optional[torch.Tensor]
+
+    def accuracy(self, k: int) -> float:
+        """Share of queries whose true candidate is among the k best (reads the ranks back)."""
+        if self.ranks is None:
+            raise ValueError("Retrieval.accuracy: retrieve() was called without labels")
+        return float((self.ranks < k).float().mean())
+
+
+class SpeechBank:
+    """M candidate segments, resident on the device in the loss's row layout: every candidate is one contiguous row of
+    rows_tp(T) * pad_channels(F) elements of `dtype` (padding zero), with its fp32 squared norm beside it.  A bank filled by
+    several add() calls holds the same bytes and norms as one filled at once."""
+
+    def __init__(self, F: int, T: int, dtype=torch.bfloat16, device="cuda", capacity: Optional[int] = None):
+        if int(F) < 1 or int(T) < 1:
+            raise ValueError(f"SpeechBank: F and T must be positive, got F={F}, T={T}")
+        if dtype not in ops.COMPUTE_DTYPES:
+            raise ValueError(f"SpeechBank: dtype {dtype}; a bank holds float32, bfloat16 or float16")
+        if capacity is not None and int(capacity) < 0:
+            raise ValueError("SpeechBank: capacity must not be negative")
+        self.F, self.T, self.dtype = int(F), int(T), dtype
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.SdaError("SpeechBank lives on the MI355X device (there is no CPU path)")
+        self.row_elems = L.rows_tp(self.T) * L.pad_channels(self.F)
+        self._size = 0
+        self._capacity = 0
+        self._rows = None               # (capacity * row_elems,) of dtype
+        self._sq = None                 # (capacity,) fp32
+        if capacity:
+            self._reserve(int(capacity))
+
+    @classmethod
+    def from_tensor(cls, Y: torch.Tensor, dtype=torch.bfloat16) -> "SpeechBank":
+        if not torch.is_tensor(Y) or Y.dim() != 3:
+            raise ValueError("SpeechBank.from_tensor: Y must be an (M, F, T) tensor")
+        if not Y.is_cuda:
+            raise L.SdaError("SpeechBank.from_tensor: Y must live on the MI355X device (there is no CPU path)")
+        bank = cls(Y.shape[1], Y.shape[2], dtype=dtype, device=Y.device, capacity=Y.shape[0])
+        bank.add(Y)
+        return bank
+
+    def __len__(self) -> int:
+        return self._size
+
+    @property
+    def rows(self) -> torch.Tensor:
+        """(M, row_elems) view of the stored candidates."""
+        return self._rows[: self._size * self.row_elems].view(self._size, self.row_elems)
+
+    @property
+    def norms_sq(self) -> torch.Tensor:
+        """(M,) fp32 squared norms of the stored (rounded) candidates."""
+        return self._sq[: self._size]
+
+    def _reserve(self, capacity: int):
+        if capacity <= self._capacity:
+            return
+        L.load()
+        rows = torch.empty(capacity * self.row_elems, dtype=self.dtype, device=self.device)
+        sq = torch.empty(capacity, dtype=torch.float32, device=self.device)
+        if self._size:
+            rows[: self._size * self.row_elems].copy_(self._rows[: self._size * self.row_elems])
+            sq[: self._size].copy_(self._sq[: self._size])
+        self._rows, self._sq, self._capacity = rows, sq, capacity
+
+    @torch.no_grad()
+    def add(self, Y: torch.Tensor) -> range:
+        """Append the m candidates of Y (m, F, T) — fp32, bf16 or fp16, any strides, or the zero-copy view an encoder
+        returns — and return the bank indices they received."""
+        if not torch.is_tensor(Y) or Y.dim() != 3 or tuple(Y.shape[1:]) != (self.F, self.T):
+            got = tuple(Y.shape) if torch.is_tensor(Y) else type(Y).__name__
+            raise ValueError(f"SpeechBank.add: expected (m, {self.F}, {self.T}), got {got}")
+        if not Y.is_cuda:
+            raise L.SdaError("SpeechBank.add: Y must live on the MI355X device (there is no CPU path)")
+        if Y.device != self.device and not (self.device.index is None and Y.device.index == torch.cuda.current_device()):
+            raise L.SdaError(f"SpeechBank.add: Y is on {Y.device}, the bank on {self.device}")
+        if Y.dtype not in ops.COMPUTE_DTYPES:
+            raise L.SdaError(f"SpeechBank.add: Y of dtype {Y.dtype}; candidates are float32, bfloat16 or float16")
+        m, first, re = Y.shape[0], self._size, self.row_elems
+        if m == 0:
+            return range(first, first)
+        if first + m > self._capacity:
+            self._reserve(max(first + m, 2 * self._capacity))
+        packed = _loss.as_rows(Y, m, self.F, self.T, self.dtype, "SpeechBank.add: Y")        # pad rows and channels zero
+        self._rows[first * re: (first + m) * re].copy_(packed.reshape(-1)[: m * re])
+        self._sq[first: first + m].copy_(ops.rows_sumsq(packed, m, re, re))
+        self._size = first + m
+        return range(first, first + m)
+
+
+def plan_blocks(N: int, M: int, K: int, dtype, scratch_bytes: int):
+    """(nb, mc, tiles256, ksplit): queries are decoded nb rows at a time; a block's raw scores over the WHOLE bank are held
+    (nb x pad64(M) fp32, at most half of scratch_bytes), filled by one GEMM per chunk of mc bank rows, each in `ksplit` K slices
+    whose partial sums (ksplit x nb x mc fp32, not needed when ksplit is 1) take the rest.  Every (block, chunk) pair is
+    multiplied once, so the GEMM work does not depend on the blocking.  mc starts at the whole bank and is halved (in multiples
+    of 256, the GEMM's tile) while the K slices the GEMM would like do not fit; what still does not fit is run in fewer slices.
+    The plan depends only on its arguments and the device's CU count, so one call always computes the same bits."""
+    Mp = L.pad_channels(M)
+    if scratch_bytes < 8 * Mp:
+        raise ValueError(f"retrieve: scratch_bytes={scratch_bytes} does not hold one query's scores over the bank twice ({8 * Mp} bytes)")
+    nb = min(N, scratch_bytes // 2 // (4 * Mp))
+    if nb >= 256:
+        nb = nb // 256 * 256
+    budget = scratch_bytes - 4 * nb * Mp
+    mc = Mp
+    if dtype == torch.float32:
+        # fp32 storage runs on conv_gemm's matrix mode: a chunk's operand stays inside 2 GB, the spans that mode is run at
+        mc = min(mc, max(64, ((1 << 31) // (4 * K)) // 64 * 64))
+    while True:
+        tiles256, ks = ops.splitk_plan(dtype, nb, min(mc, M), K, K)
+        if ks == 1 or 4 * ks * nb * mc <= budget or mc <= 256:
+            break
+        mc = max(256, (mc // 2 + 255) // 256 * 256)
+    ks = max(1, min(ks, budget // (4 * nb * mc)))
+    return nb, mc, tiles256, ks
+
+
+def _checked_labels(labels, N: int, M: int):
+    """Device labels as an int64 device tensor; host labels, range-checked, as an int64 numpy array (uploaded later)."""
+    if torch.is_tensor(labels) and labels.is_cuda:
+        if labels.dim() != 1 or labels.shape[0] != N or labels.dtype.is_floating_point or labels.dtype == torch.bool:
+            raise ValueError(f"retrieve: labels must be {N} integer bank indices")
+        return labels.to(torch.int64).contiguous()          # checked by the kernel: a value outside the bank gives rank -1
+    arr = labels.detach().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    if arr.shape != (N,) or arr.dtype.kind not in "iu":
+        raise ValueError(f"retrieve: labels must be {N} integer bank indices")
+    if (arr < 0).any() or (arr >= M).any():
+        raise IndexError(f"retrieve: label outside the bank's [0, {M})")
+    return arr.astype(np.int64)
+
+
+@torch.no_grad()
+def retrieve(queries: torch.Tensor, bank: SpeechBank, k: int = 10, labels=None, scratch_bytes: int = 1 << 30) -> Retrieval:
+    """Score the N segments of `queries` (N, F, T) against every candidate of `bank` and return the k best of each
+    (Retrieval); with `labels` (N integer bank indices, host or device) also the rank of each query's true candidate over the
+    whole bank.  Labels on the host are checked here (IndexError); labels on the device are checked by the kernel, which
+    reports -1 for one outside the bank, because nothing is read back: the results are device tensors.  `scratch_bytes`
+    bounds the temporary memory (plan_blocks); the same call with the same arguments returns the same bits."""
+    if not isinstance(bank, SpeechBank):
+        raise ValueError("retrieve: bank must be a SpeechBank")
+    if not torch.is_tensor(queries) or queries.dim() != 3 or queries.shape[0] < 1:
+        raise ValueError("retrieve: queries must be an (N, F, T) tensor with N >= 1")
+    N, F, T = queries.shape
+    if (F, T) != (bank.F, bank.T):
+        raise ValueError(f"retrieve: queries are (N, {F}, {T}), the bank holds ({bank.F}, {bank.T}) segments")
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= MAX_K:
+        raise ValueError(f"retrieve: k={k} outside 1 ... {MAX_K}")
+    M, k = len(bank), int(k)
+    if M == 0:
+        raise ValueError("retrieve: the bank is empty")
+    if k > M:
+        raise ValueError(f"retrieve: k={k} outside 1 ... min({MAX_K}, M={M})")
+    if labels is not None:
+        labels = _checked_labels(labels, N, M)
+    K = bank.row_elems
+    nb, mc, tiles256, ks = plan_blocks(N, M, K, bank.dtype, int(scratch_bytes))
+    if not queries.is_cuda:
+        raise L.SdaError("retrieve: queries must live on the MI355X device (there is no CPU path)")
+    if queries.device != bank.rows.device:
+        raise L.SdaError(f"retrieve: queries are on {queries.device}, the bank on {bank.rows.device}")
+    if queries.dtype not in ops.COMPUTE_DTYPES:
+        raise L.SdaError(f"retrieve: queries of dtype {queries.dtype}; segments are float32, bfloat16 or float16")
+    dev = queries.device
+    if isinstance(labels, np.ndarray):
+        labels = ops.upload_small(labels, dev)
+
+    Qt = _loss.as_rows(queries, N, F, T, bank.dtype, "retrieve: queries").reshape(-1)
+    qsq = ops.rows_sumsq(Qt, N, K, K)
+    Bt, csq = bank.rows.reshape(-1), bank.norms_sq
+    S = torch.empty(ops.retrieval_scores_floats(nb, M, mc), dtype=torch.float32, device=dev)
+    partial = torch.empty(ks * nb * mc if ks > 1 else 0, dtype=torch.float32, device=dev)
+    indices = torch.empty((N, k), dtype=torch.int64, device=dev)
+    scores = torch.empty((N, k), dtype=torch.float32, device=dev)
+    ranks = torch.empty(N, dtype=torch.int32, device=dev) if labels is not None else None
+    for i0 in range(0, N, nb):
+        n = min(nb, N - i0)
+        for c0 in range(0, M, mc):
+            m = min(mc, M - c0)
+            ops.matmul_nt_splitk_into(Qt[i0 * K:], Bt[c0 * K:], n, m, K, K, tiles256, ks, partial, S[(c0 // mc) * n * mc:])
+        ops.retrieval_select(S, qsq[i0:], csq, n, M, k, mc, labels=None if labels is None else labels[i0:],
+                             indices=indices[i0:], scores=scores[i0:], ranks=None if ranks is None else ranks[i0:])
+    return Retrieval(indices, scores, ranks)

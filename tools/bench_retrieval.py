@@ -1,0 +1,171 @@
+"""Times decoding against a speech bank (speech_decoding_amd/retrieval.py) on the MI355X: the bank build, the similarity GEMM,
+the selection kernel and the whole retrieve(), each beside plain torch on the same device and the same operands (the library
+GEMM on the same packed rows with a 16-bit result widened to fp32, `topk` of the normalised matrix) as a library baseline.  Device events after warm-up; the two sides
+alternate inside one run.
+
+    python tools/bench_retrieval.py [--M 4096 32768] [--N 256] [--F 1024] [--T 360] [--dtype bf16] [--k 10] [--limit 420]
+
+Every bank size runs in a process of its own under a time limit of its own (--limit seconds); after a size that fails or runs
+out of time no further size is started.  Prints one JSON line per size (kept as profiles/retrieval_bench.json), times in
+milliseconds per call.  The M = 32768 bank of the default shape takes about 24 GB."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def timed(fns, iters, warmup, reps=1):
+    """Milliseconds per call of each callable: warm-up, then `iters` rounds that alternate the callables, events around `reps`
+    back-to-back calls of one of them (short kernels: the events' own resolution is a few microseconds)."""
+    import torch
+    for _ in range(warmup):
+        for f in fns:
+            f()
+    torch.cuda.synchronize()
+    total = [0.0] * len(fns)
+    for _ in range(iters):
+        for i, f in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                f()
+            b.record()
+            b.synchronize()
+            total[i] += a.elapsed_time(b)
+    return [t / (iters * reps) for t in total]
+
+
+def one_size(a, M):
+    import torch
+    from speech_decoding_amd import SpeechBank, retrieve, lib as L, ops
+    from speech_decoding_amd.retrieval import plan_blocks
+    dev = "cuda:0"
+    dt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[a.dtype]
+    N, F, T, k = a.N, a.F, a.T, a.k
+    g = torch.Generator(device=dev).manual_seed(5)
+    # bank build: batches of wav2vec2-sized output, timed per add() (pack + norms + the copy into the bank)
+    bank = SpeechBank(F, T, dtype=dt, device=dev, capacity=M)
+    batch, build_ms = 512, 0.0
+    labels = torch.randint(M, (N,), generator=g, device=dev)
+    queries = torch.randn((N, F, T), generator=g, device=dev)
+    for m0 in range(0, M, batch):
+        Y = torch.randn((min(batch, M - m0), F, T), generator=g, device=dev)
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        bank.add(Y)
+        e.record()
+        e.synchronize()
+        if m0:                                        # the first add loads the code objects
+            build_ms += s.elapsed_time(e)
+        del Y
+    build_rows = M - min(batch, M)
+    K = bank.row_elems
+    nb, mc, tiles256, ks = plan_blocks(N, M, K, dt, a.scratch)
+    n = min(nb, N)
+    Qt = ops.new_rows(N, T, L.pad_channels(F), dt, dev)
+    ops.pack_rows(queries, Qt)
+    Qt = Qt.reshape(-1)
+    qsq = ops.rows_sumsq(Qt, N, K, K)
+    Bt, csq = bank.rows.reshape(-1), bank.norms_sq
+    S = torch.empty(ops.retrieval_scores_floats(n, M, mc), dtype=torch.float32, device=dev)
+    partial = torch.empty(ks * n * mc if ks > 1 else 0, dtype=torch.float32, device=dev)
+
+    def gemm():
+        for c0 in range(0, M, mc):
+            ops.matmul_nt_splitk_into(Qt, Bt[c0 * K:], n, min(mc, M - c0), K, K, tiles256, ks, partial, S[(c0 // mc) * n * mc:])
+
+    Qm, Bm = Qt[: n * K].view(n, K), bank.rows
+
+    def torch_gemm():
+        return (Qm @ Bm.T).float()
+
+    gemm_ms, torch_gemm_ms = timed([gemm, torch_gemm], a.iters, a.warmup)
+    # selection on ONE fp32 (n, M) matrix for both sides: the plain matrix when the plan has one chunk, else a dense copy
+    gemm()
+    if mc >= M:
+        plain, Mp = S, L.pad_channels(M)
+    else:
+        Mp = L.pad_channels(M)
+        plain = torch.empty(n * Mp, dtype=torch.float32, device=dev)
+        for c0 in range(0, M, mc):
+            m = min(mc, M - c0)
+            mp = L.pad_channels(m)
+            plain.view(n, Mp)[:, c0: c0 + m] = S[(c0 // mc) * n * mc:][: n * mp].view(n, mp)[:, :m]
+    dense = plain.view(n, Mp)
+    lab = labels[:n].contiguous()
+    out = {}
+
+    def select():
+        out["ours"] = ops.retrieval_select(plain, qsq, csq, n, M, k, None, labels=lab)
+
+    def torch_select():
+        den = torch.clamp(torch.sqrt(qsq[:n])[:, None] * torch.sqrt(csq)[None, :], min=1e-8)
+        out["torch"] = torch.topk(dense[:, :M] / den, k, dim=1)
+
+    def torch_select_ranks():
+        den = torch.clamp(torch.sqrt(qsq[:n])[:, None] * torch.sqrt(csq)[None, :], min=1e-8)
+        sc = dense[:, :M] / den
+        out["torch"] = torch.topk(sc, k, dim=1)
+        out["torch_ranks"] = (sc > sc.gather(1, lab[:, None])).sum(dim=1)
+
+    sel_ms, tsel_ms, tselr_ms = timed([select, torch_select, torch_select_ranks], a.iters, a.warmup, reps=20)
+    same_scores = bool(torch.equal(out["ours"][1], out["torch"].values))
+
+    def whole():
+        out["whole"] = retrieve(queries, bank, k=k, labels=labels, scratch_bytes=a.scratch)
+
+    def torch_whole():
+        sc = (Qt[: N * K].view(N, K) @ bank.rows.T).float() / torch.clamp(torch.sqrt(qsq)[:, None] * torch.sqrt(csq)[None, :], min=1e-8)
+        out["torch_whole"] = torch.topk(sc, k, dim=1)
+
+    whole_ms, twhole_ms = timed([whole, torch_whole], a.iters, a.warmup)
+    bank_bytes = M * K * bank.rows.element_size()
+    return {
+        "bench": "retrieval", "N": N, "M": M, "F": F, "T": T, "dtype": a.dtype, "k": k, "plan": {"nb": nb, "mc": mc, "tiles256": tiles256, "ksplit": ks},
+        "bank_gb": round(bank_bytes / 1e9, 2),
+        "bank_build_ms_per_512": round(build_ms / max(1, build_rows) * 512, 3),
+        "gemm_ms": round(gemm_ms, 3), "gemm_tb_per_s": round(bank_bytes / gemm_ms / 1e9, 2), "torch_gemm_ms": round(torch_gemm_ms, 3),
+        "select_ms": round(sel_ms, 4), "torch_normalise_topk_ms": round(tsel_ms, 4), "torch_normalise_topk_ranks_ms": round(tselr_ms, 4),
+        "select_scores_equal_torch": same_scores,
+        "retrieve_ms": round(whole_ms, 3), "torch_whole_ms": round(twhole_ms, 3),
+        "iters": a.iters, "warmup": a.warmup,
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--M", type=int, nargs="+", default=[4096, 32768])
+    ap.add_argument("--N", type=int, default=256)
+    ap.add_argument("--F", type=int, default=1024)
+    ap.add_argument("--T", type=int, default=360)
+    ap.add_argument("--dtype", default="bf16", choices=["fp32", "bf16", "fp16"])
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--scratch", type=int, default=1 << 30)
+    ap.add_argument("--limit", type=int, default=420, help="seconds one bank size may take")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        print(json.dumps(one_size(a, a.M[0])), flush=True)
+        return 0
+    for M in a.M:                                      # this process never opens the GPU: one fresh child per size
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--M", str(M), "--N", str(a.N), "--F", str(a.F), "--T", str(a.T),
+               "--dtype", a.dtype, "--k", str(a.k), "--iters", str(a.iters), "--warmup", str(a.warmup), "--scratch", str(a.scratch)]
+        try:
+            rc = subprocess.run(cmd, timeout=a.limit).returncode
+        except subprocess.TimeoutExpired:
+            print(json.dumps({"bench": "retrieval", "M": M, "error": f"time limit of {a.limit} s"}), flush=True)
+            return 1
+        if rc != 0:
+            print(json.dumps({"bench": "retrieval", "M": M, "error": f"exit status {rc}"}), flush=True)
+            return 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
