@@ -7,7 +7,7 @@ share none of its state: every call allocates its own row-layout (RL) buffers, p
 by the module, and issues no collective (BatchNorm statistics stay local to the rank, as with a plain nn.BatchNorm1d).
 
 Activations travel as RL buffers (rows of Cp channels).  An input that is an RL view made by this package in
-the compute dtype is consumed with no copy; any other (B, C, T) device tensor is packed in one pass by sda_pack_rows_typed.
+the compute dtype is consumed with no copy; any other (B, C, T) device tensor is packed in one pass by ops.pack_rows.
 """
 from __future__ import annotations
 
@@ -20,7 +20,6 @@ import torch
 from . import lib as L
 from . import ops
 from .engine import block_dilations, subject_segments
-from .loss import _rows_base
 
 FWD_FLAGS = L.CONV_PAIR_TILES            # the forward k = 3 convs of the encoder: two tiles per workgroup share a weight slab
 BWD_FLAGS = L.CONV_WAVE_PRIO             # the data-gradient convs of the encoder's backward
@@ -28,26 +27,16 @@ BWD_FLAGS = L.CONV_WAVE_PRIO             # the data-gradient convs of the encode
 
 # ------------------------------------------------------------------------------------------------------------- operands
 def rows_in(X: torch.Tensor, Cc: int, dtype):
-    """(RL buffer, True) when X is a row-layout view of `dtype` made by this package (zero copy); else (X packed into a fresh
-    RL buffer of `dtype`, False).  X: a (B, C, T) device tensor of fp32 / bf16 / fp16."""
-    B, _, T = X.shape
-    base = _rows_base(X, B, Cc, T, dtype)
-    if base is not None:
-        return base, True
+    """ops.rows_of for a module input: (RL buffer, True) for a row-layout view of `dtype` made by this package (zero copy); else
+    (X packed into a fresh RL buffer of `dtype`, False).  X: a (B, C, T) device tensor of fp32 / bf16 / fp16."""
     if X.dtype not in ops.COMPUTE_DTYPES:
         raise L.SdaError(f"input of dtype {X.dtype}: the modules take float32, bfloat16 or float16")
-    buf = ops.new_rows_uninit(B, T, L.pad_channels(Cc), dtype, X.device)
-    return ops.pack_rows_typed(X.detach().contiguous(), buf), False
+    return ops.rows_of(X, Cc, dtype, ops.new_rows_uninit)
 
 
 def grad_rows(dY: torch.Tensor, Cc: int, dtype) -> torch.Tensor:
     """The incoming gradient of a module output as an RL buffer of `dtype` (zero copy when it already is one)."""
-    B, _, T = dY.shape
-    base = _rows_base(dY, B, Cc, T, dtype)
-    if base is not None:
-        return base
-    buf = ops.new_rows_uninit(B, T, L.pad_channels(Cc), dtype, dY.device)
-    return ops.pack_rows_typed(dY if dY.is_contiguous() else dY.contiguous(), buf)
+    return ops.rows_of(dY, Cc, dtype, ops.new_rows_uninit)[0]
 
 
 def _new(B: int, T: int, Cp: int, dtype, dev) -> torch.Tensor:

@@ -84,88 +84,20 @@ static inline int stream_blocks(int B, int T, int nch) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// (B, C, T) fp32  <->  RL rows
+// (B, C, T) of storage type S (fp32 / bf16 / fp16)  <->  RL rows of E
 // ------------------------------------------------------------------------------------------------
-template <typename E>
-__global__ __launch_bounds__(256) void pack_rows_kernel(const float* __restrict__ src, E* __restrict__ dst,
+// One pass: a 16-bit input is widened in registers, not through an fp32 copy in HBM.  Widening is exact and the one rounding is
+// to E, so every S gives the bits of the fp32 pack of the same values.  A workgroup owns 64 channels x 64 time steps of one
+// sample; valid rows get all Cp channels (padding channel `one_ch` ones, -1 = none, the others zero), pad rows are not touched.
+template <typename S, typename E>
+__global__ __launch_bounds__(256) void pack_rows_kernel(const S* __restrict__ src, E* __restrict__ dst,
                                                         int C, int T, int Cp, int one_ch) {
   __shared__ float tile[64][65];
   const int b = blockIdx.z, c0 = blockIdx.y * 64, t0 = blockIdx.x * 64;
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   for (int cc = ty; cc < 64; cc += 4) {
     const int c = c0 + cc, t = t0 + tx;
-    tile[cc][tx] = (c < C && t < T) ? src[((size_t)b * C + c) * T + t] : ((c == one_ch && t < T) ? 1.f : 0.f);
-  }
-  __syncthreads();
-  for (int rr = ty; rr < 64; rr += 4) {
-    const int t = t0 + rr;
-    if (t < T) Elem<E>::st(dst + ((size_t)b * rows_tp(T) + PAD + t) * Cp + c0 + tx, tile[tx][rr]);
-  }
-}
-
-// The same for T % 4 == 0 and a 16-byte aligned source: 16-byte loads along t, 16-byte stores along c (8 channels of a 16-bit
-// type per lane instead of one: a wave's store covers 8 rows x 128 B instead of 128 B).  Same values, same rounding.
-template <typename E>
-__global__ __launch_bounds__(256) void pack_rows_vec_kernel(const float* __restrict__ src, E* __restrict__ dst,
-                                                            int C, int T, int Cp, int one_ch) {
-  __shared__ float tile[64][65];
-  const int b = blockIdx.z, c0 = blockIdx.y * 64, t0 = blockIdx.x * 64;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int idx = threadIdx.x + 256 * k, cc = idx >> 4, t4 = (idx & 15) * 4;
-    const int c = c0 + cc, t = t0 + t4;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (t < T) {                                       // (T % 4 == 0: the four are inside or outside together)
-      if (c < C) v = *reinterpret_cast<const float4*>(src + ((size_t)b * C + c) * T + t);
-      else if (c == one_ch) v = make_float4(1.f, 1.f, 1.f, 1.f);
-    }
-    tile[cc][t4] = v.x; tile[cc][t4 + 1] = v.y; tile[cc][t4 + 2] = v.z; tile[cc][t4 + 3] = v.w;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int item = threadIdx.x + 256 * k, chunk = item & 7, rr = item >> 3;
-    const int t = t0 + rr;
-    if (t < T) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = tile[chunk * 8 + j][rr];
-      E* out = dst + ((size_t)b * rows_tp(T) + PAD + t) * Cp + c0 + chunk * 8;
-      if constexpr (sizeof(E) == 4) { Vec16<E>::store(out, v); Vec16<E>::store(out + 4, v + 4); }
-      else Vec16<E>::store(out, v);
-    }
-  }
-}
-
-template <typename E, typename O = float>
-__global__ __launch_bounds__(256) void unpack_rows_kernel(const E* __restrict__ src, O* __restrict__ dst,
-                                                          int C, int T, int Cp) {
-  __shared__ float tile[64][65];
-  const int b = blockIdx.z, c0 = blockIdx.y * 64, t0 = blockIdx.x * 64;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  for (int rr = ty; rr < 64; rr += 4) {
-    const int t = t0 + rr;
-    tile[rr][tx] = (t < T) ? Elem<E>::ld(src + ((size_t)b * rows_tp(T) + PAD + t) * Cp + c0 + tx) : 0.f;
-  }
-  __syncthreads();
-  for (int cc = ty; cc < 64; cc += 4) {
-    const int c = c0 + cc, t = t0 + tx;
-    if (c < C && t < T) Elem<O>::st(dst + ((size_t)b * C + c) * T + t, tile[tx][cc]);
-  }
-}
-
-// (B, C, T) of storage type S (fp32 / bf16 / fp16) -> RL rows of E in one pass: a 16-bit input is widened in registers, not
-// through an fp32 copy in HBM.  Widening is exact and the one rounding is to E, so the bits equal sda_pack_rows of the same
-// values.  A workgroup owns 64 channels x 64 time steps of one sample; valid rows get all Cp channels (the padding ones zero),
-// pad rows are not touched.
-template <typename S, typename E>
-__global__ __launch_bounds__(256) void pack_rows_typed_kernel(const S* __restrict__ src, E* __restrict__ dst, int C, int T, int Cp) {
-  __shared__ float tile[64][65];
-  const int b = blockIdx.z, c0 = blockIdx.y * 64, t0 = blockIdx.x * 64;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  for (int cc = ty; cc < 64; cc += 4) {
-    const int c = c0 + cc, t = t0 + tx;
-    tile[cc][tx] = (c < C && t < T) ? Elem<S>::ld(src + ((size_t)b * C + c) * T + t) : 0.f;
+    tile[cc][tx] = (c < C && t < T) ? Elem<S>::ld(src + ((size_t)b * C + c) * T + t) : ((c == one_ch && t < T) ? 1.f : 0.f);
   }
   __syncthreads();
   for (int rr = ty; rr < 64; rr += 4) {
@@ -176,10 +108,11 @@ __global__ __launch_bounds__(256) void pack_rows_typed_kernel(const S* __restric
 
 // The same for T % (16 / sizeof(S)) == 0 and a 16-byte aligned source: every load and store is 16 bytes.  Loads run along t
 // (a channel's 64 steps are 4 lanes x 64 B of bf16 / fp16 or 16 lanes x 16 B of fp32, so a wave reads whole 128 / 256-byte
-// runs), stores along c (8 channels of a 16-bit E per lane: a wave writes 8 rows x 128 B).
+// runs), stores along c (8 channels of a 16-bit E per lane instead of one: a wave writes 8 rows x 128 B instead of 128 B).
+// Same values, same rounding.
 template <typename S, typename E>
-__global__ __launch_bounds__(256) void pack_rows_typed_vec_kernel(const S* __restrict__ src, E* __restrict__ dst, int C, int T,
-                                                                  int Cp) {
+__global__ __launch_bounds__(256) void pack_rows_vec_kernel(const S* __restrict__ src, E* __restrict__ dst,
+                                                            int C, int T, int Cp, int one_ch) {
   __shared__ float tile[64][65];
   constexpr int N = Vec16<S>::N, PER_RUN = 64 / N;          // source elements per load, loads per channel run of the tile
   const int b = blockIdx.z, c0 = blockIdx.y * 64, t0 = blockIdx.x * 64;
@@ -188,11 +121,14 @@ __global__ __launch_bounds__(256) void pack_rows_typed_vec_kernel(const S* __res
     const int idx = threadIdx.x + 256 * k, cc = idx / PER_RUN, tn = (idx % PER_RUN) * N;
     const int c = c0 + cc, t = t0 + tn;
     float v[N];
-    if (c < C && t < T) {                              // (T % N == 0: the N steps are inside or outside together)
-      Vec16<S>::load(src + ((size_t)b * C + c) * T + t, v);
-    } else {
 #pragma unroll
-      for (int j = 0; j < N; ++j) v[j] = 0.f;
+    for (int j = 0; j < N; ++j) v[j] = 0.f;
+    if (t < T) {                                       // (T % N == 0: the N steps are inside or outside together)
+      if (c < C) Vec16<S>::load(src + ((size_t)b * C + c) * T + t, v);
+      else if (c == one_ch) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) v[j] = 1.f;
+      }
     }
 #pragma unroll
     for (int j = 0; j < N; ++j) tile[cc][tn + j] = v[j];
@@ -210,6 +146,23 @@ __global__ __launch_bounds__(256) void pack_rows_typed_vec_kernel(const S* __res
       if constexpr (sizeof(E) == 4) { Vec16<E>::store(out, v); Vec16<E>::store(out + 4, v + 4); }
       else Vec16<E>::store(out, v);
     }
+  }
+}
+
+template <typename E, typename O>
+__global__ __launch_bounds__(256) void unpack_rows_kernel(const E* __restrict__ src, O* __restrict__ dst,
+                                                          int C, int T, int Cp) {
+  __shared__ float tile[64][65];
+  const int b = blockIdx.z, c0 = blockIdx.y * 64, t0 = blockIdx.x * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  for (int rr = ty; rr < 64; rr += 4) {
+    const int t = t0 + rr;
+    tile[rr][tx] = (t < T) ? Elem<E>::ld(src + ((size_t)b * rows_tp(T) + PAD + t) * Cp + c0 + tx) : 0.f;
+  }
+  __syncthreads();
+  for (int cc = ty; cc < 64; cc += 4) {
+    const int c = c0 + cc, t = t0 + tx;
+    if (c < C && t < T) Elem<O>::st(dst + ((size_t)b * C + c) * T + t, tile[tx][cc]);
   }
 }
 
@@ -1041,16 +994,23 @@ extern "C" int sda_scalar_mul(const float* a, const float* b, float* out, int n,
   return check_launch("scalar_mul");
 }
 
-extern "C" int sda_pack_rows(const float* src, void* dst, int B, int C, int T, int Cp, int dtype, void* stream) {
-  if (!src || !dst || Cp % 64 || C > Cp || B < 1) { set_error("pack_rows: bad arguments"); return -1; }
+// The one launch of the pack: 16-byte loads where the source allows them, else one element per lane.  one_ch: -1 = none.
+template <typename S>
+static int launch_pack_rows(const S* src, void* dst, int B, int C, int T, int Cp, int one_ch, int dtype, void* stream,
+                            const char* what) {
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((T + 63) / 64, Cp / 64, B);
-  if (T % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-    SDA_DISPATCH(dtype, hipLaunchKernelGGL(pack_rows_vec_kernel<E>, grid, dim3(256), 0, st, src, (E*)dst, C, T, Cp, -1));
+  if (T % Vec16<S>::N == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+    SDA_DISPATCH(dtype, hipLaunchKernelGGL((pack_rows_vec_kernel<S, E>), grid, dim3(256), 0, st, src, (E*)dst, C, T, Cp, one_ch));
   } else {
-    SDA_DISPATCH(dtype, hipLaunchKernelGGL(pack_rows_kernel<E>, grid, dim3(256), 0, st, src, (E*)dst, C, T, Cp, -1));
+    SDA_DISPATCH(dtype, hipLaunchKernelGGL((pack_rows_kernel<S, E>), grid, dim3(256), 0, st, src, (E*)dst, C, T, Cp, one_ch));
   }
-  return check_launch("pack_rows");
+  return check_launch(what);
+}
+
+extern "C" int sda_pack_rows(const float* src, void* dst, int B, int C, int T, int Cp, int dtype, void* stream) {
+  if (!src || !dst || Cp % 64 || C > Cp || B < 1) { set_error("pack_rows: bad arguments"); return -1; }
+  return launch_pack_rows(src, dst, B, C, T, Cp, -1, dtype, stream, "pack_rows");
 }
 
 extern "C" int sda_pack_rows_ones(const float* src, void* dst, int B, int C, int T, int Cp, int ones_channel, int dtype,
@@ -1058,40 +1018,7 @@ extern "C" int sda_pack_rows_ones(const float* src, void* dst, int B, int C, int
   if (!src || !dst || Cp % 64 || C > Cp || B < 1 || ones_channel < C || ones_channel >= Cp) {
     set_error("pack_rows_ones: bad arguments (the constant channel must be a padding channel)"); return -1;
   }
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid((T + 63) / 64, Cp / 64, B);
-  if (T % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-    SDA_DISPATCH(dtype, hipLaunchKernelGGL(pack_rows_vec_kernel<E>, grid, dim3(256), 0, st, src, (E*)dst, C, T, Cp, ones_channel));
-  } else {
-    SDA_DISPATCH(dtype, hipLaunchKernelGGL(pack_rows_kernel<E>, grid, dim3(256), 0, st, src, (E*)dst, C, T, Cp, ones_channel));
-  }
-  return check_launch("pack_rows_ones");
-}
-
-extern "C" int sda_unpack_rows(const void* src, float* dst, int B, int C, int T, int Cp, int dtype, void* stream) {
-  if (!src || !dst || Cp % 64 || C > Cp || B < 1) { set_error("unpack_rows: bad arguments"); return -1; }
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid((T + 63) / 64, Cp / 64, B);
-  SDA_DISPATCH(dtype, hipLaunchKernelGGL(unpack_rows_kernel<E>, grid, dim3(256), 0, st, (const E*)src, dst, C, T, Cp));
-  return check_launch("unpack_rows");
-}
-
-// the same transpose into a (B, C, T) tensor of dst_dtype: one rounding where the stored value does not fit the output type
-extern "C" int sda_unpack_rows_typed(const void* src, void* dst, int B, int C, int T, int Cp, int dtype, int dst_dtype,
-                                     void* stream) {
-  if (!src || !dst || Cp % 64 || C > Cp || B < 1) { set_error("unpack_rows_typed: bad arguments"); return -1; }
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid((T + 63) / 64, Cp / 64, B);
-  if (dst_dtype == SDA_F32)
-    SDA_DISPATCH(dtype, hipLaunchKernelGGL((unpack_rows_kernel<E, float>), grid, dim3(256), 0, st, (const E*)src, (float*)dst, C, T, Cp));
-  else if (dst_dtype == SDA_BF16)
-    SDA_DISPATCH(dtype, hipLaunchKernelGGL((unpack_rows_kernel<E, uint16_t>), grid, dim3(256), 0, st, (const E*)src, (uint16_t*)dst, C,
-                                           T, Cp));
-  else if (dst_dtype == SDA_F16)
-    SDA_DISPATCH(dtype, hipLaunchKernelGGL((unpack_rows_kernel<E, half_t>), grid, dim3(256), 0, st, (const E*)src, (half_t*)dst, C, T,
-                                           Cp));
-  else { set_error("unpack_rows_typed: unknown output dtype %d", dst_dtype); return -1; }
-  return check_launch("unpack_rows_typed");
+  return launch_pack_rows(src, dst, B, C, T, Cp, ones_channel, dtype, stream, "pack_rows_ones");
 }
 
 // true for memory the current process allocated on a device (or managed memory); false for host memory, or with no device.
@@ -1105,17 +1032,7 @@ static bool device_memory(const void* p) {
   return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
 
-template <typename S>
-static int launch_pack_rows_typed(const S* src, void* dst, int B, int C, int T, int Cp, int dtype, hipStream_t st) {
-  dim3 grid((T + 63) / 64, Cp / 64, B);
-  if (T % Vec16<S>::N == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-    SDA_DISPATCH(dtype, hipLaunchKernelGGL((pack_rows_typed_vec_kernel<S, E>), grid, dim3(256), 0, st, src, (E*)dst, C, T, Cp));
-  } else {
-    SDA_DISPATCH(dtype, hipLaunchKernelGGL((pack_rows_typed_kernel<S, E>), grid, dim3(256), 0, st, src, (E*)dst, C, T, Cp));
-  }
-  return check_launch("pack_rows_typed");
-}
-
+// any source dtype; off the step's host path, so it can afford the pointer query the two fp32 entry points do without
 extern "C" int sda_pack_rows_typed(const void* src, void* dst, int B, int C, int T, int Cp, int src_dtype, int dtype,
                                    void* stream) {
   if (!src || !dst || B < 1 || C < 1 || T < 1 || Cp % 64 || C > Cp || B > 65535) {
@@ -1125,10 +1042,31 @@ extern "C" int sda_pack_rows_typed(const void* src, void* dst, int B, int C, int
     set_error("pack_rows_typed: unknown dtype (source %d, destination %d)", src_dtype, dtype); return -1;
   }
   if (!device_memory(src) || !device_memory(dst)) { set_error("pack_rows_typed: src and dst must be device memory"); return -1; }
+  if (src_dtype == SDA_F32) return launch_pack_rows((const float*)src, dst, B, C, T, Cp, -1, dtype, stream, "pack_rows_typed");
+  if (src_dtype == SDA_BF16) return launch_pack_rows((const uint16_t*)src, dst, B, C, T, Cp, -1, dtype, stream, "pack_rows_typed");
+  return launch_pack_rows((const half_t*)src, dst, B, C, T, Cp, -1, dtype, stream, "pack_rows_typed");
+}
+
+// RL of `dtype` -> a (B, C, T) tensor of dst_dtype: one rounding where the stored value does not fit the output type
+extern "C" int sda_unpack_rows_typed(const void* src, void* dst, int B, int C, int T, int Cp, int dtype, int dst_dtype,
+                                     void* stream) {
+  if (!src || !dst || Cp % 64 || C > Cp || B < 1) { set_error("unpack_rows: bad arguments"); return -1; }
   hipStream_t st = (hipStream_t)stream;
-  if (src_dtype == SDA_F32) return launch_pack_rows_typed((const float*)src, dst, B, C, T, Cp, dtype, st);
-  if (src_dtype == SDA_BF16) return launch_pack_rows_typed((const uint16_t*)src, dst, B, C, T, Cp, dtype, st);
-  return launch_pack_rows_typed((const half_t*)src, dst, B, C, T, Cp, dtype, st);
+  dim3 grid((T + 63) / 64, Cp / 64, B);
+  if (dst_dtype == SDA_F32)
+    SDA_DISPATCH(dtype, hipLaunchKernelGGL((unpack_rows_kernel<E, float>), grid, dim3(256), 0, st, (const E*)src, (float*)dst, C, T, Cp));
+  else if (dst_dtype == SDA_BF16)
+    SDA_DISPATCH(dtype, hipLaunchKernelGGL((unpack_rows_kernel<E, uint16_t>), grid, dim3(256), 0, st, (const E*)src, (uint16_t*)dst, C,
+                                           T, Cp));
+  else if (dst_dtype == SDA_F16)
+    SDA_DISPATCH(dtype, hipLaunchKernelGGL((unpack_rows_kernel<E, half_t>), grid, dim3(256), 0, st, (const E*)src, (half_t*)dst, C, T,
+                                           Cp));
+  else { set_error("unpack_rows: unknown output dtype %d", dst_dtype); return -1; }
+  return check_launch("unpack_rows");
+}
+
+extern "C" int sda_unpack_rows(const void* src, float* dst, int B, int C, int T, int Cp, int dtype, void* stream) {
+  return sda_unpack_rows_typed(src, dst, B, C, T, Cp, dtype, SDA_F32, stream);
 }
 
 extern "C" int sda_rows_sumsq_from_stats(const float* stats, int tiles_per_sample, int Cp, float* out, int B, void* stream) {

@@ -87,17 +87,7 @@ def _cached_ranks(Y, Z):
     return None
 
 
-def _rows_base(t: torch.Tensor, B: int, Cc: int, T: int, dtype):
-    """If `t` is a (B, C, T) view laid out exactly like ops.rows_view(...) of an RL buffer, return that
-    buffer as a (rows_alloc, Cp) tensor sharing its storage (zero copy); else None."""
-    if t.dtype != dtype or not t.is_cuda or t.dim() != 3:
-        return None
-    Cp, rows = L.pad_channels(Cc), L.rows_alloc(B, T)
-    if tuple(t.stride()) != (L.rows_tp(T) * Cp, 1, Cp) or t.storage_offset() != L.ROW_PAD * Cp:
-        return None
-    if t.untyped_storage().nbytes() < rows * Cp * t.element_size():
-        return None
-    return t.detach().as_strided((rows, Cp), (Cp, 1), 0)
+_rows_base = ops.rows_base      # its name while it lived here: kept for code outside this tree that imported it; use ops.rows_base
 
 
 def _ring_rows(state: LossState, key, B, Cc, T, dtype, device) -> RingSlot:
@@ -124,19 +114,15 @@ def as_rows(t: torch.Tensor, B: int, Cc: int, T: int, dtype, name: str, ring_key
     With want_slot: (buffer, RingSlot or None)."""
     if tuple(t.shape) != (B, Cc, T):
         raise ValueError(f"{name}: expected shape {(B, Cc, T)}, got {tuple(t.shape)}")
-    base = _rows_base(t, B, Cc, T, dtype)
-    if base is not None:
-        return (base, None) if want_slot else base
     if not t.is_cuda:
         raise L.SdaError(f"{name} must live on the MI355X device (there is no CPU path)")
-    slot = None
-    if ring_key is not None:
-        slot = _ring_rows(state or _DEFAULT_STATE, ring_key, B, Cc, T, dtype, t.device)   # pack_rows rewrites every valid row
-        buf = slot.buf
-    else:
-        buf = ops.new_rows(B, T, L.pad_channels(Cc), dtype, t.device)
-    ops.pack_rows(t.detach().float().contiguous(), buf)
-    return (buf, slot) if want_slot else buf
+    slots = []
+
+    def ring_slot(*_):                                     # pack_rows rewrites every valid row
+        slots.append(_ring_rows(state or _DEFAULT_STATE, ring_key, B, Cc, T, dtype, t.device))
+        return slots[0].buf
+    buf, _ = ops.rows_of(t, Cc, dtype, ops.new_rows if ring_key is None else ring_slot)
+    return (buf, slots[0] if slots else None) if want_slot else buf
 
 
 def _dist_group():
@@ -273,7 +259,7 @@ class _ClipFn(torch.autograd.Function):
         if want_y:
             # the gradient leaves in the argument's own form: the row-layout buffer of a rows view in the compute dtype, else a
             # (B, F, T) tensor of the argument's dtype
-            y_rows = _rows_base(Y, B, F, T, dtype) is not None
+            y_rows = ops.rows_base(Y, B, F, T, dtype) is not None
             if not y_rows and not Y.is_cuda:
                 raise L.SdaError("CLIPLoss: x (speech embeddings) must live on the MI355X device (there is no CPU path)")
             if not y_rows and Y.dtype not in ops.COMPUTE_DTYPES:
@@ -331,7 +317,7 @@ class _ClipFn(torch.autograd.Function):
             dZ = ops.rows_view(dZt, B, F, T)
         if ctx.y_requires_grad:
             dYt = _clip_dy(ctx, scale.reshape(1).contiguous())
-            dY = ops.rows_view(dYt, B, F, T) if ctx.y_rows else ops.unpack_rows_typed(dYt, B, F, T, ctx.y_dtype)
+            dY = ops.rows_view(dYt, B, F, T) if ctx.y_rows else ops.unpack_rows(dYt, B, F, T, ctx.y_dtype)
         dtemp = ops.scalar_mul(c.dtemp, scale.reshape(1))
         return None, dY, dZ, dtemp
 
@@ -450,7 +436,7 @@ def torch_log(x: torch.Tensor) -> torch.Tensor:
 def _mse_operand(t: torch.Tensor, B: int, F: int, T: int, name: str):
     """(operand, is_rows): the row-layout buffer behind a rows_view (zero copy), else the plain tensor made contiguous."""
     if t.dtype in ops.COMPUTE_DTYPES:
-        base = _rows_base(t, B, F, T, t.dtype)
+        base = ops.rows_base(t, B, F, T, t.dtype)
         if base is not None:
             return base, True
     if not t.is_cuda:

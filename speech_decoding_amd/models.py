@@ -139,7 +139,7 @@ class _ConvBlockFn(torch.autograd.Function):
             # an RL-view input (the output of another module) gets its gradient as an RL view of the same layout, which that
             # module's backward consumes without a pack; a plain input gets a contiguous tensor of its own dtype
             dX = (ops.rows_view(g["X"], c.B, module.in_channels, c.T) if c.x_rows
-                  else ops.unpack_rows_typed(g["X"], c.B, module.in_channels, c.T, c.x_dtype))
+                  else ops.unpack_rows(g["X"], c.B, module.in_channels, c.T, c.x_dtype))
         return (None, dX, None, *[g.get(name) for name in _blocks.CB_PARAMS])
 
 

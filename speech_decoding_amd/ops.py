@@ -76,7 +76,6 @@ def _need_cuda(*ts):
 
 def upload_small(array, device) -> torch.Tensor:
     """Host numpy array -> new device tensor without a memcpy (payload travels in kernel arguments)."""
-    import numpy as np
     array = np.ascontiguousarray(array)
     nbytes = array.nbytes
     padded = (nbytes + 3) // 4 * 4
@@ -101,7 +100,6 @@ class UploadCache:
         self._upload = upload or upload_small     # (array, device) -> tensor; the keying and eviction rules do not depend on it
 
     def upload(self, key, array, device) -> torch.Tensor:
-        import numpy as np
         array = np.ascontiguousarray(array)
         k = (key, str(array.dtype), array.shape, array.tobytes(), str(device))
         hit = self.items.get(k)
@@ -188,46 +186,62 @@ def rows_view(buf: torch.Tensor, B: int, C: int, T: int) -> torch.Tensor:
     return buf.as_strided((B, C, T), (Tp * Cp, 1, Cp), L.ROW_PAD * Cp)
 
 
-def pack_rows(src: torch.Tensor, dst: torch.Tensor, ones_channel: Optional[int] = None):
-    """(B, C, T) fp32 -> row layout; with `ones_channel` that padding channel is 1 on every valid row."""
-    _need_cuda(src, dst)
-    B, Cc, T = src.shape
-    src = src.contiguous().float()
-    if ones_channel is None:
-        L.check(L.load().sda_pack_rows(_p(src), _p(dst), B, Cc, T, dst.shape[1], dt_code(dst.dtype), _st()), "pack_rows")
-    else:
-        L.check(L.load().sda_pack_rows_ones(_p(src), _p(dst), B, Cc, T, dst.shape[1], ones_channel, dt_code(dst.dtype), _st()),
-                "pack_rows_ones")
+def rows_base(t: torch.Tensor, B: int, Cc: int, T: int, dtype) -> Optional[torch.Tensor]:
+    """The inverse of rows_view: if `t` is a (B, C, T) view of `dtype` laid out exactly like rows_view(...) of an RL buffer,
+    that buffer as a (rows_alloc, Cp) tensor sharing its storage (zero copy); else None."""
+    if t.dtype != dtype or not t.is_cuda or t.dim() != 3:
+        return None
+    Cp, rows = L.pad_channels(Cc), L.rows_alloc(B, T)
+    if tuple(t.stride()) != (L.rows_tp(T) * Cp, 1, Cp) or t.storage_offset() != L.ROW_PAD * Cp:
+        return None
+    if t.untyped_storage().nbytes() < rows * Cp * t.element_size():
+        return None
+    return t.detach().as_strided((rows, Cp), (Cp, 1), 0)
 
 
-def pack_rows_typed(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
-    """Contiguous (B, C, T) fp32 / bf16 / fp16 -> RL buffer `dst` of its own dtype in one pass (sda_pack_rows_typed): a 16-bit
-    input is not widened to an fp32 copy first.  Valid rows and their channel padding are written, pad rows are not: `dst`
-    comes from new_rows / new_rows_uninit."""
+def rows_of(t: torch.Tensor, Cc: int, dtype, alloc=new_rows):
+    """(RL buffer of `dtype` holding the (B, C, T) device tensor `t`, was_view): the buffer behind a rows view made by this
+    package (zero copy, True); else `t` packed into the buffer `alloc(B, T, Cp, dtype, device)` hands out (new_rows,
+    new_rows_uninit or a caller's pool; not called for a view), and False."""
+    B, _, T = t.shape
+    base = rows_base(t, B, Cc, T, dtype)
+    if base is not None:
+        return base, True
+    return pack_rows(t.detach(), alloc(B, T, L.pad_channels(Cc), dtype, t.device)), False
+
+
+def pack_rows(src: torch.Tensor, dst: torch.Tensor, ones_channel: Optional[int] = None) -> torch.Tensor:
+    """(B, C, T) device tensor -> RL buffer `dst` of its own dtype in one pass; with `ones_channel` that padding channel is 1 on
+    every valid row.  Valid rows and their channel padding are written, pad rows are not: `dst` comes from new_rows /
+    new_rows_uninit.  An fp32 source takes sda_pack_rows / sda_pack_rows_ones, a bf16 / fp16 one sda_pack_rows_typed (widened
+    in registers: no fp32 copy).  A source that is not contiguous is made so first."""
     _need_cuda(src, dst)
-    if src.dim() != 3 or not src.is_contiguous():
-        raise L.SdaError("pack_rows_typed: src must be a contiguous (B, C, T) tensor")
+    if src.dim() != 3:
+        raise L.SdaError("pack_rows: src must be a (B, C, T) tensor")
     B, Cc, T = src.shape
     if dst.dim() != 2 or not dst.is_contiguous() or dst.shape[0] < L.rows_alloc(B, T):
-        raise L.SdaError("pack_rows_typed: dst must be a row-layout buffer for (B, T)")
-    L.check(L.load().sda_pack_rows_typed(_p(src), _p(dst), B, Cc, T, dst.shape[1], dt_code(src.dtype), dt_code(dst.dtype), _st()),
-            "pack_rows_typed")
+        raise L.SdaError("pack_rows: dst must be a row-layout buffer for (B, T)")
+    if src.dtype not in _DT or (ones_channel is not None and src.dtype != torch.float32):
+        # no entry point packs a 16-bit source WITH a ones channel (the composed SubjectBlock fed a 16-bit X): that one, and a
+        # dtype the kernels do not read, go through an fp32 copy
+        src = src.float()
+    src = src.contiguous()
+    lib, Cp, dt = L.load(), dst.shape[1], dt_code(dst.dtype)
+    if ones_channel is not None:
+        L.check(lib.sda_pack_rows_ones(_p(src), _p(dst), B, Cc, T, Cp, ones_channel, dt, _st()), "pack_rows_ones")
+    elif src.dtype == torch.float32:
+        L.check(lib.sda_pack_rows(_p(src), _p(dst), B, Cc, T, Cp, dt, _st()), "pack_rows")
+    else:
+        L.check(lib.sda_pack_rows_typed(_p(src), _p(dst), B, Cc, T, Cp, dt_code(src.dtype), dt, _st()), "pack_rows_typed")
     return dst
 
 
-def unpack_rows(src: torch.Tensor, B: int, Cc: int, T: int) -> torch.Tensor:
-    _need_cuda(src)
-    out = torch.empty((B, Cc, T), dtype=torch.float32, device=src.device)
-    L.check(L.load().sda_unpack_rows(_p(src), _p(out), B, Cc, T, src.shape[1], dt_code(src.dtype), _st()), "unpack_rows")
-    return out
-
-
-def unpack_rows_typed(src: torch.Tensor, B: int, Cc: int, T: int, dtype) -> torch.Tensor:
+def unpack_rows(src: torch.Tensor, B: int, Cc: int, T: int, dtype=torch.float32) -> torch.Tensor:
     """RL buffer -> a fresh contiguous (B, C, T) tensor of `dtype` (fp32 / bf16 / fp16), one HBM pass."""
     _need_cuda(src)
     out = torch.empty((B, Cc, T), dtype=dtype, device=src.device)
     L.check(L.load().sda_unpack_rows_typed(_p(src), _p(out), B, Cc, T, src.shape[1], dt_code(src.dtype), dt_code(dtype), _st()),
-            "unpack_rows_typed")
+            "unpack_rows")
     return out
 
 
@@ -388,7 +402,6 @@ class PackPlan:
                 arr[i].src, arr[i].dst = src.data_ptr(), dst.data_ptr()
                 for name, val in f.items():
                     setattr(arr[i], name, val)
-            import numpy as np
             self._table = upload_small(np.frombuffer(bytes(arr), dtype=np.uint8), self.device)
             self._sig = sig
             self._max_total = max(f["total"] for *_, f in self.items)

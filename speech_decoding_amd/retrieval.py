@@ -5,7 +5,8 @@ is its forward-only counterpart for a trained encoder: a resident bank of candid
 which scores N query segments against all M candidates and returns the k best of each, and, given the true candidates, their
 ranks over the whole bank.  The score is the reference's similarity (models.py:223-232), <q, c> / max(|q| |c|, 1e-8).
 
-Everything runs in libsdamd.so: the pack and the norms (sda_pack_rows, sda_rows_sumsq), the similarity GEMM of the loss
+Everything runs in libsdamd.so: the pack and the norms (ops.rows_of: one ops.pack_rows launch for fp32, bf16 or fp16 segments
+with no widened copy, none for an encoder's row-layout view; sda_rows_sumsq), the similarity GEMM of the loss
 (ops.matmul_nt_splitk's two kernels, rectangular) and one selection launch per block of queries (csrc/retrieval.hip).  The
 N x M score matrix is never held whole: see plan_blocks.  Which side is "query" is the caller's choice — brain segments against
 a speech bank (`Classifier.decode`) or the other way round; under torch.distributed every rank decodes its own queries
@@ -19,7 +20,6 @@ import numpy as np
 import torch
 
 from . import lib as L
-from . import loss as _loss
 from . import ops
 
 MAX_K = 64          # the selection kernel keeps the 64 best candidates of a row
@@ -116,7 +116,7 @@ class SpeechBank:
             return range(first, first)
         if first + m > self._capacity:
             self._reserve(max(first + m, 2 * self._capacity))
-        packed = _loss.as_rows(Y, m, self.F, self.T, self.dtype, "SpeechBank.add: Y")        # pad rows and channels zero
+        packed, _ = ops.rows_of(Y, self.F, self.dtype)                    # pad rows and channels zero
         self._rows[first * re: (first + m) * re].copy_(packed.reshape(-1)[: m * re])
         self._sq[first: first + m].copy_(ops.rows_sumsq(packed, m, re, re))
         self._size = first + m
@@ -199,7 +199,7 @@ def retrieve(queries: torch.Tensor, bank: SpeechBank, k: int = 10, labels=None, 
     if isinstance(labels, np.ndarray):
         labels = ops.upload_small(labels, dev)
 
-    Qt = _loss.as_rows(queries, N, F, T, bank.dtype, "retrieve: queries").reshape(-1)
+    Qt = ops.rows_of(queries, F, bank.dtype)[0].reshape(-1)
     qsq = ops.rows_sumsq(Qt, N, K, K)
     Bt, csq = bank.rows.reshape(-1), bank.norms_sq
     S = torch.empty(ops.retrieval_scores_floats(nb, M, mc), dtype=torch.float32, device=dev)

@@ -56,8 +56,8 @@ def packed(x, dtype):
 
 
 def is_rows_view(t):
-    from speech_decoding_amd.loss import _rows_base
-    return _rows_base(t, *t.shape, t.dtype) is not None
+    from speech_decoding_amd import ops
+    return ops.rows_base(t, *t.shape, t.dtype) is not None
 
 
 def randn(*shape, seed):
@@ -166,7 +166,7 @@ def test_swapped_arguments():
 @pytest.mark.parametrize("dtype", ["bf16", "fp32"])
 def test_rows_dx_buffer_contract_on_poisoned_memory(dtype):
     from speech_decoding_amd import lib as L
-    from speech_decoding_amd.loss import _rows_base
+    from speech_decoding_amd import ops
     B, F, T = 5, 100, 45
     Cp = L.pad_channels(F)
     _, x = packed(randn(B, F, T, seed=7), DT[dtype])
@@ -178,7 +178,7 @@ def test_rows_dx_buffer_contract_on_poisoned_memory(dtype):
         del junk                                  # the backward's buffer comes back out of this NaN-filled block
         (dx,) = torch.autograd.grad(crit(x, y), [x])
         assert is_rows_view(dx)
-        buf = _rows_base(dx, B, F, T, DT[dtype]).float().cpu()
+        buf = ops.rows_base(dx, B, F, T, DT[dtype]).float().cpu()
         Tp = L.rows_tp(T)
         valid = torch.zeros(buf.shape[0], dtype=torch.bool)
         for b in range(B):
@@ -261,7 +261,7 @@ def test_x_without_grad_never_calls_the_new_entry_points(monkeypatch):
     def boom(*a, **k):
         raise AssertionError("speech-side gradient kernel called although x needs no gradient")
 
-    for mod, name in ((ops, "clip_grad_y"), (ops, "clip_grad_y_finish"), (ops, "unpack_rows_typed"), (engine, "clip_backward_y")):
+    for mod, name in ((ops, "clip_grad_y"), (ops, "clip_grad_y_finish"), (ops, "unpack_rows"), (engine, "clip_backward_y")):
         monkeypatch.setattr(mod, name, boom)
     x = randn(6, 64, 40, seed=31).to(DEV)
     y = randn(6, 64, 40, seed=32).to(DEV).requires_grad_(True)

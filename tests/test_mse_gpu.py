@@ -51,8 +51,8 @@ def operand(x, layout, dtype, requires_grad=False):
 
 
 def is_rows_view(t):
-    from speech_decoding_amd.loss import _rows_base
-    return _rows_base(t, *t.shape, t.dtype) is not None
+    from speech_decoding_amd import ops
+    return ops.rows_base(t, *t.shape, t.dtype) is not None
 
 
 def ref_mse(Y, Z):
@@ -139,7 +139,7 @@ def test_errors():
 @pytest.mark.parametrize("dtype", ["bf16", "fp32"])
 def test_rows_dz_buffer_contract_on_poisoned_memory(dtype):
     from speech_decoding_amd import lib as L
-    from speech_decoding_amd.loss import _rows_base
+    from speech_decoding_amd import ops
     B, F, T = 5, 100, 45
     Cp = L.pad_channels(F)
     g = torch.Generator().manual_seed(11)
@@ -152,7 +152,7 @@ def test_rows_dz_buffer_contract_on_poisoned_memory(dtype):
         junk = torch.full((nbytes // 4,), float("nan"), dtype=torch.float32, device=DEV)
         del junk
         (dZ,) = torch.autograd.grad(mse()(Y, Z), [Z])
-        buf = _rows_base(dZ, B, F, T, DT[dtype]).float().cpu()
+        buf = ops.rows_base(dZ, B, F, T, DT[dtype]).float().cpu()
         Tp = L.rows_tp(T)
         valid = torch.zeros(buf.shape[0], dtype=torch.bool)
         for b in range(B):

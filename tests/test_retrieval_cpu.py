@@ -136,3 +136,20 @@ def test_blocking_plan_keeps_the_memory_bound(lib):
             assert used <= scratch, (N, M, K, scratch, dtype, nb, mc, ks, used)
     nb, mc, _, ks = plan_blocks(96, 1000, 6784, torch.bfloat16, 64 << 10)
     assert nb < 96 and mc < 1000          # the setting the GPU suite uses to force several query blocks and bank chunks
+
+
+def test_retrieval_module_does_not_import_the_loss():
+    """retrieval.py rests on ops alone: importing it brings in neither the loss module nor the encoder's engine.  Checked in a
+    fresh process; the package's __init__ (which re-exports CLIPLoss and BrainEncoder) is stood in for by a bare package."""
+    import subprocess
+    import sys
+    code = ("import sys, types\n"
+            "pkg = types.ModuleType('speech_decoding_amd')\n"
+            "pkg.__path__ = [%r]\n"
+            "sys.modules['speech_decoding_amd'] = pkg\n"
+            "import speech_decoding_amd.retrieval as R\n"
+            "assert callable(R.retrieve) and 'speech_decoding_amd.ops' in sys.modules\n"
+            "bad = [m for m in ('loss', 'engine', 'models', 'blocks') if 'speech_decoding_amd.' + m in sys.modules]\n"
+            "assert not bad, bad\n" % os.path.join(ROOT, "speech_decoding_amd"))
+    done = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
+    assert done.returncode == 0, done.stderr

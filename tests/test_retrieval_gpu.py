@@ -294,7 +294,7 @@ def test_square_case_agrees_with_classifier_ranks(dtype):
 # ---------------------------------------------------------------------------------------------------------------------------
 def test_encoder_output_view_equals_its_contiguous_copy():
     from speech_decoding_amd import SpeechBank, retrieve
-    from speech_decoding_amd.loss import _rows_base
+    from speech_decoding_amd import ops
     from speech_decoding.models import BrainEncoder
     C, S, D1, D2, F, K, T, B = 20, 3, 32, 48, 64, 4, 90, 12
     loc = O.synthetic_positions(C, seed=1)
@@ -308,7 +308,7 @@ def test_encoder_output_view_equals_its_contiguous_copy():
     X, Y, subj = O.synthetic_batch(B, C, T, F, S, seed=3)
     with torch.no_grad():
         Z = enc(X.to(DEV), subj)
-    assert not Z.is_contiguous() and _rows_base(Z, B, F, T, torch.float32) is not None       # the zero-copy rows view
+    assert not Z.is_contiguous() and ops.rows_base(Z, B, F, T, torch.float32) is not None       # the zero-copy rows view
     bank = SpeechBank.from_tensor(Y.to(DEV), dtype=torch.float32)
     labels = torch.arange(B)
     a = retrieve(Z, bank, k=5, labels=labels)

@@ -125,4 +125,4 @@ def test_pack_rows_typed_argument_validation_without_launch(lib):
 def test_ops_pack_rows_typed_refuses_host_tensors(lib):
     from speech_decoding_amd import SdaError, ops
     with pytest.raises(SdaError, match="device"):
-        ops.pack_rows_typed(torch.randn(2, 8, 8, dtype=torch.bfloat16), torch.zeros(lib.rows_alloc(2, 8), 64))
+        ops.pack_rows(torch.randn(2, 8, 8, dtype=torch.bfloat16), torch.zeros(lib.rows_alloc(2, 8), 64))

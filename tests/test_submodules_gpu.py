@@ -1,7 +1,7 @@
 """The standalone submodules `SpatialAttention`, `SubjectBlock` and `ConvBlock` on the MI355X: the reference's own activations,
 running statistics and gradients (tests/golden/e2e_small.npz) from standalone calls, every compute dtype x input dtype in train
 and eval mode against float64 autograd of the oracle's stage functions on the same rounded operands, RNG and BatchNorm modes,
-isolation from the encoder's engine, and the row-layout hand-off between chained calls (sda_pack_rows_typed included)."""
+isolation from the encoder's engine, and the row-layout hand-off between chained calls (ops.pack_rows / unpack_rows / rows_of included)."""
 import numpy as np
 import pytest
 import torch
@@ -437,16 +437,15 @@ def test_chained_calls_hand_over_row_layout_views(dtype, monkeypatch):
         loop = blk(loop)
     assert torch.equal(enc.conv_blocks(h), loop)
 
-    packs = []
-    real_typed, real_pack = ops.pack_rows_typed, ops.pack_rows
-    monkeypatch.setattr(ops, "pack_rows_typed", lambda *a, **k: (packs.append("typed"), real_typed(*a, **k))[1])
-    monkeypatch.setattr(ops, "pack_rows", lambda *a, **k: (packs.append("fp32"), real_pack(*a, **k))[1])
+    packs = []                                                 # dtype of the source each pack was handed
+    real_pack = ops.pack_rows
+    monkeypatch.setattr(ops, "pack_rows", lambda src, *a, **k: (packs.append(src.dtype), real_pack(src, *a, **k))[1])
     Xl = X.clone().requires_grad_(True)
     y = enc.conv_blocks(enc.subject_block(Xl, subj))
-    assert packs == ["typed"]                                  # X only: every stage hands an RL view to the next
+    assert packs == [Xl.dtype]                                 # X only, as it came (no widened copy): every stage hands an RL view on
     R = torch.randn(y.shape, device=DEV, dtype=y.dtype)
     (y * R).sum().backward()
-    assert packs == ["typed", "typed"]                         # + the plain incoming gradient of the last block
+    assert packs == [Xl.dtype, y.dtype]                        # + the plain incoming gradient of the last block, in its own dtype
     assert Xl.grad is not None and Xl.grad.is_contiguous()
 
 
@@ -465,7 +464,7 @@ def test_pack_rows_typed_bits_and_contract(T, dst):
         want = ops.new_rows(B, T, Cp, DT[dst], DEV)
         ops.pack_rows(Xs.float(), want)
         got = torch.full((L.rows_alloc(B, T), Cp), float("nan"), dtype=DT[dst], device=DEV)
-        ops.pack_rows_typed(Xs, got)
+        ops.pack_rows(Xs, got)
         valid = torch.zeros(L.rows_alloc(B, T), dtype=torch.bool)
         for b in range(B):
             valid[b * L.rows_tp(T) + L.ROW_PAD: b * L.rows_tp(T) + L.ROW_PAD + T] = True
@@ -474,6 +473,51 @@ def test_pack_rows_typed_bits_and_contract(T, dst):
         assert bool(torch.isnan(got[~valid]).all())                         # pad rows and slack untouched
         assert float(got[valid][:, C:].abs().max()) == 0.0
         assert torch.equal(ops.rows_view(got, B, C, T).float(), Xs.float().to(DT[dst]).float())
+
+
+def packed_randn(B, C, T, dtype):
+    from speech_decoding_amd import lib as L
+    from speech_decoding_amd import ops
+    return ops.pack_rows(torch.randn(B, C, T, device=DEV) * 3, ops.new_rows(B, T, L.pad_channels(C), dtype, DEV))
+
+
+@pytest.mark.parametrize("T", [40, 70])
+def test_unpack_rows_dtypes(T):
+    """Every (buffer dtype, output dtype) pair: the unpack into `dt` is the fp32 unpack rounded once to `dt`, bit for bit, as a
+    contiguous (B, C, T) tensor.  C = 70: the second channel tile is mostly padding; T = 70: a partial time tile."""
+    from speech_decoding_amd import ops
+    B, C = 3, 70
+    for src in DT.values():
+        buf = packed_randn(B, C, T, src)
+        ref = ops.unpack_rows(buf, B, C, T)
+        assert ref.dtype == torch.float32 and torch.equal(ref, ops.rows_view(buf, B, C, T).float())
+        for dt in DT.values():
+            out = ops.unpack_rows(buf, B, C, T, dt)
+            assert out.dtype == dt and tuple(out.shape) == (B, C, T) and out.is_contiguous()
+            assert torch.equal(out.view(torch.uint8), ref.to(dt).view(torch.uint8)), (src, dt)
+
+
+@pytest.mark.parametrize("T", [40, 70])
+def test_rows_of_roundtrip(T):
+    """rows_base is the inverse of rows_view; rows_of recognises such a view (zero copy) and packs anything else — a clone of the
+    view, a non-contiguous tensor of equal values — into the same bits."""
+    from speech_decoding_amd import ops
+    B, C = 3, 70
+    for dt in DT.values():
+        buf = packed_randn(B, C, T, dt)
+        view = ops.rows_view(buf, B, C, T)
+        base = ops.rows_base(view, B, C, T, dt)
+        assert base is not None and base.shape == buf.shape and base.data_ptr() == buf.data_ptr()
+        assert base.untyped_storage().data_ptr() == buf.untyped_storage().data_ptr()
+        got, was_view = ops.rows_of(view, C, dt)
+        assert was_view and got.data_ptr() == buf.data_ptr()
+        assert ops.rows_base(view, B, C, T, torch.float64) is None and ops.rows_base(view.clone(), B, C, T, dt) is None
+        strided = view.clone().transpose(1, 2).contiguous().transpose(1, 2)          # (B, C, T) values, t-major memory
+        assert not strided.is_contiguous() and torch.equal(strided, view)
+        for plain in (view.clone(), view.contiguous(), strided):
+            packed, was_view = ops.rows_of(plain, C, dt)
+            assert not was_view and packed.data_ptr() != buf.data_ptr()
+            assert torch.equal(packed.view(torch.uint8), buf.view(torch.uint8)), dt
 
 
 @pytest.mark.parametrize("kind", ["sa", "sb", "cb1"])

@@ -264,7 +264,7 @@ def test_resident_feed_with_packed_embeddings_hands_out_the_loss_operand():
         assert torch.equal(X, X0) and torch.equal(subj, subj0) and Y.dtype == dtype and tuple(Y.shape) == tuple(Y0.shape)
         assert torch.equal(Y.float().cpu(), Y0.to(dtype).float().cpu())
         B, F, T = Y.shape
-        assert sda_loss._rows_base(Y, B, F, T, dtype) is not None          # recognised as a row-layout view: consumed in place
+        assert ops.rows_base(Y, B, F, T, dtype) is not None          # recognised as a row-layout view: consumed in place
         # the loss on the packed view equals the loss on the fp32 batch packed per call
         from speech_decoding_amd import CLIPLoss
         lossf = CLIPLoss(args).to("cuda:0")
