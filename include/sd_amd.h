@@ -34,7 +34,9 @@ extern "C" {
                                3: sda_wgrad_args.flags (SDA_WGRAD_FLAT_ROWS), sda_stream_create_cumask / sda_stream_create_priority / sda_stream_destroy, sda_sim_gemm / sda_sim_gemm_ksplit,
                                conv3_flat takes x_pitch == w_pitch only
                                4: sda_fill_zero, sda_gather_samples, sda_clip_merge_rows; SDA_WGRAD_FLAT_ROWS with a sample permutation;
-                                  sda_clip_dz serves more than 256 speech rows (256 x 256 tiles); SDA_CONV_WIDE_TILES */
+                                  sda_clip_dz serves more than 256 speech rows (256 x 256 tiles); SDA_CONV_WIDE_TILES
+                                  (still 4, additions only: sda_robust_stats / sda_robust_stats_scratch_bytes, sda_scale_clamp_rows,
+                                  sda_gather_baseline_windows — the Brennan2018 input path) */
 #define SDA_ROW_PAD 16
 #define SDA_CH_ALIGN 64
 
@@ -452,6 +454,30 @@ int sda_collate_rows(const float* src, float* dst, long rows, int T, int baselin
  * window, win_cstride[b] is that session's channel stride in elements (device arrays of length B). dst (B, C, T). */
 int sda_collate_windows(const float* const* win_ptr, const long* win_cstride, float* dst, int B, int C, int T,
                         int baseline_len, float clamp_lim, int clamp, void* stream);
+
+/* ---- Brennan2018's input path (brennan2018.py:72-152): scale and clamp over the WHOLE recording first, then segment, then
+ * baseline-correct each segment.  A "row" of the next two entry points is n_chunks pieces of chunk_len floats, chunk_stride
+ * elements apart, starting at x + row * row_stride:
+ *     subject-wise (brennan2018.py:114-126) on X (S, C, L): rows = S * C, row_stride = L, n_chunks = 1;
+ *     pooled       (brennan2018.py:127-134):                rows = C, row_stride = L, n_chunks = S, chunk_stride = C * L. ---- */
+/* RobustScaler.fit over each row (brennan2018.py:117,130): centre[row] = median, scale[row] = 75th - 25th percentile, a zero
+ * scale becomes 1 (sklearn).  numpy's "linear" rule: position q * (N - 1) and its fraction in double, the two elements at
+ * floor and floor + 1 SELECTED exactly (radix select on order-preserving keys: they are elements of the row), one fp32
+ * a + (b - a) * g.  Deterministic: the same input gives the same bits.  2 <= N = n_chunks * chunk_len < 2^31, rows <= 65535.
+ * Preconditions: no NaN in the rows; +-inf order like any value (-0.0 counts as +0.0).  scratch: device memory of
+ * sda_robust_stats_scratch_bytes(rows) bytes, contents irrelevant before and after. */
+long sda_robust_stats_scratch_bytes(long rows);
+int sda_robust_stats(const float* x, long rows, long row_stride, int n_chunks, long chunk_len, long chunk_stride,
+                     float* centre, float* scale, void* scratch, long scratch_bytes, void* stream);
+/* RobustScaler.transform + clamp_ (brennan2018.py:120-124,130-133): y = (x - centre[row]) / scale[row], limited to
+ * +-clamp_lim when `clamp`; y is laid out like x (same strides); y == x (in place) is allowed. */
+int sda_scale_clamp_rows(const float* x, float* y, long rows, long row_stride, int n_chunks, long chunk_len, long chunk_stride,
+                         const float* centre, const float* scale, float clamp_lim, int clamp, void* stream);
+/* Segment gather + baseline_correction (brennan2018.py:136-152): dst[b, c, :] = w - mean(w[:baseline_len]) with w the T
+ * samples at win_ptr[b] + c * win_cstride[b] (the pointer tables of sda_collate_windows); dst fp32 (B, C, T), any T >= 1;
+ * baseline_len = 0 copies the window.  The baseline sum runs in a fixed order. */
+int sda_gather_baseline_windows(const float* const* win_ptr, const long* win_cstride, float* dst, int B, int C, int T,
+                                int baseline_len, void* stream);
 
 /* ---- Frozen wav2vec 2.0 speech embedder (utils/wav2vec_util.py:14-32 calls the third-party HF Wav2Vec2Model; this is that
  * model's published forward for the layer-norm / stable-layer-norm variant xlsr-53 uses).  Every Linear, strided Conv1d and

@@ -5,5 +5,6 @@ from .models import BrainEncoder, Classifier              # noqa: F401
 from .loss import CLIPLoss, MSELoss, torch_exp, torch_log   # noqa: F401
 from .retrieval import SpeechBank, Retrieval, retrieve   # noqa: F401
 from .config import Config, load_config                   # noqa: F401
+from .data import ResidentSubjectFeed                     # noqa: F401
 
-__all__ = ["BrainEncoder", "Classifier", "CLIPLoss", "MSELoss", "SpeechBank", "Retrieval", "retrieve", "torch_exp", "torch_log", "Config", "load_config", "load_library", "SdaError"]
+__all__ = ["BrainEncoder", "Classifier", "CLIPLoss", "MSELoss", "SpeechBank", "Retrieval", "retrieve", "ResidentSubjectFeed", "torch_exp", "torch_log", "Config", "load_config", "load_library", "SdaError"]

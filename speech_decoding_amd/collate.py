@@ -24,6 +24,81 @@ def robust_scale_clamp(X: torch.Tensor, baseline_len_samp: int, clamp_lim: float
     return out
 
 
+def _row_layout(X: torch.Tensor, pooled: bool):
+    """(rows, row_stride, n_chunks, chunk_len, chunk_stride) of a contiguous (S, C, L) tensor: one row per (subject, channel),
+    or — pooled — one row per channel made of the S subjects' pieces (brennan2018.py:114-134), with no rearranging copy."""
+    if not X.is_cuda:
+        raise L.SdaError("whole-recording scaling needs device tensors (no CPU fallback)")
+    if X.dim() != 3 or X.dtype != torch.float32 or not X.is_contiguous():
+        raise L.SdaError("whole-recording scaling: a contiguous fp32 (S, C, L) tensor")
+    S, C, Ln = X.shape
+    return (C, Ln, S, Ln, C * Ln) if pooled else (S * C, Ln, 1, Ln, Ln)
+
+
+def robust_stats(X: torch.Tensor, pooled: bool = False):
+    """RobustScaler.fit over whole recordings (brennan2018.py:117,130), sda_robust_stats: X (S, C, L) fp32 on the device ->
+    (centre, scale), each (S, C) — or (C,) when `pooled` (every subject's samples of a channel in one row).  Median and
+    inter-quartile range by exact selection, numpy's "linear" rule, zero scale -> 1.  X must hold no NaN."""
+    rows, rstride, nch, clen, cstride = _row_layout(X, pooled)
+    lib = L.load()
+    out = torch.empty((2, rows), dtype=torch.float32, device=X.device)
+    nbytes = int(lib.sda_robust_stats_scratch_bytes(rows))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
+    with torch.cuda.device(X.device):
+        L.check(lib.sda_robust_stats(X.data_ptr(), rows, rstride, nch, clen, cstride, out[0].data_ptr(), out[1].data_ptr(),
+                                     scratch.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream), "robust_stats")
+    shape = (X.shape[1],) if pooled else tuple(X.shape[:2])
+    return out[0].reshape(shape), out[1].reshape(shape)
+
+
+def scale_clamp_rows(X: torch.Tensor, centre: torch.Tensor, scale: torch.Tensor, clamp_lim: float, clamp: bool = True,
+                     pooled: bool = False, out: torch.Tensor = None) -> torch.Tensor:
+    """RobustScaler.transform + clamp_ (brennan2018.py:120-124,130-133), sda_scale_clamp_rows: (X - centre) / scale per row of
+    robust_stats' layout, limited to +-clamp_lim.  `out`: a contiguous tensor of X's shape; `out=X` works in place."""
+    rows, rstride, nch, clen, cstride = _row_layout(X, pooled)
+    out = torch.empty_like(X) if out is None else out
+    if out.shape != X.shape or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous():
+        raise L.SdaError("scale_clamp_rows: out must be a contiguous fp32 device tensor of X's shape")
+    centre, scale = centre.reshape(-1), scale.reshape(-1)
+    for t in (centre, scale):
+        if not t.is_cuda or t.dtype != torch.float32 or t.numel() != rows or not t.is_contiguous():
+            raise L.SdaError("scale_clamp_rows: centre and scale must hold one fp32 device value per row")
+    with torch.cuda.device(X.device):
+        L.check(L.load().sda_scale_clamp_rows(X.data_ptr(), out.data_ptr(), rows, rstride, nch, clen, cstride, centre.data_ptr(),
+                                              scale.data_ptr(), float(clamp_lim), int(bool(clamp)),
+                                              torch.cuda.current_stream().cuda_stream), "scale_clamp_rows")
+    return out
+
+
+def gather_baseline_windows(X: torch.Tensor, subjects, starts, T: int, baseline_len_samp: int) -> torch.Tensor:
+    """Segment gather + baseline_correction (brennan2018.py:136-152), sda_gather_baseline_windows: X (S, C, L) fp32 resident;
+    window b = X[subjects[b], :, starts[b] : starts[b] + T] minus the mean of its first baseline_len_samp samples, per channel.
+    subjects, starts: host integer sequences of length B -> (B, C, T) fp32."""
+    if not X.is_cuda:
+        raise L.SdaError("gather_baseline_windows needs device tensors (no CPU fallback)")
+    if X.dim() != 3 or X.dtype != torch.float32 or not X.is_contiguous():
+        raise L.SdaError("gather_baseline_windows: a contiguous fp32 (S, C, L) tensor")
+    S, C, Ln = X.shape
+    import numpy as np
+    sub = np.asarray(subjects, dtype=np.int64).reshape(-1)
+    on = np.asarray(starts, dtype=np.int64).reshape(-1)
+    T, nb = int(T), int(baseline_len_samp)
+    if len(sub) != len(on) or len(sub) < 1:
+        raise L.SdaError("gather_baseline_windows: one subject and one start per window")
+    if T < 1 or nb < 0 or nb > T:
+        raise L.SdaError("gather_baseline_windows: 0 <= baseline_len_samp <= T")
+    if bool(((sub < 0) | (sub >= S) | (on < 0) | (on + T > Ln)).any()):
+        raise IndexError("segment window leaves its recording")
+    dev = X.device
+    out = torch.empty((len(sub), C, T), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ptrs = ops.upload_small(X.data_ptr() + 4 * (sub * (C * Ln) + on), dev)
+        cstr = ops.upload_small(np.full(len(sub), Ln, dtype=np.int64), dev)
+        L.check(L.load().sda_gather_baseline_windows(ptrs.data_ptr(), cstr.data_ptr(), out.data_ptr(), len(sub), C, T, nb,
+                                                     torch.cuda.current_stream().cuda_stream), "gather_baseline_windows")
+    return out
+
+
 class Gwilliams2022Collator(nn.Module):
     def __init__(self, args, device="cuda"):
         super().__init__()

@@ -10,7 +10,12 @@ What it mirrors (SeanNobel/speech-decoding):
   * dataclass/gwilliams2022.py:129-142 (`__getitem__`: a speech segment i -> a random recording of that task, the MEG
     window at the segment's onset, the subject index) and :640-661 (`Gwilliams2022Collator`: baseline correction, robust
     scaling, clamp) — here `ResidentSegmentFeed`: the recordings stay in HBM, a batch is (recording, onset) pairs turned
-    into X (B, C, T) by ONE kernel (collate.ResidentSegments), Y rows are gathered from the resident embedding table.
+    into X (B, C, T) by ONE kernel (collate.ResidentSegments), Y rows are gathered from the resident embedding table;
+  * dataclass/brennan2018.py:72-152 (shift, trim, RobustScaler + clamp over the WHOLE recording per subject and channel or
+    per channel with the subjects pooled, split into chunks, baseline correction per chunk; `__getitem__`: chunk i of a
+    random subject) — here `ResidentSubjectFeed`: the (S, C, L) array is scaled once on the device by exact order statistics
+    (collate.robust_stats / scale_clamp_rows) and stays resident; a batch is (subject, chunk) pairs turned into X by one
+    kernel (collate.gather_baseline_windows).
 """
 from __future__ import annotations
 
@@ -19,6 +24,7 @@ from typing import Iterator, List, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import collate as _collate
 from .collate import ResidentSegments
 
 
@@ -50,7 +56,46 @@ class ShardedRandomSampler:
         return self.updates
 
 
-class ResidentSegmentFeed:
+class _ResidentEmbeddings:
+    """The speech side shared by the resident feeds: Y (N, F, T) embeddings on the device, optionally kept as a row-layout
+    table in the compute dtype (pack_embeddings), one gather per batch."""
+
+    Y: torch.Tensor
+    _Yt = None                # row-layout table in the compute dtype (pack_embeddings)
+
+    def pack_embeddings(self, dtype: torch.dtype, chunk: int = 128):
+        """Keep the speech embeddings resident as a row-layout table in `dtype` (the encoder's compute dtype): batch() then
+        hands out Y as a zero-copy (B, F, T) view of ONE gather kernel's output, which CLIPLoss consumes as its packed operand —
+        per step 0.4 GB of HBM traffic instead of the 1.3 GB of index_select + sda_pack_rows (batch 256, bf16).  Values: each
+        embedding is rounded to `dtype` once here instead of once per step in the loss's pack — the same numbers."""
+        from . import lib as L
+        from . import ops
+        N, F, T = self.Y.shape
+        Tp, Fp = L.rows_tp(T), L.pad_channels(F)
+        table = torch.zeros((N * Tp + L.rows_alloc(1, T) - Tp, Fp), dtype=dtype, device=self.Y.device)
+        for k in range(0, N, chunk):
+            n = min(chunk, N - k)
+            ops.pack_rows(self.Y[k: k + n], table[k * Tp:])
+        self._Yt = table
+        return self
+
+    def _gather_Y(self, ii: np.ndarray) -> torch.Tensor:
+        """Y of the segments `ii` (host int64 indices; duplicates allowed)."""
+        if self._Yt is not None:
+            # embeddings resident in ROW LAYOUT in the compute dtype (pack_embeddings): the gathered batch IS the loss's packed
+            # operand — CLIPLoss recognises the view and neither copies nor re-packs it
+            from . import ops
+            B, (F, T) = len(ii), self.Y.shape[1:]
+            with torch.cuda.device(self._Yt.device):
+                return ops.rows_view(ops.gather_samples(self._Yt, ops.upload_small(ii, self._Yt.device), B, T), B, F, T)
+        if self.Y.is_cuda:
+            from . import ops
+            with torch.cuda.device(self.Y.device):
+                return self.Y.index_select(0, ops.upload_small(ii, self.Y.device))    # (index table in kernel arguments: no host wait)
+        return self.Y.index_select(0, torch.as_tensor(ii, dtype=torch.int64))
+
+
+class ResidentSegmentFeed(_ResidentEmbeddings):
     """recordings: list of (C, L_r) device tensors, one per (subject, session) recording, each with the subject index
     `rec_subject[r]` and the task `rec_task[r]` it recorded; onsets[r][j] = first MEG sample of the j-th speech segment of
     that task; seg_task[i], seg_in_task[i] = (task, position) of global speech segment i (gwilliams2022.py: `segment_to_task`);
@@ -80,22 +125,6 @@ class ResidentSegmentFeed:
     def __len__(self) -> int:
         return int(self.Y.shape[0])
 
-    def pack_embeddings(self, dtype: torch.dtype, chunk: int = 128):
-        """Keep the speech embeddings resident as a row-layout table in `dtype` (the encoder's compute dtype): batch() then
-        hands out Y as a zero-copy (B, F, T) view of ONE gather kernel's output, which CLIPLoss consumes as its packed operand —
-        per step 0.4 GB of HBM traffic instead of the 1.3 GB of index_select + sda_pack_rows (batch 256, bf16).  Values: each
-        embedding is rounded to `dtype` once here instead of once per step in the loss's pack — the same numbers."""
-        from . import lib as L
-        from . import ops
-        N, F, T = self.Y.shape
-        Tp, Fp = L.rows_tp(T), L.pad_channels(F)
-        table = torch.zeros((N * Tp + L.rows_alloc(1, T) - Tp, Fp), dtype=dtype, device=self.Y.device)
-        for k in range(0, N, chunk):
-            n = min(chunk, N - k)
-            ops.pack_rows(self.Y[k: k + n], table[k * Tp:])
-        self._Yt = table
-        return self
-
     def draw_recordings(self, idx) -> np.ndarray:
         """gwilliams2022.py:133: one random recording of each segment's task, drawn item by item from the feed's generator
         (`rng.choice(recordings of the task)`).  When every task has the same number of recordings the whole batch is ONE
@@ -116,19 +145,7 @@ class ResidentSegmentFeed:
         rec = self.draw_recordings(ii) if rec is None else np.asarray(rec, dtype=np.int64)
         on = self._onset_of(rec, self.seg_in_task[ii])
         X = self.rs.batch(rec, on)
-        if self._Yt is not None:
-            # embeddings resident in ROW LAYOUT in the compute dtype (pack_embeddings): the gathered batch IS the loss's packed
-            # operand — CLIPLoss recognises the view and neither copies nor re-packs it
-            from . import ops
-            B, (F, T) = len(ii), self.Y.shape[1:]
-            with torch.cuda.device(self._Yt.device):
-                Y = ops.rows_view(ops.gather_samples(self._Yt, ops.upload_small(ii, self._Yt.device), B, T), B, F, T)
-        elif self.Y.is_cuda:
-            from . import ops
-            with torch.cuda.device(self.Y.device):
-                Y = self.Y.index_select(0, ops.upload_small(ii, self.Y.device))    # (index table in kernel arguments: no host wait)
-        else:
-            Y = self.Y.index_select(0, idx)
+        Y = self._gather_Y(ii)
         return X, Y, torch.from_numpy(self.rec_subject[rec].astype(np.int32))
 
     def _onset_of(self, rec: np.ndarray, j: np.ndarray) -> np.ndarray:
@@ -196,3 +213,126 @@ def synthetic_resident_dataset(args, device, *, n_segments: int, n_tasks: int = 
     n_train = int(n_segments * float(args.split_ratio))
     perm = np.random.RandomState(seed).permutation(n_segments)
     return feed, perm[:n_train], perm[n_train:]
+
+
+def subject_feed_geometry(length: int, srate: float, seq_len_sec: float, baseline_len_sec: float, shift_ms: float = 150,
+                          segment_len: int = None) -> dict:
+    """The integer arithmetic of brennan2018.py:72-104 and :296 for a recording of `length` samples at `srate` Hz:
+    shift (samples dropped from the front of X and the end of Y), seq_len_samp, baseline_len_samp, trim_len (the shifted length
+    cut to a multiple of seq_len_samp), reference_segment_len (what the reference's `split(num_segments)` really cuts:
+    trim_len // seq_len_samp samples per chunk), segment_len (the one used: `segment_len` or seq_len_samp) and n_segments."""
+    shift = int(srate * (shift_ms / 1000))
+    seq = int(seq_len_sec * srate)
+    nb = int(seq * baseline_len_sec / seq_len_sec)
+    if seq < 1:
+        raise ValueError("seq_len_sec * srate is below one sample")
+    shifted = int(length) - shift
+    trim = (shifted // seq) * seq
+    if shift < 0 or trim < seq:
+        raise ValueError(f"a recording of {length} samples holds no segment of {seq} after a shift of {shift}")
+    seg = seq if segment_len is None else int(segment_len)
+    if seg < 1 or trim % seg:
+        raise ValueError(f"segment_len={seg} does not divide the trimmed length {trim}")
+    if nb > seg:
+        raise ValueError(f"baseline of {nb} samples is longer than a segment of {seg}")
+    return {"shift": shift, "seq_len_samp": seq, "baseline_len_samp": nb, "trim_len": trim, "reference_segment_len": trim // seq,
+            "segment_len": seg, "n_segments": trim // seg}
+
+
+class ResidentSubjectFeed(_ResidentEmbeddings):
+    """Brennan2018's input path on the device (brennan2018.py:72-152).  X (S, C, L): every subject's recording of the SAME
+    stimulus, Y (F, L): the speech embeddings of that stimulus, both on the device — the contents of the reference's
+    `processed_X.pt` ("X", with "srate") and `embd_wav2vec.pt`.  Construction, on the feed's own copy of X:
+      shift X forward by shift_ms (X[..., shift:], Y[:, :-shift]); trim to a multiple of seq_len_samp = int(seq_len_sec * srate);
+      RobustScaler over the whole recording — per (subject, channel), or per channel with all subjects pooled when
+      `subject_wise` is False — and clamp to +-clamp_lim (collate.robust_stats + scale_clamp_rows, in place);
+      cut into segments; baseline correction (mean of the first baseline_len_samp samples) per segment at batch time.
+    Segments of X are not materialised: segment i of subject s is columns [i * seg, (i + 1) * seg) of the scaled recording.
+
+    segment_len: the default, seq_len_samp, is the documented intent (T = 360 at 120 Hz, 3 s).  The reference calls
+    `split(num_segments)` and therefore really cuts chunks of trim_len // seq_len_samp samples (and seq_len_samp of them,
+    up to a remainder): pass segment_len=subject_feed_geometry(...)["reference_segment_len"] to reproduce its files' chunks.
+    A segment_len that does not divide the trimmed length raises ValueError.
+
+    batch(idx) -> (X (B, C, seg) fp32, Y (B, F, seg), subject_idxs int32); the chunk ids are idx itself."""
+
+    def __init__(self, X: torch.Tensor, Y: torch.Tensor, *, srate: float, seq_len_sec: float, baseline_len_sec: float,
+                 clamp_lim: float, clamp: bool = True, subject_wise: bool = True, shift_ms: float = 150, segment_len: int = None,
+                 seed: int = 0):
+        if X.dim() != 3 or Y.dim() != 2 or X.shape[-1] != Y.shape[-1]:
+            raise ValueError("X (S, C, L) and Y (F, L) of the same length")
+        geo = subject_feed_geometry(X.shape[-1], srate, seq_len_sec, baseline_len_sec, shift_ms, segment_len)
+        self.geometry = geo
+        shift, trim, seg = geo["shift"], geo["trim_len"], geo["segment_len"]
+        self.S, self.C = int(X.shape[0]), int(X.shape[1])
+        self.seg, self.nb, self.subject_wise = seg, geo["baseline_len_samp"], bool(subject_wise)
+        # the feed's own contiguous copy of the shifted, trimmed recording: scaled in place, the caller's X is left alone
+        Xs = X[..., shift: shift + trim].float().contiguous()
+        if Xs.data_ptr() == X.data_ptr():
+            Xs = Xs.clone()
+        self.centre, self.scale = _collate.robust_stats(Xs, pooled=not self.subject_wise)
+        self.X = _collate.scale_clamp_rows(Xs, self.centre, self.scale, float(clamp_lim), bool(clamp), pooled=not self.subject_wise,
+                                           out=Xs)
+        n = geo["n_segments"]
+        F = int(Y.shape[0])
+        # (Y[:, :-shift] then [:trim_len]: the first trim_len samples; Y's segments ARE materialised, one embedding per item)
+        self.Y = Y[:, :trim].reshape(F, n, seg).permute(1, 0, 2).contiguous()
+        self._Yt = None
+        self.rng = np.random.RandomState(seed)       # (the global generator stays reserved for SpatialDropout, see above)
+
+    def __len__(self) -> int:
+        return int(self.geometry["n_segments"])
+
+    def draw_subjects(self, n: int) -> np.ndarray:
+        """brennan2018.py:148 draws `np.random.choice(num_subjects)` item by item; one vectorised randint(0, S, size=n) from the
+        feed's own generator is the same stream of values."""
+        return self.rng.randint(0, self.S, size=int(n)).astype(np.int64)
+
+    def batch(self, idx, subjects=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """idx: this rank's segment indices (duplicates allowed); subjects: their subjects when the caller drew them (data
+        parallelism: drawn for the GLOBAL batch on every rank alike and sliced, see batches())."""
+        ii = np.asarray(torch.as_tensor(idx, dtype=torch.int64).numpy(), dtype=np.int64).reshape(-1)
+        if len(ii) and (ii.min() < 0 or ii.max() >= len(self)):
+            raise IndexError("segment index outside the feed")
+        sub = self.draw_subjects(len(ii)) if subjects is None else np.asarray(subjects, dtype=np.int64).reshape(-1)
+        X = _collate.gather_baseline_windows(self.X, sub, ii * self.seg, self.seg, self.nb)
+        return X, self._gather_Y(ii), torch.from_numpy(sub.astype(np.int32))
+
+    def batches(self, sampler, index_map=None) -> Iterator[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+        """One (X, Y, subject_idxs) per batch of `sampler` (ResidentSegmentFeed.batches): with a ShardedRandomSampler of more
+        than one rank the subjects of the GLOBAL batch are drawn on every rank alike and the rank keeps its slice."""
+        if hasattr(sampler, "global_batches") and getattr(sampler, "world", 1) > 1:
+            per = sampler.batch_size // sampler.world
+            lo = sampler.rank * per
+            for gidx in sampler.global_batches():
+                g = gidx.numpy() if index_map is None else np.asarray(index_map)[gidx.numpy()]
+                sub = self.draw_subjects(len(g))
+                yield self.batch(g[lo: lo + per], subjects=sub[lo: lo + per])
+            return
+        for idx in sampler:
+            i = idx.numpy() if isinstance(idx, torch.Tensor) else np.asarray(idx)
+            yield self.batch(i if index_map is None else np.asarray(index_map)[i])
+
+
+def synthetic_subject_dataset(args, device, *, length: int, seed: int = 1234) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Seeded stand-in with the STRUCTURE of Brennan2018: S subjects hear one stimulus; a shared latent brain response
+    (C, length) reaches subject s with a per-(subject, channel) gain spread over two decades, an offset and noise — what the
+    whole-recording scaling removes (and what makes subject_wise matter) — plus rare artefact spikes for the clamp.  The
+    speech embedding at sample t is a fixed linear read-out of the latent response `shift_len` ms LATER plus noise, so
+    retrieval is learnable after the feed's shift.  Returns (X (S, C, length), Y (F, length)) on `device`."""
+    C = int(args.get("num_channels", 208 if args.dataset == "Gwilliams2022" else 60))
+    F = 1024 if args.preprocs["last4layers"] else int(args.F)
+    S = int(args.num_subjects)
+    shift = int(args.preprocs["brain_resample_rate"] * (args.preprocs.get("shift_len", 150) / 1000))
+    g = torch.Generator().manual_seed(seed)
+    latent = torch.randn(C, length, generator=g)
+    gain = 10.0 ** (2.0 * torch.rand(S, C, 1, generator=g) - 1.0)
+    offset = 3.0 * torch.randn(S, C, 1, generator=g)
+    X = (latent[None] + 0.3 * torch.randn(S, C, length, generator=g)) * gain + offset * gain
+    spikes = torch.rand(S, C, length, generator=g) < 1e-3
+    X = torch.where(spikes, X * 60.0, X)
+    P = torch.randn(F, C, generator=g) / np.sqrt(C)
+    Y = torch.zeros(F, length)
+    Y[:, : length - shift] = (P @ latent)[:, shift:] / 1.35
+    Y = Y + 0.5 * torch.randn(F, length, generator=g)
+    return X.to(device), Y.to(device)

@@ -125,6 +125,10 @@ SIGNATURES = {
     "sda_clip_grad_y_finish": (i32, [vp, i32, i32, vp, vp, i32, vp, f32, i32, i32, vp, vp, vp]),
     "sda_collate_rows": (i32, [vp, vp, i64, i32, i32, f32, i32, vp]),
     "sda_collate_windows": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
+    "sda_robust_stats_scratch_bytes": (i64, [i64]),
+    "sda_robust_stats": (i32, [vp, i64, i64, i32, i64, i64, vp, vp, vp, i64, vp]),
+    "sda_scale_clamp_rows": (i32, [vp, vp, i64, i64, i32, i64, i64, vp, vp, f32, i32, vp]),
+    "sda_gather_baseline_windows": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "sda_clip_ranks": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "sda_retrieval_scores_floats": (i64, [i32, i32, i32]),
     "sda_retrieval_select": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),

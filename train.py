@@ -14,6 +14,8 @@ What is kept from the reference loop (train.py:148-259):
     loss (train.py:200-209);
   * evaluation in eval() mode on the whole test split as ONE batch (train.py:99,211-233);
   * the per-epoch print line and the optional W&B scalar names; `model_last.pt` = encoder.state_dict().
+`data=continuous` (with dataset=Brennan2018) runs that dataset's own input path on the GPU: whole-recording robust scaling
+(preprocs.subject_wise), clamp, segment gather with baseline correction (speech_decoding_amd.data.ResidentSubjectFeed).
 What is not: the M/EEG + wav2vec2 dataset classes (out of scope, they need MNE, the raw recordings and
 un-downloadable weights).  `--data synthetic` (default) builds a seeded stand-in with the same tensor
 shapes; a real dataset object can be passed to `run()` as (train_batches, test_batch) callables.
@@ -75,6 +77,9 @@ class SyntheticSegments:
 
 def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Callable] = None, log=print):
     import torch.distributed as dist
+    data_kind = str(args.get("data", "pool"))
+    if train_batches is None and data_kind == "continuous" and args.dataset != "Brennan2018":
+        raise ValueError("data=continuous is Brennan2018's input path (one stimulus, every subject): use dataset=Brennan2018")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -98,9 +103,12 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
     # data=pool (default): a resident pool of ready-made segments, every rank slicing its shard out of the global batch;
     # data=resident: the reference's own input path on the GPU — recordings resident in HBM, RandomSampler(replacement=True)
     # (get_dataloaders.py:48-87) cut into rank shards so that no rank materialises another rank's samples, window gather +
-    # baseline correction + robust scaling + clamp (gwilliams2022.py:129-142,640-661) as one kernel per batch
+    # baseline correction + robust scaling + clamp (gwilliams2022.py:129-142,640-661) as one kernel per batch;
+    # data=continuous (dataset=Brennan2018): that dataset's own input path — the (subjects, channels, time) recording of one
+    # stimulus resident in HBM, robust scaling + clamp over the WHOLE recording once (preprocs.subject_wise: per subject, or all
+    # subjects pooled), a batch = chunk i of a random subject with its baseline removed (brennan2018.py:72-152)
     feeds_local_shards = False
-    if train_batches is None and str(args.get("data", "pool")) == "resident":
+    if train_batches is None and data_kind == "resident":
         from speech_decoding_amd.data import ShardedRandomSampler, synthetic_resident_dataset
         n_seg = int(args.get("synthetic_segments", 4 * int(args.batch_size)))
         feed, train_idx, test_idx = synthetic_resident_dataset(args, device, n_segments=n_seg, seed=1234)
@@ -112,6 +120,34 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
             sampler = ShardedRandomSampler(len(train_idx), int(args.batch_size), updates, rank, world, seed=4321 + epoch_no[0])
             epoch_no[0] += 1
             # (under data parallelism the recordings of the whole global batch are drawn on every rank alike and sliced)
+            yield from feed.batches(sampler, index_map=train_idx)
+
+        def test_batch():
+            lo, hi = shard_range(len(test_idx), rank, world)
+            return feed.batch(test_idx[lo:hi])
+        feeds_local_shards = True
+    elif train_batches is None and data_kind == "continuous":
+        from speech_decoding_amd.data import ResidentSubjectFeed, ShardedRandomSampler, synthetic_subject_dataset
+        pre = args.preprocs
+        rate = pre["brain_resample_rate"]
+        seq = int(pre["seq_len_sec"] * rate)
+        n_seg = int(args.get("synthetic_segments", 4 * int(args.batch_size)))
+        shift_ms = pre.get("shift_len", 150) if pre.get("shift_brain", True) else 0
+        Xc, Yc = synthetic_subject_dataset(args, device, length=n_seg * seq + int(rate * (shift_ms / 1000)) + seq // 3, seed=1234)
+        feed = ResidentSubjectFeed(Xc, Yc, srate=rate, seq_len_sec=pre["seq_len_sec"], baseline_len_sec=pre["baseline_len_sec"],
+                                   clamp_lim=float(pre["clamp_lim"]), clamp=bool(pre["clamp"]),
+                                   subject_wise=bool(pre.get("subject_wise", True)), shift_ms=shift_ms, seed=1234 + 17)
+        del Xc, Yc
+        n_train = int(len(feed) * float(args.split_ratio))
+        perm = np.random.RandomState(1234).permutation(len(feed))
+        train_idx, test_idx = perm[:n_train], perm[n_train:]
+        updates = int(args.get("updates_per_epoch", max(1, len(train_idx) // int(args.batch_size))))
+        epoch_no = [0]
+        pack_resident_embeddings = feed
+
+        def train_batches():
+            sampler = ShardedRandomSampler(len(train_idx), int(args.batch_size), updates, rank, world, seed=4321 + epoch_no[0])
+            epoch_no[0] += 1
             yield from feed.batches(sampler, index_map=train_idx)
 
         def test_batch():
