@@ -187,10 +187,15 @@ class Wav2Vec2Embedder:
             rows = lambda t, c: ops.new_rows(1, t, c, dt, dev)
             G, K = cfg.num_conv_pos_embedding_groups, cfg.num_conv_pos_embeddings
             lead = K // 2 + L.ROW_PAD
+            # xg: a view row of the positional conv's GEMM is K buffer rows long, and the GEMM fetches whole 128-row tiles with
+            # the row index clamped to the LAST buffer row, so it reads up to K - 1 rows behind the last group: they are allocated
+            # here (zero, feeding outputs that are never stored), behind the (G, rows, gwp) view the kernels are given
+            grows = lead + T + K + 2 * L.ROW_PAD
+            xg_store = torch.zeros((G * grows + K) * self.gwp, dtype=dt, device=dev)
             ws = dict(feat=[rows(t, self.Cp) for t in frames], h=[rows(T, self.Hp) for _ in range(8)], a=rows(T, self.Hp),
                       o=rows(T, self.Hp), qk=rows(T, 2 * self.Hp), u=rows(T, self.Fp),
                       vt=torch.zeros((cfg.hidden_size, (T + 63) // 64 * 64), dtype=dt, device=dev),
-                      xg=torch.zeros((G, lead + T + K + 2 * L.ROW_PAD, self.gwp), dtype=dt, device=dev),
+                      xg=xg_store[:G * grows * self.gwp].view(G, grows, self.gwp),
                       lead=lead)
             ws["yg"] = torch.zeros_like(ws["xg"])              # same row geometry: the G groups are ONE batched GEMM's samples
             # split-K scratch of ops.linear_rows: ksplit * T * Cout_p <= (256 / tiles) * T * Cout_p ~ 256 * 128 * 160 floats
