@@ -36,7 +36,7 @@ extern "C" {
                                4: sda_fill_zero, sda_gather_samples, sda_clip_merge_rows; SDA_WGRAD_FLAT_ROWS with a sample permutation;
                                   sda_clip_dz serves more than 256 speech rows (256 x 256 tiles); SDA_CONV_WIDE_TILES
                                   (still 4, additions only: sda_robust_stats / sda_robust_stats_scratch_bytes, sda_scale_clamp_rows,
-                                  sda_gather_baseline_windows — the Brennan2018 input path) */
+                                  sda_gather_baseline_windows — the Brennan2018 input path; sda_window_gemm_f32 — FIR filter / sinc resampler) */
 #define SDA_ROW_PAD 16
 #define SDA_CH_ALIGN 64
 
@@ -538,6 +538,19 @@ int sda_mse_backward(const void* z, int z_cp, int z_dtype, const void* y, int y_
  * Null pointers, bad sizes or misaligned operands return -1 (sda_last_error) and launch nothing. */
 int sda_input_grad(const void* G, long g_pitch, const void* W, const int* widx, int nW, int Kp, int Cp, int B, int C, int T,
                    int dtype, void* out, int out_dtype, void* stream);
+
+/* ---- Signal conditioning in front of the data (ABI 4, addition): the FIR band-pass of the raw recordings
+ * (mne.filter.filter_data, gwilliams2022.py:253 / brennan2018.py:263) and the polyphase sinc resampler of the audio
+ * (torchaudio.functional.resample, gwilliams2022.py:349 / brennan2018.py:172) are both a fixed matrix applied to strided
+ * windows of each row (csrc/window_gemm.hip):
+ *     out[r][m * N + j] = sum_{k < K} x[r][m * S + k] * B[k][j],     r < rows, m < frames, j < N
+ * fp32 in and out, exact-fp32 MFMA (a k-ordered fmaf chain per output).  x: rows x_row_stride elements apart, of which
+ * x[r][0 ... (frames - 1) * S + K - 1] must be readable — nothing else is read; B: K x N row-major; out: rows out_row_stride
+ * elements apart, out[r][0 ... frames * N - 1] written and nothing else.  Any rows, frames, S, K, N >= 1; no padding or
+ * alignment of N, K or the pointers beyond the element's.  Null pointers, non-positive sizes, out_row_stride < frames * N and
+ * x_row_stride < (frames - 1) * S + K return -1 (sda_last_error) and launch nothing. */
+int sda_window_gemm_f32(const float* x, long x_row_stride, int rows, long frames, int S, int K, const float* B, int N,
+                        float* out, long out_row_stride, void* stream);
 
 #ifdef __cplusplus
 }

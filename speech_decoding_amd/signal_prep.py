@@ -1,0 +1,238 @@
+"""Signal conditioning on the GPU: from raw recordings and audio to the arrays the datasets are built from.
+
+What the reference does with MNE and torchaudio on CPU workers before anything else can start:
+
+    mne.filter.filter_data(raw, sfreq, l_freq, h_freq)             gwilliams2022.py:253, brennan2018.py:263   -> filter_data
+    torchaudio.functional.resample(wave, sr, 16000, lowpass_filter_width=128)
+                                                                   gwilliams2022.py:349, brennan2018.py:172   -> resample_audio
+    mne.filter.resample(filtered, down=orig / 120)                 gwilliams2022.py:258, brennan2018.py:270   -> wav2vec2.resample_fft
+
+The first two are one computation — a fixed matrix applied to strided windows of each row,
+
+    out[r, m N + j] = sum_{k < K} x[r, m S + k] B[k, j]
+
+— and run on one kernel, `sda_window_gemm_f32` (csrc/window_gemm.hip, exact-fp32 MFMA).  The polyphase resampler is it with
+S = reduced input rate, N = reduced output rate, B = bank^T; the FIR filter is the degenerate resampler S = N = 1 with G
+consecutive frames grouped into one, which `window_matrix` does for any bank.  `brain_preproc` and `speech_embeddings` compose
+the three calls as the reference's dataset classes do.  Device tensors only: there is no CPU path.
+
+Parity.  Neither mne nor torchaudio can be installed next to this build, so bit-parity with `mne.filter.create_filter` and
+with `torchaudio.functional.resample` is UNPINNED: `bandpass_taps` follows mne's documented "firwin" design rule and
+`sinc_resample_bank` torchaudio's documented `sinc_interp_hann` kernel, and both are tested against float64 restatements of
+those rules, not against the libraries.  `fir_filter` takes arbitrary taps, so a user with mne can pass mne's own
+(`mne.filter.create_filter(...)`).
+"""
+from __future__ import annotations
+
+import math
+from functools import lru_cache
+from typing import Tuple
+
+import numpy as np
+import torch
+
+from . import lib as L
+from .wav2vec2 import resample_fft
+
+MAX_GROUP = 64          # largest G window_group considers = the kernel's output tile width
+
+
+def window_group(P: int, S: int, Kw: int) -> int:
+    """The number G of consecutive frames `window_matrix` should group for a bank of P phases, stride S and Kw taps.
+
+    The kernel computes 64-column output tiles over the grouped contraction Kw + (G - 1) S, so of the multiply-adds it issues
+    the share  G P / (64 ceil(G P / 64)) * Kw / (Kw + (G - 1) S)  is useful: the first factor is the fill of the column
+    tiles, the second the taps against the zeros the Toeplitz blocks add.  G = the value in 1 ... 64 with the largest share,
+    the smallest such G on ties.  (FIR, P = S = 1: G = 64 once Kw > 63; 44.1 k -> 16 k, P = 160: G = 1.)"""
+    best, best_g = -1.0, 1
+    for g in range(1, MAX_GROUP + 1):
+        share = (g * P) / (64.0 * math.ceil(g * P / 64.0)) * Kw / (Kw + (g - 1) * S)
+        if share > best * (1 + 1e-12):
+            best, best_g = share, g
+    return best_g
+
+
+def window_matrix(bank: np.ndarray, S: int, G: int) -> np.ndarray:
+    """bank (P, Kw): out[m P + p] = sum_k x[m S + k] bank[p, k].  Returns the block-Toeplitz matrix B' of shape
+    (Kw + (G - 1) S, G P) that computes G consecutive frames at once:  out[(m' G + g) P + p] = sum_k x[m' G S + k] B'[k, g P + p],
+    B'[g S + k, g P + p] = bank[p, k] — the same sums in the same k order with zeros in between, so the result does not depend
+    on G beyond rounding (and not at all on exactly representable operands)."""
+    bank = np.asarray(bank)
+    if bank.ndim != 2 or S < 1 or G < 1:
+        raise ValueError("window_matrix: a (P, Kw) bank, S >= 1, G >= 1")
+    P, Kw = bank.shape
+    out = np.zeros((Kw + (G - 1) * S, G * P), dtype=bank.dtype)
+    for g in range(G):
+        out[g * S:g * S + Kw, g * P:(g + 1) * P] = bank.T
+    return out
+
+
+def _check_device(x: torch.Tensor, what: str) -> None:
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise L.SdaError(f"{what} needs device tensors (no CPU fallback)")
+    if not x.is_floating_point() or x.dim() < 1 or x.shape[-1] < 1:
+        raise L.SdaError(f"{what}: a floating-point tensor (..., L) with L >= 1")
+
+
+def window_gemm(x: torch.Tensor, B: torch.Tensor, frames: int, S: int) -> torch.Tensor:
+    """`sda_window_gemm_f32` on a contiguous fp32 (rows, Lx) device tensor and a (K, N) matrix: (rows, frames N).
+    Lx >= (frames - 1) S + K is the caller's to provide (the kernel refuses otherwise)."""
+    for t in (x, B):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous():
+            raise L.SdaError("window_gemm: contiguous fp32 2-D device tensors")
+    K, N = B.shape
+    out = torch.empty((x.shape[0], frames * N), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        L.check(L.load().sda_window_gemm_f32(x.data_ptr(), x.shape[1], x.shape[0], frames, S, K, B.data_ptr(), N, out.data_ptr(),
+                                             out.shape[1], torch.cuda.current_stream().cuda_stream), "window_gemm")
+    return out
+
+
+def _apply_bank(xp: torch.Tensor, bank: np.ndarray, S: int, n_frames: int) -> torch.Tensor:
+    """xp (rows, >= (n_frames - 1) S + Kw) fp32 on the device -> (rows, n_frames P): the bank over n_frames windows, grouped by
+    window_group's rule; the row is zero-extended to what the last (partly unused) group reads."""
+    P, Kw = bank.shape
+    G = window_group(P, S, Kw)
+    Bm = torch.from_numpy(window_matrix(bank, S, G).astype(np.float32)).to(xp.device)
+    groups = -(-n_frames // G)
+    need = (groups - 1) * G * S + Bm.shape[0]
+    if xp.shape[1] < need:
+        xp = torch.cat([xp, xp.new_zeros(xp.shape[0], need - xp.shape[1])], dim=1)
+    return window_gemm(xp.contiguous(), Bm, groups, G * S)[:, :n_frames * P]
+
+
+def fir_filter(x: torch.Tensor, taps) -> torch.Tensor:
+    """Zero-phase FIR filtering of the last axis, (..., L) -> fp32 (..., L): the "same" part of the convolution of each row with
+    `taps` (odd length K, so the delay (K - 1) / 2 is whole) after mne's "reflect_limited" padding — (K - 1) / 2 samples of odd
+    extension 2 x[0] - x[i] / 2 x[-1] - x[-1 - i] per side, zero-filled where the row is shorter than that.  What
+    `mne.filter.filter_data` does with its FIR ("overlap-add" there; the same sums)."""
+    h = np.asarray(taps, dtype=np.float64).reshape(-1)
+    K = h.size
+    if K % 2 == 0:
+        raise L.SdaError(f"fir_filter: {K} taps — only odd lengths have a whole-sample delay (zero phase)")
+    _check_device(x, "fir_filter")
+    n = x.shape[-1]
+    rows = x.reshape(-1, n).float()
+    pad = (K - 1) // 2
+    p = min(pad, n - 1)
+    z = rows.new_zeros(rows.shape[0], pad - p)
+    left = 2 * rows[:, :1] - rows[:, 1:p + 1].flip(-1)
+    right = 2 * rows[:, -1:] - rows[:, n - 1 - p:n - 1].flip(-1)
+    xp = torch.cat([z, left, rows, right, z], dim=1)                 # n + K - 1
+    y = _apply_bank(xp, h[::-1][None, :].copy(), 1, n)
+    return y.contiguous().reshape(x.shape)
+
+
+@lru_cache(maxsize=16)
+def _bandpass_taps(sfreq: float, l_freq: float, h_freq: float) -> np.ndarray:
+    if not (0 < l_freq < h_freq < sfreq / 2):
+        raise ValueError("bandpass_taps: 0 < l_freq < h_freq < sfreq / 2")
+    l_trans = min(max(0.25 * l_freq, 2.0), l_freq)
+    h_trans = min(max(0.25 * h_freq, 2.0), sfreq / 2.0 - h_freq)
+
+    def odd_len(trans):
+        n = int(math.ceil(3.3 * sfreq / trans))
+        return n + (n % 2 == 0)
+
+    def lowpass(cut, n):
+        """scipy.signal.firwin(n, cut, window="hamming", fs=sfreq): windowed sinc, unit gain at DC"""
+        t = np.arange(n, dtype=np.float64) - (n - 1) / 2
+        h = 2 * cut / sfreq * np.sinc(2 * cut / sfreq * t) * np.hamming(n)
+        return h / h.sum()
+
+    n_tot = odd_len(min(l_trans, h_trans))
+    h = np.zeros(n_tot, dtype=np.float64)
+    for sign, cut, trans in ((1.0, h_freq + h_trans / 2, h_trans), (-1.0, l_freq - l_trans / 2, l_trans)):
+        n = odd_len(trans)
+        off = (n_tot - n) // 2
+        h[off:off + n] += sign * lowpass(cut, n)
+    h.setflags(write=False)
+    return h
+
+
+def bandpass_taps(sfreq: float, l_freq: float, h_freq: float) -> np.ndarray:
+    """The band-pass `mne.filter.filter_data(..., l_freq, h_freq)` designs by default (method "fir", fir_design "firwin", Hamming
+    window, "auto" lengths), by mne's documented rule: transition widths l_trans = min(max(0.25 l, 2), l) and
+    h_trans = min(max(0.25 h, 2), sfreq / 2 - h); 3.3 sfreq / trans taps per edge, made odd; the filter is the centred difference
+    of the two Hamming-windowed-sinc low-passes cut at the transition midpoints (h + h_trans / 2, l - l_trans / 2), each of its
+    own length.  float64, odd length, symmetric.  (1000, 1, 60) -> 3301 taps.  Parity with mne's own array: unpinned (module
+    docstring)."""
+    return _bandpass_taps(float(sfreq), float(l_freq), float(h_freq))
+
+
+def filter_data(x: torch.Tensor, sfreq: float, l_freq: float, h_freq: float) -> torch.Tensor:
+    """`mne.filter.filter_data(x, sfreq, l_freq, h_freq)` with both edges given: bandpass_taps + fir_filter."""
+    return fir_filter(x, bandpass_taps(sfreq, l_freq, h_freq))
+
+
+@lru_cache(maxsize=16)
+def _sinc_bank(orig: int, new: int, lpw: int, rolloff: float):
+    base = min(orig, new) * rolloff
+    width = int(math.ceil(lpw * orig / base))
+    i = np.arange(-width, width + orig, dtype=np.float64)[None, :] / orig
+    ph = np.arange(0, -new, -1, dtype=np.float64)[:, None] / new
+    t = np.clip((ph + i) * base, -lpw, lpw)
+    bank = np.sinc(t) * np.cos(t * math.pi / lpw / 2) ** 2 * (base / orig)
+    bank.setflags(write=False)
+    return bank, width
+
+
+def sinc_resample_bank(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> Tuple[np.ndarray, int, int, int]:
+    """torchaudio's `sinc_interp_hann` resampling kernel in float64: (bank (new', Kw), width, orig', new') with the rates divided
+    by their gcd, base = min(orig', new') rolloff, width = ceil(lpw orig' / base), Kw = 2 width + orig', and
+    bank[p, i] = sinc(pi t) cos^2(pi t / (2 lpw)) base / orig' at t = (-p / new' + (i - width) / orig') base clamped to +-lpw."""
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    if orig_freq < 1 or new_freq < 1 or lowpass_filter_width < 1:
+        raise ValueError("sinc_resample_bank: positive integer rates and filter width")
+    g = math.gcd(orig_freq, new_freq)
+    orig, new = orig_freq // g, new_freq // g
+    bank, width = _sinc_bank(orig, new, int(lowpass_filter_width), float(rolloff))
+    return bank, width, orig, new
+
+
+def resample_audio(wave: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> torch.Tensor:
+    """`torchaudio.functional.resample(wave, orig_freq, new_freq, lowpass_filter_width, rolloff)` (sinc_interp_hann), (..., L) ->
+    fp32 (..., ceil(new' L / orig')): the row zero-padded by (width, width + orig'), the bank applied at stride orig'.  Equal
+    rates return the input.  Parity with torchaudio's own output: unpinned (module docstring)."""
+    _check_device(wave, "resample_audio")
+    if int(orig_freq) == int(new_freq):
+        return wave
+    bank, width, orig, new = sinc_resample_bank(orig_freq, new_freq, lowpass_filter_width, rolloff)
+    n = wave.shape[-1]
+    rows = wave.reshape(-1, n).float()
+    target = -(-new * n // orig)
+    n_frames = n // orig + 1
+    xp = torch.cat([rows.new_zeros(rows.shape[0], width), rows, rows.new_zeros(rows.shape[0], width + orig)], dim=1)
+    y = _apply_bank(xp, bank, orig, n_frames)[:, :target]
+    return y.contiguous().reshape(wave.shape[:-1] + (target,))
+
+
+def brain_preproc(raw: torch.Tensor, orig_rate: float, preprocs) -> torch.Tensor:
+    """Raw recording (C, L) at orig_rate -> fp32 (C, round(L brain_resample_rate / orig_rate)): the band-pass
+    preprocs["brain_filter_low"] ... ["brain_filter_high"], then FFT resampling to preprocs["brain_resample_rate"]
+    (gwilliams2022.py:253-260, brennan2018.py:263-272)."""
+    filtered = filter_data(raw, orig_rate, preprocs["brain_filter_low"], preprocs["brain_filter_high"])
+    return resample_fft(filtered, up=preprocs["brain_resample_rate"] / orig_rate).float()
+
+
+def speech_embeddings(embedder, wave: torch.Tensor, sample_rate: int, preprocs, audio_resample_rate: int = 16000) -> torch.Tensor:
+    """One audio file (1, L) at sample_rate -> float64 (features, frames at brain_resample_rate), gwilliams2022.py:346-373:
+    resample to 16 kHz (preprocs["lowpass_filter_width"]), embed with `embedder` (a Wav2Vec2Embedder: the mean of the last four
+    hidden states, or the feature encoder's output when preprocs["last4layers"] is false), FFT-resample from the embedder's
+    frame rate to preprocs["brain_resample_rate"]."""
+    _check_device(wave, "speech_embeddings")
+    if wave.dim() != 2 or wave.shape[0] != 1:
+        raise L.SdaError("speech_embeddings: a (1, L) waveform")
+    wave16 = resample_audio(wave, sample_rate, audio_resample_rate, lowpass_filter_width=int(preprocs["lowpass_filter_width"]))
+    if preprocs["last4layers"]:
+        emb = embedder.embed(wave16)                                 # (H, frames)
+    else:
+        # the embedder keeps copies of its stages on request; the last feature-encoder layer is `feature_extractor`'s output
+        taps, embedder.taps = embedder.taps, {}
+        try:
+            embedder.hidden_states(wave16[0])
+            emb = embedder.taps[f"feat{len(embedder.cfg.conv_kernel) - 1}"].t()      # (C, frames)
+        finally:
+            embedder.taps = taps
+    rate_after = audio_resample_rate * emb.shape[-1] / wave16.shape[-1]
+    return resample_fft(emb, up=preprocs["brain_resample_rate"] / rate_after)

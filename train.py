@@ -16,8 +16,9 @@ What is kept from the reference loop (train.py:148-259):
   * the per-epoch print line and the optional W&B scalar names; `model_last.pt` = encoder.state_dict().
 `data=continuous` (with dataset=Brennan2018) runs that dataset's own input path on the GPU: whole-recording robust scaling
 (preprocs.subject_wise), clamp, segment gather with baseline correction (speech_decoding_amd.data.ResidentSubjectFeed).
-What is not: the M/EEG + wav2vec2 dataset classes (out of scope, they need MNE, the raw recordings and
-un-downloadable weights).  `--data synthetic` (default) builds a seeded stand-in with the same tensor
+What is not: the M/EEG + wav2vec2 dataset classes (they need the raw recordings and un-downloadable weights; their
+signal conditioning — band-pass, audio and FFT resampling — is built as speech_decoding_amd.signal_prep, but this
+script does not read raw files).  `--data synthetic` (default) builds a seeded stand-in with the same tensor
 shapes; a real dataset object can be passed to `run()` as (train_batches, test_batch) callables.
 """
 from __future__ import annotations
