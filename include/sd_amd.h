@@ -42,7 +42,7 @@ extern "C" {
 
 enum { SDA_F32 = 0, SDA_BF16 = 1, SDA_F16 = 2 };   /* storage + MFMA operand type; accumulation is always fp32 */
 
-/* conv_gemm epilogue flags */
+/* conv_gemm epilogue flags.  sda_conv_gemm refuses a `flags` word with any bit that is not named here. */
 enum { SDA_EPI_GELU = 1,
        SDA_EPI_GLU_BWD = 4,         /* the conv's output is the gradient dy entering an F.glu whose forward kept (out, gate) (SDA_EPI_GLU):
                                        y [rows][2 * Cout_p] = [dy * sig(gate) | dy * out * (1 - sig(gate))] (the GLU backward, written
@@ -61,6 +61,10 @@ enum { SDA_EPI_GELU = 1,
                                        Cout_p % 160 == 0 or Cout_p % 128 == 0, shared weights, no residual / statistics:
                                        the same tiling (conv1_flat.hip); other shapes ignore the flag.  `stats` then has
                                        sda_conv_stats_rows(...) rows instead of B * n_t_tiles */
+       SDA_CONV_FLAT_STAGGER = 1024,/* with SDA_CONV_FLAT_TILES, kernel size 3 (conv3_flat.hip): the second workgroup of a CU takes its
+                                       128-row tile(s) first and its 256-row tiles after them, the first workgroup the other way
+                                       round, so that the two reach their epilogues at different times.  Same results either way;
+                                       every other kernel ignores the flag */
        SDA_CONV_WIDE_TILES = 524288,/* kernel size 1, 16-bit storage, Cout_p % 256 == 0 or % 320 == 0, shared weights, no residual: 256-row x
                                        256- / 320-channel tiles of the flat row space, eight waves, one persistent workgroup per CU
                                        (conv1_wide.hip); takes SDA_EPI_GELU (+ y_pre), SDA_EPI_GELU_BWD (`stats` = one row per 256-row

@@ -102,7 +102,7 @@ __device__ __forceinline__ void flat1_tile(const sda_conv_args& a, unsigned char
     }
   });
   uint32_t kvoff = voff0;                            // per-lane offset incl. the channel offset of the slab being issued
-  const int nslab = (a.flags & 512) ? 1 : c.nslab;   // flag 512 (diagnostic): one K-step only — the epilogue's time (results are garbage)
+  const int nslab = c.nslab;
   // ---- prologue: slabs 0 and 1 into stages 0 and 1
   static_for<0, NPW>([&](auto ic) { lds_dma16_lean<true>(pbase[decltype(ic)::value], kvoff, lds_base + pdst[decltype(ic)::value]); });
   if (nslab > 1) {
@@ -111,7 +111,6 @@ __device__ __forceinline__ void flat1_tile(const sda_conv_args& a, unsigned char
   }
   const int wrow = wave_n * (P::CO / 2) + lr;
   const int xrow0 = wave_m * (R / 2) + lr;
-  const bool no_dma = a.flags & 128;                 // (diagnostic: no LDS-DMA inside the K loop — garbage results)
   uint32_t rd = 0;                                   // byte offset of the stage K-step s reads
   // One K-step.  MODE 0: issues slab s + 2; 1: the last but one (nothing left to issue); 2: the last (waits for everything).
   auto kstep = [&](auto modec) {
@@ -134,11 +133,9 @@ __device__ __forceinline__ void flat1_tile(const sda_conv_args& a, unsigned char
       mma16_row<E, NREP>(af, bf, acc[m]);
       // the DMA pieces go BETWEEN the MFMA rows: the wave's issue slot is free while the matrix pipe works through the MFMAs queued before it
       if constexpr (MODE == 0) {
-        if (!no_dma) {
-          static_for<m * PER, ((m + 1) * PER < NPW ? (m + 1) * PER : NPW)>([&](auto ic) {
-            lds_dma16_lean<false>(pbase[decltype(ic)::value], kvoff, wr + pdst[decltype(ic)::value]);
-          });
-        }
+        static_for<m * PER, ((m + 1) * PER < NPW ? (m + 1) * PER : NPW)>([&](auto ic) {
+          lds_dma16_lean<false>(pbase[decltype(ic)::value], kvoff, wr + pdst[decltype(ic)::value]);
+        });
       }
       af = af_next;
     });
@@ -147,7 +144,7 @@ __device__ __forceinline__ void flat1_tile(const sda_conv_args& a, unsigned char
   // The K loop runs at raised priority: a SIMD issues MFMA and ordinary vector instructions through one port, oldest wave
   // first — beside an OLDER workgroup's epilogue (a dense stream of vector instructions, GELU) a younger one's MFMAs would
   // only get the slots that stream leaves; an MFMA takes the port for one pass in four, so the epilogue loses little.
-  if (!(a.flags & 2048)) __builtin_amdgcn_s_setprio(2);
+  __builtin_amdgcn_s_setprio(2);
   {
     int s = 0;
     for (; s + 2 < nslab; ++s) kstep(std::integral_constant<int, 0>{});
@@ -161,16 +158,6 @@ __device__ __forceinline__ void flat1_tile(const sda_conv_args& a, unsigned char
   asm volatile("" : "+v"(tid_e));
   const int tid = tid_e, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), wave_m = wid >> 1, wave_n = wid & 1;
   const int lr = lane & 15, lq = lane >> 4;
-  if (a.flags & 256) {        // diagnostic: skip the epilogue, keep the accumulators live
-    float keep = 0.f;
-#pragma unroll
-    for (int m = 0; m < MREP; ++m)
-#pragma unroll
-      for (int n = 0; n < NREP; ++n) keep += acc[m][n][0] + acc[m][n][1] + acc[m][n][2] + acc[m][n][3];
-    if (keep == 123.456f) reinterpret_cast<float*>(a.y)[0] = keep;
-    __syncthreads();
-    return;
-  }
   if (a.bias) {
 #pragma unroll
     for (int n = 0; n < NREP; ++n) {
@@ -188,8 +175,7 @@ __device__ __forceinline__ void flat1_tile(const sda_conv_args& a, unsigned char
   E* __restrict__ yg = reinterpret_cast<E*>(a.y);
   E* __restrict__ ypre = reinterpret_cast<E*>(a.y_pre);
   const E* __restrict__ ug = reinterpret_cast<const E*>(a.bn_x);
-  const bool gelu = (a.flags & SDA_EPI_GELU) && !(a.flags & 16);    // flags 16 / 8 (diagnostic): no GELU arithmetic / no stores
-  const bool no_store = a.flags & 8;
+  const bool gelu = a.flags & SDA_EPI_GELU;
   float ssum[GB ? CH : 1];
 #pragma unroll
   for (int j = 0; j < (GB ? CH : 1); ++j) ssum[j] = 0.f;
@@ -215,8 +201,7 @@ __device__ __forceinline__ void flat1_tile(const sda_conv_args& a, unsigned char
     __syncthreads();
     // this thread's rows of the slice (the pre-activation rows of SDA_EPI_GELU_BWD are fetched one row ahead, packed; the
     // accumulators of the later slices are still live here: no register may spill)
-    const long row_mask = (a.flags & 32) ? 1023L : ~0L;   // (diagnostic: every store lands in the first 1024 rows — no HBM write traffic)
-    auto row_off = [&](int it) { return (size_t)((f0 + q * G_EP_ROWS + rg + it * G::RG) & row_mask) * a.Cout_p + co0 + chunk * CH; };
+    auto row_off = [&](int it) { return (size_t)(f0 + q * G_EP_ROWS + rg + it * G::RG) * a.Cout_p + co0 + chunk * CH; };
     int p = pq;
     auto row_ok = [&](int it, int pp) {
       const int row = rg + it * G::RG;
@@ -254,15 +239,14 @@ __device__ __forceinline__ void flat1_tile(const sda_conv_args& a, unsigned char
             ssum[j] += o.x; ssum[j + 1] += o.y;
           }
         } else if (gelu) {
-          if (ypre && !no_store) Vec16<E>::store(ypre + row_off(it), v);
+          if (ypre) Vec16<E>::store(ypre + row_off(it), v);
 #pragma unroll
           for (int j = 0; j < CH; j += 2) {
             const f32x2 gp = gelu_pair<E>(f32x2{v[j], v[j + 1]});
             v[j] = gp.x; v[j + 1] = gp.y;
           }
         }
-        if (!no_store) Vec16<E>::store(yg + row_off(it), v);
-        else if (v[0] == 123.456f) Vec16<E>::store(yg + row_off(it), v);
+        Vec16<E>::store(yg + row_off(it), v);
         if constexpr (RSQ) {
 #pragma unroll
           for (int j = 0; j < CH; ++j) { const float qv = Vec16<E>::round(v[j]); sq = fmaf(qv, qv, sq); }
@@ -334,17 +318,11 @@ __global__ __launch_bounds__(256, 2) void conv1_flat_kernel(const sda_conv_args 
   c.co0 = co_tile * P::CO;
   int u = run * units_per_wg;                               // this workgroup's 128-row units: [u, u_end)
   const int u_end = min(n_units, u + units_per_wg);
-  // the two workgroups of a CU (observed: blocks i and i + 8 * 32 of an XCD) may take their tiles in opposite order, so that
-  // their epilogues fall at different times (conv3_flat.hip; flag 1024)
-  const bool second = ((blockIdx.x >> 3) >> 5) & 1;
-  const bool small_first = second && (a.flags & 1024);     // (measured alone: the same order is 3-8 % faster here; flag 1024 staggers)
+  // both workgroups of a CU take their tiles in the same order, 256-row tiles first (measured alone: conv3_flat's staggered
+  // order, SDA_CONV_FLAT_STAGGER, is 3-8 % slower here)
   const int n = u_end - u;
   if (n <= 0) return;
-  int lead, tail, pairs;
-  if (n & 1) { pairs = n >> 1; lead = small_first ? 1 : 0; tail = 1 - lead; }
-  else if (small_first && n >= 2) { pairs = (n >> 1) - 1; lead = 1; tail = 1; }
-  else { pairs = n >> 1; lead = 0; tail = 0; }
-  if (lead) { flat1_tile<E, NREP, 4, GB, RSQ>(a, smem, c, (long)u * G_UNIT, u); ++u; }
+  const int pairs = n >> 1, tail = n & 1;
   for (int p = 0; p < pairs; ++p, u += 2) flat1_tile<E, NREP, 8, GB, RSQ>(a, smem, c, (long)u * G_UNIT, u);
   if (tail) flat1_tile<E, NREP, 4, GB, RSQ>(a, smem, c, (long)u * G_UNIT, u);
 }

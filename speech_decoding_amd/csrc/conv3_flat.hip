@@ -85,19 +85,6 @@ template <int MREP> struct FSched {
   static constexpr int WAITP = G1 + G2;
 };
 
-// MFMA "weights" fragment of a 16-column identity block: B[col][k] = 1 where k == 16 * half + col, as mma16<E> reads
-// it (lane (lr = col, lq) holds k = 8 lq + j in element j; fp32: k = 4 lq + j, one 16-wide block per slab, half = 0).
-template <typename E> __device__ inline uint4 ident_frag(int half, int lr, int lq) {
-  uint32_t w[4] = {0u, 0u, 0u, 0u};
-  if constexpr (sizeof(E) == 4) {
-    if (lq == (lr >> 2)) w[lr & 3] = 0x3F800000u;
-  } else {
-    const uint32_t one = std::is_same<E, half_t>::value ? 0x3C00u : 0x3F80u;
-    if (lq == 2 * half + (lr >> 3)) w[(lr & 7) >> 1] = one << (16 * (lr & 1));
-  }
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 struct FTileCtx {            // per-workgroup constants shared by all its tiles
   int tid, lane, wid, wave_m, wave_n, lr, lq, prow, pchunk, co0, nslab, Tp;
   long total_rows;
@@ -110,18 +97,14 @@ struct FTileCtx {            // per-workgroup constants shared by all its tiles
 // the epilogue leaves free, issued one barrier ahead of its use — no registers (the accumulators of the later slices are
 // live and a spilled register's reload waits for every store in flight), 1 KB per request instead of 16 B per lane.
 // fp32 (a slice would be 40 KB): per-thread 16-byte loads, one row ahead.
-// STAMP (diagnostic build, never the product path): s_memtime stamps split every tap phase of the K loop into
-// [barrier exit -> operands in registers] [MFMA + DMA issue] [vmcnt wait] [barrier]; the four cycle sums of wave 0 go to
-// st[0..3] (+ the phase count in st[4]).  Shares are meaningful, the run time of this build is not.
-template <typename E, bool BN, int MREP, bool RESX, int DIAG = 0, bool GLU = false>
+template <typename E, bool BN, int MREP, bool RESX, bool GLU = false>
 __device__ __forceinline__ void flat_tile(const sda_conv_args& a, unsigned char* smem, const FTileCtx& c, const long f0,
-                                          const int stat_row, unsigned long long* st = nullptr) {
+                                          const int stat_row) {
   constexpr int SLAB = ROW_B / (int)sizeof(E);
   constexpr int PER16 = Elem<E>::PER16;
   constexpr int CH = Vec16<E>::N;
   using G = FEpi<CH>;
   using S = FSched<MREP>;
-  constexpr bool STAMP = DIAG == 1;          // DIAG (diagnostic builds): 1 stamps, 2 no LDS-DMA inside the K loop, 3 no LDS-DMA and no fragment reads either
   constexpr int R = S::R;
   const int co0 = c.co0, dil = a.dil, Tp = c.Tp;
   const long lds_row0 = f0 - dil;                            // buffer row of LDS input row 0
@@ -199,7 +182,7 @@ __device__ __forceinline__ void flat_tile(const sda_conv_args& a, unsigned char*
     else lds_dma16_lean<PD>(pbase[i], kvoff, xdst + (uint32_t)cx);
   };
 
-  const int nslab = (a.flags & 512) ? 1 : c.nslab;          // flag 512 (diagnostic): one K-step only — the epilogue's time (results are garbage)
+  const int nslab = c.nslab;
   // ---- tile prologue: tap 0 of K-step 0, then the stream of "K-step -1" (x(0), taps 1 and 2 of K-step 0, tap 0 of K-step 1)
   {
     const uint32_t w00 = lds_base + 2 * F_XB;              // slot (3 * 0 + 0) & 3
@@ -213,14 +196,6 @@ __device__ __forceinline__ void flat_tile(const sda_conv_args& a, unsigned char*
   static_for<0, S::NP>([&](auto ic) { issue(ic, TrueC{}); });
   wait_vmcnt_lit<S::WAITP>();
   __builtin_amdgcn_s_barrier();
-  unsigned long long tA = 0, tB = 0, tC = 0, tD = 0, sAB = 0, sBC = 0, sCD = 0, sDA = 0, nph = 0;
-  auto now = [&]() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-  };
   // operands of phase (0, 0): the wave's five weight fragments and its first input fragment
   const int wrow = wave_n * (F_CO / 2) + lr;
   const int xrow0 = wave_m * (R / 2) + lr;
@@ -249,9 +224,7 @@ __device__ __forceinline__ void flat_tile(const sda_conv_args& a, unsigned char*
       else if (tap == 0) wait_vmcnt_lit<S::WAIT0>();
       else if (tap == 1) wait_vmcnt_lit<S::WAIT1>();
       else wait_vmcnt_lit<S::WAIT2>();
-      if constexpr (STAMP) { tD = now(); if (nph) sCD += tD - tC; }
       __builtin_amdgcn_s_barrier();                          // ... for every wave
-      if constexpr (STAMP) { tA = now(); if (nph) sDA += tA - tD; tB = tA; }
       const int xrow = xrow0 + tap * dil;
       // next phase: (s, tap + 1) or (s + 1, 0)
       const bool last_phase = MODE == 2 && tap == 2;
@@ -260,13 +233,12 @@ __device__ __forceinline__ void flat_tile(const sda_conv_args& a, unsigned char*
       static_for<0, MREP>([&](auto mc) {
         constexpr int m = decltype(mc)::value;
         uint4 af_next = af;
-        if constexpr (DIAG == 3) { asm volatile("" : "+v"(af_next.x)); }
-        else if constexpr (m + 1 < MREP) af_next = *reinterpret_cast<const uint4*>(xs + lds_sw64(xrow + (m + 1) * 16, lq));
+        if constexpr (m + 1 < MREP) af_next = *reinterpret_cast<const uint4*>(xs + lds_sw64(xrow + (m + 1) * 16, lq));
         else { if (!last_phase) af_next = *reinterpret_cast<const uint4*>(xs_n + lds_sw64(xrow_n, lq)); }
         mma16_row<E, F_NREP>(af, bf, acc[m]);
         // this phase's DMA pieces go BETWEEN the MFMA rows (the wave's issue slot is free while the matrix pipe works
         // through the MFMAs queued before it)
-        if constexpr (MODE < 2 && DIAG < 2) {
+        if constexpr (MODE < 2) {
           if (tap == 0) { if constexpr (m < S::G0) issue(std::integral_constant<int, m>{}, FalseC{}); }
           else if (tap == 1) { if constexpr (m < S::G1) issue(std::integral_constant<int, S::G0 + m>{}, FalseC{}); }
           else { if constexpr (m < S::G2) issue(std::integral_constant<int, S::G0 + S::G1 + m>{}, FalseC{}); }
@@ -277,8 +249,7 @@ __device__ __forceinline__ void flat_tile(const sda_conv_args& a, unsigned char*
       // (behind a scheduling fence: the fragments go into the registers the last MFMA row has just read — without it hipcc
       // overlaps the two sets, 20 registers the kernel does not have)
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (DIAG != 3) { if (!last_phase) load_b((3 * s + tap + 1) & 3); }
-      if constexpr (STAMP) { tC = now(); sBC += tC - tB; ++nph; }
+      if (!last_phase) load_b((3 * s + tap + 1) & 3);
     }
   };
   {
@@ -286,10 +257,6 @@ __device__ __forceinline__ void flat_tile(const sda_conv_args& a, unsigned char*
     for (; s + 1 < nslab; ++s) kstep(s, std::integral_constant<int, 0>{});
     kstep(s, std::integral_constant<int, 2>{});
   }
-  if constexpr (STAMP) {
-    if (st && c.tid == 0) { st[0] += sAB; st[1] += sBC; st[2] += sCD; st[3] += sDA; st[4] += nph; }
-  }
-
   }   // ==== end of the K loop's scope
   // ------------------------------------------------------------------ epilogue
   // Every per-thread value of the epilogue is derived HERE from a thread index hipcc cannot see through: otherwise it
@@ -301,16 +268,6 @@ __device__ __forceinline__ void flat_tile(const sda_conv_args& a, unsigned char*
   const int tid = tid_e, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), wave_m = wid >> 1, wave_n = wid & 1;
   const int lr = lane & 15, lq = lane >> 4, e_prow = lane >> 2, e_pchunk = lane & 3;
   const uint32_t lds_base = __builtin_amdgcn_readfirstlane(lds_addr(smem));
-  if (a.flags & 256) {        // diagnostic: skip the epilogue, keep the accumulators live
-    float keep = 0.f;
-#pragma unroll
-    for (int m = 0; m < MREP; ++m)
-#pragma unroll
-      for (int n = 0; n < F_NREP; ++n) keep += acc[m][n][0] + acc[m][n][1] + acc[m][n][2] + acc[m][n][3];
-    if (keep == 123.456f) reinterpret_cast<float*>(a.y)[0] = keep;
-    __syncthreads();
-    return;
-  }
   if (a.bias) {
 #pragma unroll
     for (int n = 0; n < F_NREP; ++n) {
@@ -510,7 +467,7 @@ __device__ __forceinline__ void flat_tile(const sda_conv_args& a, unsigned char*
   __syncthreads();            // the next tile's LDS-DMA overwrites the staging / reduction area
 }
 
-template <typename E, bool BN, bool RESX, int DIAG = 0, bool GLU = false>
+template <typename E, bool BN, bool RESX, bool GLU = false>
 __global__ __launch_bounds__(256, 2) void conv3_flat_kernel(const sda_conv_args a, const int n_units, const int units_per_wg,
                                                             const int runs_per_co, const long total_rows, const int Tp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -548,20 +505,18 @@ __global__ __launch_bounds__(256, 2) void conv3_flat_kernel(const sda_conv_args 
   int u = run * units_per_wg;                               // this workgroup's 128-row units: [u, u_end)
   const int u_end = min(n_units, u + units_per_wg);
   // The dispatcher fills an XCD's 32 CUs once before it gives any of them a second workgroup, so workgroups
-  // (blockIdx / 8) 0..31 and 32..63 of an XCD are the co-resident pairs (verified with tools/flat_timeline.py; not
-  // guaranteed, it only matters for speed).  With flag 1024 the second of a pair takes its 128-row tile(s) FIRST, the
-  // first one LAST, so that their epilogues fall at different times; measured: no gain, default off.
-  // flags 1024 / 2048 (diagnostic): a different tile order (128-row tile first) for the second workgroup of every CU / for
-  // every other CU — spreads the epilogues (HBM bursts) over more distinct moments
-  const bool small_first = ((((blockIdx.x >> 3) >> 5) & 1) && (a.flags & 1024)) || (((blockIdx.x >> 3) & 1) && (a.flags & 2048));
+  // (blockIdx / 8) 0..31 and 32..63 of an XCD are the co-resident pairs (observed on a per-workgroup timeline, LABNOTES.md;
+  // not guaranteed, it only matters for speed).  With SDA_CONV_FLAT_STAGGER the second of a pair takes its 128-row tile(s)
+  // FIRST, the first one LAST, so that their epilogues (HBM bursts) fall at different times.
+  const bool second = ((blockIdx.x >> 3) >> 5) & 1;
+  const bool small_first = second && (a.flags & SDA_CONV_FLAT_STAGGER);
   // The two workgroups of a CU share each SIMD's matrix pipe and issue slots, arbitrated by priority, then AGE: at equal
   // priority the first-dispatched one wins every time — it runs its three units in 42 us and the second one in 54 us, the
-  // last 11 us alone on the CU at a single workgroup's (poor) rate (tools/flat_timeline.py).  So the second
-  // workgroup of each pair holds priority 1 for its FIRST tile and drops it afterwards: each is the winner for about half
-  // of its work and both finish together.  Which workgroups share a CU is the dispatcher's business (observed: blocks i and
-  // i + 8 * 32 of an XCD) — a wrong guess costs speed only.
-  const bool younger = (((blockIdx.x >> 3) >> 5) & 1) && !(a.flags & 64);              // flag 64 (diagnostic): no priority hand-over
-  if (younger) __builtin_amdgcn_s_setprio(1);
+  // last 11 us alone on the CU at a single workgroup's (poor) rate.  So the second workgroup of each pair
+  // holds priority 1 for its FIRST tile and drops it afterwards: each is the winner for about half of its work and both
+  // finish together.  Which workgroups share a CU is the dispatcher's business (observed: blocks i and i + 8 * 32 of an
+  // XCD) — a wrong guess costs speed only.
+  if (second) __builtin_amdgcn_s_setprio(1);
   int n = u_end - u;
   if (n <= 0) return;
   // tile plan: `pairs` 256-row tiles and `lead` + `tail` 128-row tiles around them
@@ -569,39 +524,16 @@ __global__ __launch_bounds__(256, 2) void conv3_flat_kernel(const sda_conv_args 
   if (n & 1) { pairs = n >> 1; lead = small_first ? 1 : 0; tail = 1 - lead; }
   else if (small_first && n >= 2) { pairs = (n >> 1) - 1; lead = 1; tail = 1; }
   else { pairs = n >> 1; lead = 0; tail = 0; }
-  // diagnostic (flag 32, `partial` = a buffer of 16 x 8 bytes per workgroup that nothing else reads): wall-clock stamps
-  // (100 MHz) at the start and after every tile, plus where the workgroup ran — the timeline behind DESIGN.md's numbers
-  unsigned long long* dbg = (a.flags & 32) && a.partial ? reinterpret_cast<unsigned long long*>(a.partial) + (size_t)blockIdx.x * 32 : nullptr;
-  int nstamp = 0;
-  auto stamp = [&]() {
-    if (dbg && c.tid == 0 && nstamp < 5) {
-      dbg[4 + nstamp] = __builtin_amdgcn_s_memrealtime();
-      dbg[10 + nstamp] = __builtin_amdgcn_s_memtime();       // shader clock: cycles / 10 ns = the clock the chip holds
-    }
-    ++nstamp;
-  };
-  if (dbg && c.tid == 0) {
-    dbg[0] = __builtin_amdgcn_s_getreg((31 << 11) | 4);      // HW_REG_HW_ID: wave / SIMD / CU / SH / SE
-    dbg[1] = __builtin_amdgcn_s_getreg((31 << 11) | 20);     // HW_REG_XCC_ID
-    dbg[2] = (unsigned long long)lead | ((unsigned long long)pairs << 8) | ((unsigned long long)tail << 16);
-    dbg[3] = (unsigned long long)u;
-  }
-  stamp();
-  if constexpr (DIAG == 1) {       // only 256-row tiles are stamped; sums land behind the wall-clock stamps of this workgroup
-    if (dbg && c.tid == 0) { for (int i = 0; i < 5; ++i) dbg[16 + i] = 0; }
-    for (int p = 0; p < pairs; ++p, u += 2) { flat_tile<E, BN, 8, RESX, 1>(a, smem, c, (long)u * F_UNIT, u, dbg ? dbg + 16 : nullptr); stamp(); }
-    return;
-  }
   if constexpr (sizeof(E) == 4) {
     // fp32 storage (the exact path): 128-row tiles only — 64 x 80 per wave, 80 accumulator registers.  The 256-row tile's 160
     // accumulators leave the fp32 instantiation (16-deep K-steps: twice the fragment traffic per MFMA row, 40-KB epilogue
     // slices read per thread) some 300 registers short, spilled inside the K loop.
-    for (; u < u_end; ++u) { flat_tile<E, BN, 4, RESX, 0, GLU>(a, smem, c, (long)u * F_UNIT, u); __builtin_amdgcn_s_setprio(0); }
+    for (; u < u_end; ++u) { flat_tile<E, BN, 4, RESX, GLU>(a, smem, c, (long)u * F_UNIT, u); __builtin_amdgcn_s_setprio(0); }
     return;
   }
-  if (lead) { flat_tile<E, BN, 4, RESX, (DIAG > 1 ? DIAG : 0), GLU>(a, smem, c, (long)u * F_UNIT, u); ++u; stamp(); __builtin_amdgcn_s_setprio(0); }
-  for (int p = 0; p < pairs; ++p, u += 2) { flat_tile<E, BN, 8, RESX, (DIAG > 1 ? DIAG : 0), GLU>(a, smem, c, (long)u * F_UNIT, u); stamp(); __builtin_amdgcn_s_setprio(0); }
-  if (tail) { flat_tile<E, BN, 4, RESX, (DIAG > 1 ? DIAG : 0), GLU>(a, smem, c, (long)u * F_UNIT, u); stamp(); }
+  if (lead) { flat_tile<E, BN, 4, RESX, GLU>(a, smem, c, (long)u * F_UNIT, u); ++u; __builtin_amdgcn_s_setprio(0); }
+  for (int p = 0; p < pairs; ++p, u += 2) { flat_tile<E, BN, 8, RESX, GLU>(a, smem, c, (long)u * F_UNIT, u); __builtin_amdgcn_s_setprio(0); }
+  if (tail) flat_tile<E, BN, 4, RESX, GLU>(a, smem, c, (long)u * F_UNIT, u);
 }
 
 struct FlatPlan { int n_units, units_per_wg, runs_per_co, grid; };
@@ -622,10 +554,10 @@ FlatPlan flat_plan(const sda_conv_args& a) {
   return p;
 }
 
-template <typename E, bool BN, bool RESX, int DIAG = 0, bool GLU = false>
+template <typename E, bool BN, bool RESX, bool GLU = false>
 int launch_flat(const sda_conv_args& a, hipStream_t st) {
   static unsigned long long attr_done = 0;        // per device
-  auto kern = conv3_flat_kernel<E, BN, RESX, DIAG, GLU>;
+  auto kern = conv3_flat_kernel<E, BN, RESX, GLU>;
   if (first_use_on_device(attr_done)) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS) != hipSuccess) {
       set_error("conv3_flat: cannot reserve %d bytes of LDS", F_LDS);
@@ -645,23 +577,19 @@ int conv3_flat_stat_rows(int B, int T) { return (int)(((long)B * rows_tp(T) + F_
 bool conv3_flat_supports(const sda_conv_args& a) {
   const bool glu = a.flags & SDA_EPI_GLU;
   if (glu ? (a.res || a.stats || a.bn_x) : a.y_pre != nullptr) return false;
-  return a.KS == 3 && a.Cout_p % F_CO == 0 && !a.widx && a.ksplit == 1 && (!a.partial || (a.flags & 32)) && !(a.flags & SDA_EPI_GELU) &&
+  return a.KS == 3 && a.Cout_p % F_CO == 0 && !a.widx && a.ksplit == 1 && !a.partial && !(a.flags & SDA_EPI_GELU) &&
          a.y && a.x_row0 == PAD && a.x_pitch == a.w_pitch && a.x_sample_rows == rows_tp(a.T) && (!a.bn_x || (a.bn_coef && a.stats)) &&
-
          a.x_rows_limit >= (long)a.B * rows_tp(a.T) + 3 * PAD && a.x_rows_limit < (1L << 31) && a.w_rows_limit >= a.Cout_p &&
          a.Cin_p / (ROW_B / (a.dtype == SDA_F32 ? 4 : 2)) >= 1;
 }
 
 template <typename E> static int launch_flat_e(const sda_conv_args& a, hipStream_t st) {
-  if (a.flags & SDA_EPI_GLU) return launch_flat<E, false, false, 0, true>(a, st);
+  if (a.flags & SDA_EPI_GLU) return launch_flat<E, false, false, true>(a, st);
   if (a.bn_x) return a.res ? launch_flat<E, true, true>(a, st) : launch_flat<E, true, false>(a, st);
   return a.res ? launch_flat<E, false, true>(a, st) : launch_flat<E, false, false>(a, st);
 }
 
 int launch_conv3_flat(const sda_conv_args& a, hipStream_t st) {
-  if ((a.flags & 128) && (a.flags & 32) && a.dtype == SDA_BF16 && !a.bn_x && !a.res) return launch_flat<uint16_t, false, false, 1>(a, st);   // diagnostic
-  if ((a.flags & 24) && a.dtype == SDA_BF16 && !a.bn_x && !a.res && !(a.flags & SDA_EPI_GLU))                                        // diagnostic (garbage results)
-    return (a.flags & 8) ? launch_flat<uint16_t, false, false, 3>(a, st) : launch_flat<uint16_t, false, false, 2>(a, st);
   if (a.dtype == SDA_F32) return launch_flat_e<float>(a, st);
   if (a.dtype == SDA_F16) return launch_flat_e<half_t>(a, st);
   return launch_flat_e<uint16_t>(a, st);

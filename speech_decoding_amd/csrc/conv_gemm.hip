@@ -35,28 +35,12 @@ template <int TILE_CO, int KS, int NT> constexpr int conv_stage_bytes() { return
 // (measured, config-2 shapes alone: the similarity matmul 203 -> 114 us at 256 x 256 samples, 710 -> 631 us at 2048 x 256;
 // the row-layout 1x1 convs, whose time is their epilogue's, gained nothing and lose co-residency: they keep two stages)
 template <int TILE_CO, int NT, int KS, bool SV> constexpr int conv_stages() {
-#ifdef SDA_RING_SV
-  return (NT == 2 && KS == 3) ? 3 : ((NT == 1 && KS == 1) ? (TILE_CO > 128 ? 3 : 4) : 2);
-#else
   return (NT == 2 && KS == 3) ? 3 : ((NT == 1 && KS == 1 && !SV) ? (TILE_CO > 128 ? 3 : 4) : 2);
-#endif
 }
 template <int TILE_CO, int KS, int NT, bool SV = true> constexpr int conv_lds_bytes() {
   constexpr int main_b = conv_stages<TILE_CO, NT, KS, SV>() * conv_stage_bytes<TILE_CO, KS, NT>();
   constexpr int epi_b = NT * (EpiGeom<TILE_CO, 8>::EP_BYTES + EpiGeom<TILE_CO, 8>::RED_BYTES);   // CH = 8 is the larger
   return main_b > epi_b ? main_b : epi_b;
-}
-
-typedef __attribute__((address_space(1))) const void gmem_cv;
-typedef __attribute__((address_space(3))) void lds_v;
-
-template <typename T> __device__ inline float4 round_like(float4 v);
-template <> __device__ inline float4 round_like<float>(float4 v) { return v; }
-template <> __device__ inline float4 round_like<half_t>(float4 v) {
-  return make_float4((float)(half_t)v.x, (float)(half_t)v.y, (float)(half_t)v.z, (float)(half_t)v.w);
-}
-template <> __device__ inline float4 round_like<uint16_t>(float4 v) {
-  return make_float4(bf2f(f2bf(v.x)), bf2f(f2bf(v.y)), bf2f(f2bf(v.z)), bf2f(f2bf(v.w)));
 }
 
 // NT = number of 128-row output tiles one workgroup computes SIDE BY SIDE against the same weight slab
@@ -136,7 +120,7 @@ __global__ __launch_bounds__(256 * NT, 2) void conv_gemm_kernel(const sda_conv_a
   const int nslab = a.Cin_p / SLAB;
   const int per_split = (nslab + a.ksplit - 1) / a.ksplit;
   const int s_begin = ks * per_split;
-  const int s_end = (a.flags & 512) ? s_begin : min(nslab, s_begin + per_split);
+  const int s_end = min(nslab, s_begin + per_split);
 
   // LDS-DMA pieces.  A piece is one wave-instruction: 64 lanes x 16 B land lane-linearly in LDS (16 rows x
   // 64 B), so the swizzle goes on the SOURCE chunk.  Rows outside the operand (only possible in split-K
@@ -234,11 +218,7 @@ __global__ __launch_bounds__(256 * NT, 2) void conv_gemm_kernel(const sda_conv_a
     }
   };
 
-#ifdef SDA_RING_SV
-  constexpr bool RING = KS == 1 && NT == 1;
-#else
   constexpr bool RING = KS == 1 && NT == 1 && !SV;
-#endif
   if constexpr (RING) {
     // Ring of NS stages, D = NS - 1 slabs of LDS-DMA in flight.  Every wave issues EXACTLY PPW pieces per slab (2 input + 2 or 3
     // weight pieces; indices past the end are clamped, duplicates rewrite identical bytes), so a counted s_waitcnt retires slab
@@ -428,15 +408,6 @@ __global__ __launch_bounds__(256 * NT, 2) void conv_gemm_kernel(const sda_conv_a
   }
 
   // ------------------------------------------------------------------ epilogue
-  if (a.flags & 256) {        // diagnostic: skip the epilogue, keep the accumulators live
-    float keep = 0.f;
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int n = 0; n < NREP; ++n) keep += acc[m][n][0] + acc[m][n][1] + acc[m][n][2] + acc[m][n][3];
-    if (keep == 123.456f) reinterpret_cast<float*>(a.y)[0] = keep;
-    return;
-  }
   if (a.bias) {
 #pragma unroll
     for (int n = 0; n < NREP; ++n) {
@@ -718,6 +689,10 @@ extern "C" int sda_conv_n_t_tiles(int T) { return (T + TILE_T - 1) / TILE_T; }
 
 extern "C" int sda_conv_gemm(const sda_conv_args* a, void* stream) {
   if (!a || !a->x || !a->w || (!a->y && !a->partial)) { set_error("conv_gemm: null argument"); return -1; }
+  constexpr int KNOWN_FLAGS = SDA_EPI_GELU | SDA_EPI_GLU | SDA_EPI_GLU_BWD | SDA_EPI_GELU_BWD | SDA_EPI_ROW_SUMSQ | SDA_EPI_BN_STORE_DG |
+                              SDA_CONV_SINGLE_TILE | SDA_CONV_PAIR_TILES | SDA_CONV_FLAT_TILES | SDA_CONV_FLAT_STAGGER |
+                              SDA_CONV_ONE_PER_CU | SDA_CONV_WIDE_TILES | SDA_CONV_WAVE_PRIO;
+  if (a->flags & ~KNOWN_FLAGS) { set_error("conv_gemm: unknown flag bits 0x%x", (unsigned)(a->flags & ~KNOWN_FLAGS)); return -1; }
   if (a->KS != 1 && a->KS != 3) { set_error("conv_gemm: kernel size %d not supported (1 or 3)", a->KS); return -1; }
   if (a->dil < 0 || a->dil > PAD) { set_error("conv_gemm: dilation %d outside [0, %d]", a->dil, PAD); return -1; }
   if (a->Cout_p % 64 || a->Cin_p % 64) { set_error("conv_gemm: channel extents (%d, %d) must be multiples of 64", a->Cin_p, a->Cout_p); return -1; }

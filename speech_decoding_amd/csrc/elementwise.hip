@@ -19,13 +19,8 @@ namespace sda {
 // column sums and the small reductions behind them): they run beside the weight-gradient GEMMs of the other stream, and at
 // s_setprio 3 their loads and stores win the SIMD's issue arbitration against those waves.  Round 5, six alternations on
 // one box (ms per step): off 6.771, on 6.777; with the data-gradient convs' waves raised as well (SDA_CONV_WAVE_PRIO) 6.725
-// against 6.754 for those alone — the pair is worth 0.05 ms, either one alone nothing.  -DSDA_EW_BWD_PRIO=0 turns it off.
-#ifndef SDA_EW_BWD_PRIO
-#define SDA_EW_BWD_PRIO 3
-#endif
-__device__ __forceinline__ void ew_bwd_prio() {
-  if constexpr (SDA_EW_BWD_PRIO > 0) __builtin_amdgcn_s_setprio(SDA_EW_BWD_PRIO);
-}
+// against 6.754 for those alone — the pair is worth 0.05 ms, either one alone nothing.
+__device__ __forceinline__ void ew_bwd_prio() { __builtin_amdgcn_s_setprio(3); }
 
 struct RowWalk {
   int r, r1, step, T, b, t;

@@ -159,11 +159,6 @@ template <> struct Vec16<half_t> {
   __device__ static uint4 load_raw(const half_t* p) { return *reinterpret_cast<const uint4*>(p); }
 };
 
-// Byte offset of 16-byte chunk `chunk` (0..7) of 128-byte LDS row `row`, XOR-swizzled so that 16
-// lanes reading the same chunk of 16 consecutive rows (the MFMA operand pattern) hit 16 distinct
-// 16-byte slots of the 256-byte bank row.
-__device__ inline int lds_sw(int row, int chunk) { return row * 128 + (((chunk ^ (row >> 1)) & 7) << 4); }
-
 // One 64-byte K-step (4 lane groups x 16 bytes) of MFMA work on a 16x16 output tile.
 // bf16: one v_mfma_f32_16x16x32_bf16.  fp32: four v_mfma_f32_16x16x4_f32; lane group g supplies
 // k = 4g + j at step j for BOTH operands, so the contraction covers the same 16 k values.
@@ -255,10 +250,6 @@ __device__ inline f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_eleme
 __device__ inline f32x2 splat2(float v) { return f32x2{v, v}; }
 // tail = 0.5*erfc(|x|/sqrt2) = 1 - Phi(|x|),  e = exp(-x^2/2)
 __device__ inline void normal_tail2(f32x2 x, f32x2& tail, f32x2& e) {
-#ifdef SDA_FAKE_GELU          // diagnostic build (wrong results): what the step would cost if GELU / GELU' were free
-  tail = x * 0.01f; e = x * 0.02f;
-  return;
-#endif
   const f32x2 y = x * 0.849321800288f;                                // sqrt(log2(e)/2): exp(-x^2/2) = 2^-(y*y)
   const f32x2 yy = y * y;
   e = f32x2{__builtin_amdgcn_exp2f(-yy.x), __builtin_amdgcn_exp2f(-yy.y)};
@@ -339,18 +330,6 @@ __device__ inline void lds_dma16_sv(const void* sbase_in, uint32_t voff, uint32_
   const uint32_t sb_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sb64);
   const void* sbase = (const void*)(uintptr_t)(((uint64_t)sb_hi << 32) | (uint64_t)sb_lo);
   asm volatile("s_nop 4\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-// s_waitcnt vmcnt(n) for a wave-uniform runtime n (the immediate must be a literal); anything above the
-// table waits for everything, which is always safe.
-__device__ inline void wait_vmcnt_dyn(int n) {
-#define SDA_VMC(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-  switch (n) {
-    SDA_VMC(1) SDA_VMC(2) SDA_VMC(3) SDA_VMC(4) SDA_VMC(5) SDA_VMC(6) SDA_VMC(7) SDA_VMC(8) SDA_VMC(9) SDA_VMC(10)
-    SDA_VMC(11) SDA_VMC(12) SDA_VMC(13) SDA_VMC(14) SDA_VMC(15) SDA_VMC(16) SDA_VMC(17) SDA_VMC(18) SDA_VMC(19)
-    SDA_VMC(20) SDA_VMC(21) SDA_VMC(22) SDA_VMC(23) SDA_VMC(24)
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-#undef SDA_VMC
 }
 
 __device__ inline uint32_t lds_addr(const void* p) {

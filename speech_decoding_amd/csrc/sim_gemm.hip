@@ -11,7 +11,7 @@
 // at 64 FLOP per LDS-DMA byte.  Here ONE workgroup owns a 256 x 256 tile over its K slice: every operand byte of the slice
 // enters LDS exactly once (128 FLOP / byte), eight waves (2 x 4, wave tile 128 (j) x 64 (i)) share it, and the K loop is the
 // ring conv_gemm's matrix mode uses: four 32 KB stages, three slabs of LDS-DMA in flight behind counted s_waitcnt vmcnt,
-// one raw s_barrier per 32-deep K-step (32 MFMAs per wave).  All DMA addresses are a scalar base advanced by a scalar add
+// one raw s_barrier per 32-deep K-step (16 MFMAs of 32 x 32 x 16 per wave).  All DMA addresses are a scalar base advanced by a scalar add
 // per K-step plus four per-lane byte offsets computed once (rows past the operands are clamped: they feed outputs that are
 // never stored).  Bound: HBM into LDS (~6 TB/s, MI355X_MICROARCH.md), then the matrix pipe.  Measured alone (SQ counters,
 // tools/probes/pmc_sim.sh, 2048 x 256): 525-590 us = 6 TB/s of LDS-DMA (half of it the 1.7 GB from HBM, half re-reads of W
@@ -35,10 +35,10 @@ constexpr int SG_NS = 4;                           // LDS stages; SG_NS - 1 slab
                                                    // five stages, 160 KB: 570 vs 590 us at 2048 x 256, 107 vs 103 at 256 x 256)
 constexpr int SG_PPW = 4;                          // 1 KB pieces per wave and slab: 2 of W + 2 of X (8 waves x 4 = 32 pieces)
 
-// M32: the K-step on v_mfma_f32_32x32x16 (sd_common.h, mma32): per wave 4 (j) x 2 (i) blocks of 32 x 32, two MFMAs each per
+// The K-step runs on v_mfma_f32_32x32x16 (sd_common.h, mma32): per wave 4 (j) x 2 (i) blocks of 32 x 32, two MFMAs each per
 // K-step; the 64-byte rows' swizzle is then chunk ^ ((row >> 2) & 3) — a 16-lane service group of ds_read_b128 (conv_tile.h)
 // holds the row quads {0, 3, 5, 6} or {1, 2, 4, 7} of ONE chunk.
-template <typename E, int NS, bool M32>
+template <typename E, int NS>
 __global__ __launch_bounds__(512, 2) void sim_gemm_kernel(const E* __restrict__ X, const E* __restrict__ W, float* __restrict__ partial,
                                                            const int M, const int N, const int Np, const long pitch, const int nslab,
                                                            const int ksplit, const int m_tiles, const int n_tiles) {
@@ -48,7 +48,6 @@ __global__ __launch_bounds__(512, 2) void sim_gemm_kernel(const E* __restrict__ 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wj = wid & 1, wi = wid >> 1;           // wave tile: columns j [wj * 128, +128), rows i [wi * 64, +64)
-  const int lr = lane & 15, lq = lane >> 4;
 
   // XCD-aware order (blocks b and b + 8 share an XCD / L2): the output tiles of one K slice run on one XCD side by side, so
   // the operand rows two tiles share are fetched from HBM once.  Pure speed: any placement is correct.
@@ -78,7 +77,7 @@ __global__ __launch_bounds__(512, 2) void sim_gemm_kernel(const E* __restrict__ 
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int r = (wid + 8 * h) * 16 + prow;                       // row of the tile
-    const int sw = (pchunk ^ (M32 ? ((r >> 2) & 3) : sw64(r))) * PER16;
+    const int sw = (pchunk ^ ((r >> 2) & 3)) * PER16;
     const long xr = min((long)r, (long)(M - 1 - m0)), wr = min((long)r, (long)(N - 1 - n0));      // clamped: never stored
     xoff[h] = (uint32_t)((xr * pitch + sw) * (long)sizeof(E));
     woff[h] = (uint32_t)((wr * pitch + sw) * (long)sizeof(E));
@@ -95,21 +94,13 @@ __global__ __launch_bounds__(512, 2) void sim_gemm_kernel(const E* __restrict__ 
   };
   auto advance = [&]() { xs += SLAB; ws += SLAB; };
 
-  f32x4 acc[M32 ? 1 : 8][M32 ? 1 : 4];
-  f32x16 acc32[M32 ? 4 : 1][M32 ? 2 : 1];
-  if constexpr (M32) {
+  f32x16 acc32[4][2];
 #pragma unroll
-    for (int a = 0; a < 4; ++a)
+  for (int a = 0; a < 4; ++a)
 #pragma unroll
-      for (int b = 0; b < 2; ++b)
+    for (int b = 0; b < 2; ++b)
 #pragma unroll
-        for (int v = 0; v < 16; ++v) acc32[a][b][v] = 0.f;
-  } else {
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
+      for (int v = 0; v < 16; ++v) acc32[a][b][v] = 0.f;
   const int l32 = lane & 31, lh = lane >> 5;
 
   constexpr int D = NS - 1;
@@ -135,70 +126,41 @@ __global__ __launch_bounds__(512, 2) void sim_gemm_kernel(const E* __restrict__ 
     const unsigned char* xsm = wsm + SG_OP_BYTES;              // X rows (second operand -> accumulator columns = i)
     // all twelve fragments of the K-step are requested at once, right behind the barrier
     uint4 bf[4], af[8];
-    if constexpr (M32) {
-      auto at = [&](int row, int chunk) { return row * ROW_B + ((chunk ^ ((row >> 2) & 3)) << 4); };
+    auto at = [&](int row, int chunk) { return row * ROW_B + ((chunk ^ ((row >> 2) & 3)) << 4); };
 #pragma unroll
-      for (int b = 0; b < 4; ++b) bf[b] = *reinterpret_cast<const uint4*>(xsm + at(wi * 64 + (b >> 1) * 32 + l32, 2 * (b & 1) + lh));
+    for (int b = 0; b < 4; ++b) bf[b] = *reinterpret_cast<const uint4*>(xsm + at(wi * 64 + (b >> 1) * 32 + l32, 2 * (b & 1) + lh));
 #pragma unroll
-      for (int a = 0; a < 8; ++a) af[a] = *reinterpret_cast<const uint4*>(wsm + at(wj * 128 + (a >> 1) * 32 + l32, 2 * (a & 1) + lh));
-      // af[2 A + h], bf[2 B + h]: block A / B, K half h; h outer, so an accumulator block comes round every eighth MFMA
+    for (int a = 0; a < 8; ++a) af[a] = *reinterpret_cast<const uint4*>(wsm + at(wj * 128 + (a >> 1) * 32 + l32, 2 * (a & 1) + lh));
+    // af[2 A + h], bf[2 B + h]: block A / B, K half h; h outer, so an accumulator block comes round every eighth MFMA;
+    // slab s + D's pieces go out behind every second row of MFMAs: the matrix pipe works through the issue
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
+    for (int h = 0; h < 2; ++h)
 #pragma unroll
-        for (int a = 0; a < 4; ++a) {
+      for (int a = 0; a < 4; ++a) {
 #pragma unroll
-          for (int b = 0; b < 2; ++b) acc32[a][b] = mma32<E>(af[2 * a + h], bf[2 * b + h], acc32[a][b]);
-          if ((a & 1) && more) issue(nxt, 2 * h + (a >> 1));
-        }
-    } else {
-#pragma unroll
-    for (int b = 0; b < 4; ++b) bf[b] = *reinterpret_cast<const uint4*>(xsm + lds_sw64(wi * 64 + b * 16 + lr, lq));
-#pragma unroll
-    for (int a = 0; a < 8; ++a) af[a] = *reinterpret_cast<const uint4*>(wsm + lds_sw64(wj * 128 + a * 16 + lr, lq));
-#pragma unroll
-    for (int a = 0; a < 8; ++a) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b) acc[a][b] = mma16<E>(af[a], bf[b], acc[a][b]);
-      // slab s + D's pieces go out behind MFMA rows 1, 3, 5, 7: the matrix pipe works through the issue
-      if ((a & 1) && more) issue(nxt, a >> 1);
-    }
-    }
+        for (int b = 0; b < 2; ++b) acc32[a][b] = mma32<E>(af[2 * a + h], bf[2 * b + h], acc32[a][b]);
+        if ((a & 1) && more) issue(nxt, 2 * h + (a >> 1));
+      }
     if (more) advance();
     cur = cur == NS - 1 ? 0 : cur + 1;
   }
 
-  // K-split partial sums: lane (lq, lr) of block (a, b) holds S[i][j .. j + 3], i = m0 + wi * 64 + b * 16 + lr,
-  // j = n0 + wj * 128 + a * 16 + 4 * lq
+  // K-split partial sums.  Block (a, b), register v: S[i][j], i = m0 + wi * 64 + b * 32 + (lane & 31), j = n0 + wj * 128 +
+  // a * 32 + 8 * (v >> 2) + 4 * (lane >> 5) + (v & 3): four consecutive j per register quad
   float* __restrict__ P = partial + (size_t)ks * M * Np;
-  if constexpr (M32) {
-    // block (a, b), register v: S[i][j], i = m0 + wi * 64 + b * 32 + (lane & 31), j = n0 + wj * 128 + a * 32 + 8 * (v >> 2) +
-    // 4 * (lane >> 5) + (v & 3): four consecutive j per register quad
 #pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int i = m0 + wi * 64 + b * 32 + l32;
-      if (i < M) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int j = n0 + wj * 128 + a * 32 + 8 * g + 4 * lh;
-            if (j + 3 < Np)
-              *reinterpret_cast<f32x4*>(P + (size_t)i * Np + j) =
-                  f32x4{acc32[a][b][4 * g], acc32[a][b][4 * g + 1], acc32[a][b][4 * g + 2], acc32[a][b][4 * g + 3]};
-          }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int i = m0 + wi * 64 + b * 16 + lr;
+  for (int b = 0; b < 2; ++b) {
+    const int i = m0 + wi * 64 + b * 32 + l32;
     if (i < M) {
 #pragma unroll
-      for (int a = 0; a < 8; ++a) {
-        const int j = n0 + wj * 128 + a * 16 + 4 * lq;
-        if (j + 3 < Np) *reinterpret_cast<f32x4*>(P + (size_t)i * Np + j) = acc[a][b];
-      }
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int j = n0 + wj * 128 + a * 32 + 8 * g + 4 * lh;
+          if (j + 3 < Np)
+            *reinterpret_cast<f32x4*>(P + (size_t)i * Np + j) =
+                f32x4{acc32[a][b][4 * g], acc32[a][b][4 * g + 1], acc32[a][b][4 * g + 2], acc32[a][b][4 * g + 3]};
+        }
     }
   }
 }
@@ -207,8 +169,7 @@ template <typename E, int NS>
 int launch_sim_ns(const void* X, const void* W, float* partial, int M, int N, int Np, long K, long pitch, int ksplit, hipStream_t st) {
   constexpr int lds = NS * SG_STAGE;
   static unsigned long long attr_done = 0;        // per device
-  static const bool m32 = []() { const char* e = getenv("SDA_SIM_MFMA32"); return !e || atoi(e) != 0; }();
-  auto kern = m32 ? sim_gemm_kernel<E, NS, true> : sim_gemm_kernel<E, NS, false>;
+  auto kern = sim_gemm_kernel<E, NS>;
   if (first_use_on_device(attr_done)) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
       set_error("sim_gemm: cannot reserve %d bytes of LDS", lds);

@@ -43,9 +43,6 @@ template <> struct WK<uint16_t> { static constexpr int KSTEP = 32; };
 template <> struct WK<half_t> { static constexpr int KSTEP = 32; };
 template <> struct WK<float> { static constexpr int KSTEP = 16; };
 
-typedef __attribute__((address_space(1))) const void gmem_cv;
-typedef __attribute__((address_space(3))) void lds_v;
-
 // TN = ci columns per workgroup: 64 for KS = 3 (three accumulator sets), 128 for KS = 1 (wave tile
 // TILE_M/2 x 64: fewer LDS bytes per MFMA and half as many re-reads of dy).
 // KM = MFMA K-steps per staged chunk, NS = LDS stages (NS - 1 chunks of LDS-DMA in flight behind the MFMAs).
@@ -263,10 +260,6 @@ __global__ __launch_bounds__(256, (WGeom<E, TILE_M, KS, TN, KM, NS>::LDS > 80 * 
     if (c_valid == KT && xrow0 >= 0 && xrow0 + KT + 2 * halo <= a.rows_limit) {
       dy_base = dyg + (size_t)c_row * a.dy_pitch + co0;
       x_base = xg + (size_t)xrow0 * a.x_pitch + ci0;
-#ifdef SDA_WGRAD_FAKE_SRC      /* diagnostic build (garbage results): every chunk re-reads the segment's first rows — no memory-system load */
-      dy_base = dyg + (size_t)seg_r0 * a.dy_pitch + co0;
-      x_base = xg + (size_t)seg_r0 * a.x_pitch + ci0;
-#endif
       nxt_off = (uint32_t)(buf * G::STAGE);
       return true;
     }
@@ -285,12 +278,9 @@ __global__ __launch_bounds__(256, (WGeom<E, TILE_M, KS, TN, KM, NS>::LDS > 80 * 
   };
   constexpr int NPW = NDY + NX;                // pieces per wave and chunk (upper bound)
   constexpr int NGRP = (KT / KSTEP) * KS;      // MFMA groups per chunk
-#ifndef SDA_WGRAD_FRONT
-#define SDA_WGRAD_FRONT 1
-#endif
-  // pieces per MFMA group: SDA_WGRAD_FRONT = 1 spreads them over all groups of the chunk, 2 over its first half, 3 over its
-  // first third (more time to land before the next chunk's wait; an issue is three scalar-side instructions now)
-  constexpr int PER_GRP = (NPW * SDA_WGRAD_FRONT + NGRP - 1) / NGRP;
+  // pieces per MFMA group: spread over all groups of the chunk (issuing them during its first half or third would leave them
+  // more time to land before the next chunk's wait, but an issue is three scalar-side instructions now)
+  constexpr int PER_GRP = (NPW + NGRP - 1) / NGRP;
 
   // 16-bit types: per-lane offsets of every transposed fragment read of a stage, computed once (tr_operand.h); a read of
   // K-step kk is then `stage base + offset` plus the immediate kk * KSTEP rows

@@ -389,7 +389,7 @@ class EncoderEngine:
         # forward k = 3 convs (nothing competes for the CU's LDS there): two tiles per workgroup share each weight slab
         k3_flags = L.CONV_PAIR_TILES
         if self.flat_forward:
-            k3_flags |= L.CONV_FLAT_TILES | 1024     # 1024: a CU's second workgroup takes its 128-row tile first (staggered epilogues)
+            k3_flags |= L.CONV_FLAT_TILES | L.CONV_FLAT_STAGGER     # a CU's second workgroup takes its 128-row tile first
         f = _Forward(self, P, ctx, dev, torch.cuda.current_stream(dev), need_grad, need_dx, eps, momentum, k3_flags,
                      count=float(B) * T * self.world)       # BatchNorm statistics span the GLOBAL batch under data parallelism
 

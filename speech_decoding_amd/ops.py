@@ -3,7 +3,6 @@ memory and the current HIP stream; every computation happens inside libsdamd.so.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Optional
 
 import numpy as np
@@ -570,9 +569,9 @@ def conv_stats_rows(B: int, T: int, KS: int, Cout_p: int, flags: int = 0) -> int
     return L.load().sda_conv_stats_rows(B, T, KS, Cout_p, flags)
 
 
-# the similarity matmul of 16-bit operands on sim_gemm.hip's 256 x 256 tiles (SDA_SIM_GEMM=0: conv_gemm's split-K matrix mode
-# with 128 x 128 tiles, which fp32 storage always uses)
-SIM_GEMM_TILES256 = os.environ.get("SDA_SIM_GEMM", "1") != "0"
+# the similarity matmul of 16-bit operands on sim_gemm.hip's 256 x 256 tiles (False: conv_gemm's split-K matrix mode with
+# 128 x 128 tiles, which fp32 storage always uses)
+SIM_GEMM_TILES256 = True
 
 
 def splitk_plan(dtype, M: int, N: int, K: int, pitch: int):

@@ -75,6 +75,11 @@ def test_argument_validation_without_launch(lib):
     a = lib.ConvArgs()
     assert L.sda_conv_gemm(ctypes.byref(a), None) == -1
     assert b"null" in L.sda_last_error()
+    for flags in (256, 1 << 30):          # a bit sd_amd.h does not name is refused before anything looks at the device
+        a = lib.ConvArgs()
+        a.x, a.w, a.y, a.flags = 64, 64, 64, flags
+        assert L.sda_conv_gemm(ctypes.byref(a), None) == -1
+        assert b"flag" in L.sda_last_error()
     w = lib.WgradArgs()
     assert L.sda_wgrad_gemm(ctypes.byref(w), None) == -1
     assert L.sda_pack_rows(None, None, 1, 1, 1, 64, 0, None) == -1

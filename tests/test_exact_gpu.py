@@ -115,6 +115,55 @@ def test_conv3_flat_glu_epilogue_keeps_the_exact_gate(ops, regime, dtype):
     assert padding_is_zero(gate, s.B, half, s.T)
 
 
+@pytest.mark.parametrize("B,T,dtype", [(136, 345, torch.bfloat16), (136, 345, torch.float16), (227, 345, torch.bfloat16),
+                                       (227, 345, torch.float16), (136, 345, torch.float32)],
+                         ids=lambda v: name(v) if isinstance(v, torch.dtype) else str(v))
+def test_conv3_flat_staggered_tile_order_gives_the_same_bits(ops, B, T, dtype):
+    """SDA_CONV_FLAT_STAGGER (the forward path's order: the second workgroup of a CU takes its 128-row tile(s) first) against
+    SDA_CONV_FLAT_TILES alone on the same operands, 320 -> 320 channels (two channel tiles), dilation 2, bias + residual +
+    statistics: the stored buffers are equal bit for bit.  On 256 CUs (136, 345) is 384 units, 2 per workgroup — every second
+    workgroup of a CU turns one 256-row tile into 128 + 128 — and (227, 345) is 641 units, 3 per workgroup — 128 + 256 instead of
+    256 + 128; fp32 storage runs 128-row tiles in either order.
+    The statistics: a 256-row tile writes its sums into its first unit's row and zeros into the second, so the two orders
+    spread the same sums over a run's rows differently by design (and the same for fp32, where the rows themselves must be
+    equal).  What both orders share is the sum over a workgroup's run of units, and the operands are integers small enough that
+    every partial sum (and sum of squares) of a tile is exact in fp32, whatever the order: the per-run sums, taken in float64,
+    are compared with torch.equal, and so are the raw rows for fp32."""
+    from speech_decoding_amd import lib as L
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if cus != 256:
+        pytest.skip(f"the shapes are taken from conv3_flat's tile plan for 256 CUs; this device has {cus}")
+    C, dil = 320, 2
+    n_units = ops.conv_stats_rows(B, T, 3, C, L.CONV_FLAT_TILES)
+    per_wg = -(-n_units * (C // 160) // (2 * cus))
+    assert (n_units, per_wg) == {136: (384, 2), 227: (641, 3)}[B]
+    g = torch.Generator(device=DEV)
+    g.manual_seed(B)
+    x = torch.randint(-1, 2, (B, C, T), device=DEV, generator=g).to(dtype)
+    w = torch.randint(-1, 2, (C, C, 3), device=DEV, generator=g).float()
+    xb = ops.pack_rows(x, ops.new_rows(B, T, C, dtype, DEV))
+    wp = ops.pack_conv_weight(w, C, C, dtype)
+    bias = ops.pack_vector(torch.randint(-3, 4, (C,), device=DEV, generator=g).float(), C)
+    got = []
+    for flags in (L.CONV_FLAT_TILES, L.CONV_FLAT_TILES | L.CONV_FLAT_STAGGER):
+        yb = ops.new_rows(B, T, C, dtype, DEV)
+        stats = torch.full((n_units, 2, C), NAN, device=DEV)
+        ops.conv_gemm(xb, wp, yb, B=B, T=T, KS=3, dil=dil, bias=bias, res=xb, stats=stats, flags=flags)
+        got.append((yb, stats))
+    (y0, s0), (y1, s1) = got
+    assert torch.equal(ops.unpack_rows(y0, B, C, T), ops.unpack_rows(y1, B, C, T))
+    assert torch.equal(y0, y1)                                           # padding included
+    assert float(y0.float().abs().max()) ** 2 * 256 < 2 ** 24            # a tile's sums are exact in fp32
+    run = torch.arange(n_units, device=DEV) // per_wg
+    sums = [torch.zeros((int(run[-1]) + 1, 2, C), dtype=torch.float64, device=DEV).index_add_(0, run, s.double()) for s in (s0, s1)]
+    assert not bool(torch.isnan(sums[0]).any())
+    assert torch.equal(sums[0], sums[1])
+    if dtype == torch.float32:
+        assert torch.equal(s0, s1)
+    else:
+        assert not torch.equal(s0, s1), "the staggered order was not taken"
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # kernel size 1
 # ---------------------------------------------------------------------------------------------------------------

@@ -27,20 +27,10 @@ def main():
             res = x if cin == cout else None
             fl = 2.0 * B * T * KS * cin * cout
             for name, kw in [("full", dict(bias=bias, res=res, stats=stats)), ("plain", dict()),
-                             ("no_epi", dict(flags=256)), ("no_main", dict(bias=bias, res=res, stats=stats, flags=512)),
-                             ("neither", dict(flags=768)), ("pair_full", dict(bias=bias, res=res, stats=stats, flags=8192)),
-                             ("flat", dict(bias=bias, res=res, stats=stats, flags=16384)), ("flat_plain", dict(flags=16384)),
-                             ("flat_noepi", dict(flags=16384 | 256)),
-
-                             ("flat_noho", dict(bias=bias, res=res, stats=stats, flags=16384 | 64)),       # 64: no priority hand-over
-                             ("flat_noepi_noho", dict(flags=16384 | 256 | 64)),
-                             ("flat_1024", dict(bias=bias, res=res, stats=stats, flags=16384 | 1024)),
-                             ("flat_2048", dict(bias=bias, res=res, stats=stats, flags=16384 | 2048)),
-                             ("flat_3072", dict(bias=bias, res=res, stats=stats, flags=16384 | 3072)),
-                             ("flat_1024_noho", dict(bias=bias, res=res, stats=stats, flags=16384 | 1024 | 64)),
-                             ("flat_2048_noho", dict(bias=bias, res=res, stats=stats, flags=16384 | 2048 | 64)),
-                             ("flat_noepi_nodma", dict(flags=16384 | 256 | 16)),       # diagnostic builds: no LDS-DMA in the K loop
-                             ("flat_noepi_nodma_nolds", dict(flags=16384 | 256 | 8))]:  # ... and no fragment reads either (MFMA only)
+                             ("pair_full", dict(bias=bias, res=res, stats=stats, flags=L.CONV_PAIR_TILES)),
+                             ("flat", dict(bias=bias, res=res, stats=stats, flags=L.CONV_FLAT_TILES)),
+                             ("flat_plain", dict(flags=L.CONV_FLAT_TILES)),
+                             ("flat_stagger", dict(bias=bias, res=res, stats=stats, flags=L.CONV_FLAT_TILES | L.CONV_FLAT_STAGGER))]:
                 if KS != 3 and name.startswith("flat"):
                     continue
                 us = timeit(lambda: ops.conv_gemm(x, wp, y, B=B, T=T, KS=KS, dil=dil, **kw))

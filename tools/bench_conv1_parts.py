@@ -21,7 +21,6 @@ for name, cin, cout in [("f2 fwd", 640, 1024), ("f2 dgrad", 1024, 640), ("f1 fwd
     stats = torch.empty((B * ops.n_t_tiles(T), 2, cout), device=dev)
     fl = 2.0 * B * T * cin * cout
     for tag, kw in [("gelu+pre+stats", dict(bias=bias, gelu=True, y_pre=yp, stats=stats)), ("gelu+pre", dict(bias=bias, gelu=True, y_pre=yp)),
-                    ("gelu", dict(bias=bias, gelu=True)), ("plain", dict()), ("no_epi", dict(flags=256)), ("no_main", dict(bias=bias, gelu=True, y_pre=yp, flags=512)),
-                    ("neither", dict(flags=768))]:
+                    ("gelu", dict(bias=bias, gelu=True)), ("plain", dict())]:
         us = timeit(lambda: ops.conv_gemm(x, wp, y, B=B, T=T, KS=1, dil=0, **kw))
         print(f"{name:10s} {tag:16s} {us:7.1f} us {fl/us/1e6:7.1f} TF", flush=True)

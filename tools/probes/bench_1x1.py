@@ -1,9 +1,9 @@
-"""The row-layout 1 x 1 convs of the config-2 step alone (f1, f2 forward; their data gradients), each with its K loop /
-epilogue switched off in turn (diagnostic flags 256 = no epilogue, 512 = no K loop).  Diagnostic, not part of the product."""
+"""The row-layout 1 x 1 convs of the config-2 step alone (f1, f2 forward; their data gradients) on each tiling.
+Diagnostic, not part of the product."""
 import sys, os, math
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
-from speech_decoding_amd import ops
+from speech_decoding_amd import ops, lib as L
 
 
 def timeit(fn, n=20, warm=3):
@@ -35,20 +35,9 @@ def main():
         fl = 2.0 * B * T * cin * cout
         wr = B * (T + 16) * cout * 2 * (2 if fwd else 1) / 1e6
         rd = B * (T + 16) * cin * 2 / 1e6
-        for vn, kw in [("full", full), ("plain", dict()), ("no_epi", dict(flags=256)), ("no_main", dict(flags=512, **full)),
-                       ("neither", dict(flags=768)),
-                       ("flat", dict(flags=16384, **fullf)), ("flat_plain", dict(flags=16384)), ("flat_no_epi", dict(flags=16384 | 256)),
-                       ("flat_no_main", dict(flags=16384 | 512, **fullf)), ("flat_same_order", dict(flags=16384 | 1024, **fullf)),
-                       ("flat_no_prio", dict(flags=16384 | 2048, **fullf)), ("flat_no_prio_same", dict(flags=16384 | 2048 | 1024, **fullf)),
-                       ("flat_1percu", dict(flags=16384 | 32768, **fullf)), ("flat_1percu_no_epi", dict(flags=16384 | 32768 | 256)),
-                       ("flat_1percu_no_main", dict(flags=16384 | 32768 | 512, **fullf)),
-                       ("flat_wrap_store", dict(flags=16384 | 32, **fullf)), ("flat_wrap_store_no_gelu", dict(flags=16384 | 32 | 16, **fullf)),
-                       ("flat_no_main_wrap_store", dict(flags=16384 | 32 | 512, **fullf)),
-                       ("flat_no_dma", dict(flags=16384 | 128, **fullf)), ("flat_no_dma_no_gelu", dict(flags=16384 | 128 | 16, **fullf)),
-                       ("flat_no_dma_no_epi", dict(flags=16384 | 128 | 256)),
-                       ("flat_no_store", dict(flags=16384 | 8, **fullf)), ("flat_no_gelu", dict(flags=16384 | 16, **fullf)),
-                       ("flat_no_store_no_gelu", dict(flags=16384 | 24, **fullf)),
-                       ("flat_no_main_no_store", dict(flags=16384 | 512 | 8, **fullf)), ("flat_no_main_no_gelu", dict(flags=16384 | 512 | 16, **fullf))]:
+        for vn, kw in [("full", full), ("plain", dict()),
+                       ("flat", dict(flags=L.CONV_FLAT_TILES, **fullf)), ("flat_plain", dict(flags=L.CONV_FLAT_TILES)),
+                       ("flat_1percu", dict(flags=L.CONV_FLAT_TILES | L.CONV_ONE_PER_CU, **fullf))]:
             us = timeit(lambda: ops.conv_gemm(x, wp, y, B=B, T=T, KS=1, dil=0, **kw))
             print(f"{name:9s} {cin:4d}->{cout:4d} {vn:8s} {us:7.1f} us  {fl / us / 1e6:6.1f} TF  (reads {rd:.0f} MB, writes {wr:.0f} MB"
                   f" -> {(rd + wr) / us:.2f} TB/s)", flush=True)
