@@ -36,7 +36,8 @@ extern "C" {
                                4: sda_fill_zero, sda_gather_samples, sda_clip_merge_rows; SDA_WGRAD_FLAT_ROWS with a sample permutation;
                                   sda_clip_dz serves more than 256 speech rows (256 x 256 tiles); SDA_CONV_WIDE_TILES
                                   (still 4, additions only: sda_robust_stats / sda_robust_stats_scratch_bytes, sda_scale_clamp_rows,
-                                  sda_gather_baseline_windows — the Brennan2018 input path; sda_window_gemm_f32 — FIR filter / sinc resampler) */
+                                  sda_gather_baseline_windows — the Brennan2018 input path; sda_window_gemm_f32 — FIR filter / sinc resampler;
+                                  sda_mel_power_f32 — power, mel filterbank and log behind the STFT) */
 #define SDA_ROW_PAD 16
 #define SDA_CH_ALIGN 64
 
@@ -555,6 +556,23 @@ int sda_input_grad(const void* G, long g_pitch, const void* W, const int* widx, 
  * x_row_stride < (frames - 1) * S + K return -1 (sda_last_error) and launch nothing. */
 int sda_window_gemm_f32(const float* x, long x_row_stride, int rows, long frames, int S, int K, const float* B, int N,
                         float* out, long out_row_stride, void* stream);
+
+/* ---- Log-mel speech features (ABI 4, addition): the pass behind the STFT (csrc/mel_power.hip).  The STFT is
+ * sda_window_gemm_f32 with S = hop, K = n_fft, N = 2 * n_freqs and B = window x DFT, real and imaginary parts interleaved;
+ * its output is this entry's `spec` as it stands (torchaudio.transforms.MelSpectrogram(power=2.0), then log(eps + mel)):
+ *     P[r][m][b]   = spec[r][m * spec_pitch + 2 b]^2 + spec[r][m * spec_pitch + 2 b + 1]^2,        b < n_freqs
+ *     mel[r][j][m] = sum_{b < n_freqs} P[r][m][b] * fb[b * n_mels + j],                            j < n_mels, m < frames
+ *     out[r][j * out_pitch + m] = log_eps < 0 ? mel : logf(log_eps + mel),                         r < rows
+ * fp32 in and out; P = fmaf(im, im, re * re); exact-fp32 MFMA (one fmaf chain per output in increasing b).  spec: rows
+ * spec_row_stride elements apart, frame m at m * spec_pitch, spec_pitch >= 2 * n_freqs; only the 2 * n_freqs floats of each of
+ * the `frames` frames are read.  fb: n_freqs x n_mels row-major.  out: rows out_row_stride elements apart, each
+ * (n_mels, out_pitch) with out_pitch >= frames: out[r][j][0 ... frames - 1] written and nothing else (features x frames, the
+ * layout of the speech tables).  Any rows, frames, n_freqs, n_mels >= 1; no alignment beyond the element's.  No atomics: the
+ * same bits on every call.  Null pointers, non-positive sizes, spec_pitch < 2 * n_freqs, out_pitch < frames,
+ * spec_row_stride < (frames - 1) * spec_pitch + 2 * n_freqs and out_row_stride < (n_mels - 1) * out_pitch + frames return -1
+ * (sda_last_error) and launch nothing. */
+int sda_mel_power_f32(const float* spec, long spec_row_stride, long spec_pitch, int rows, long frames, int n_freqs,
+                      const float* fb, int n_mels, float log_eps, float* out, long out_row_stride, long out_pitch, void* stream);
 
 #ifdef __cplusplus
 }

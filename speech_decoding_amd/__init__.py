@@ -6,5 +6,6 @@ from .loss import CLIPLoss, MSELoss, torch_exp, torch_log   # noqa: F401
 from .retrieval import SpeechBank, Retrieval, retrieve   # noqa: F401
 from .config import Config, load_config                   # noqa: F401
 from .data import ResidentSubjectFeed                     # noqa: F401
+from .signal_prep import mel_spectrogram, log_mel, mel_embeddings   # noqa: F401
 
-__all__ = ["BrainEncoder", "Classifier", "CLIPLoss", "MSELoss", "SpeechBank", "Retrieval", "retrieve", "ResidentSubjectFeed", "torch_exp", "torch_log", "Config", "load_config", "load_library", "SdaError"]
+__all__ = ["BrainEncoder", "Classifier", "CLIPLoss", "MSELoss", "SpeechBank", "Retrieval", "retrieve", "ResidentSubjectFeed", "mel_spectrogram", "log_mel", "mel_embeddings", "torch_exp", "torch_log", "Config", "load_config", "load_library", "SdaError"]

@@ -1092,3 +1092,26 @@ def linear_rows(x, w, y, T, *, bias=None, res=None, gelu=False, scratch=None):
     L.check(L.load().sda_splitk_epilogue(_p(scratch), ksplit, _p(bias), _p(res), _p(y), T, Cout_p, int(gelu), dt_code(x.dtype), _st()),
             "splitk_epilogue")
     return y
+
+
+def mel_power(spec: torch.Tensor, fb: torch.Tensor, log_eps: Optional[float] = None) -> torch.Tensor:
+    """`sda_mel_power_f32` (csrc/mel_power.hip): spec (..., frames, n_freqs, 2) contiguous fp32, real and imaginary parts
+    interleaved as the STFT window GEMM leaves them, fb (n_freqs, n_mels) contiguous fp32 -> fp32 (..., n_mels, frames):
+    out[..., j, m] = sum_b (re^2 + im^2)[..., m, b] fb[b, j], or logf(log_eps + that) when log_eps is given (>= 0)."""
+    _need_cuda(spec, fb)
+    if spec.dtype != torch.float32 or fb.dtype != torch.float32 or not spec.is_contiguous() or not fb.is_contiguous():
+        raise L.SdaError("mel_power: contiguous fp32 tensors")
+    if spec.dim() < 3 or spec.shape[-1] != 2 or fb.dim() != 2 or fb.shape[0] != spec.shape[-2]:
+        raise L.SdaError(f"mel_power: spec (..., frames, n_freqs, 2) and fb (n_freqs, n_mels), got {tuple(spec.shape)} and {tuple(fb.shape)}")
+    if log_eps is not None and not log_eps >= 0:
+        raise L.SdaError("mel_power: log_eps must be None (no log) or >= 0")
+    frames, n_freqs = spec.shape[-3], spec.shape[-2]
+    n_mels = fb.shape[1]
+    lead = tuple(spec.shape[:-3])
+    rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    out = torch.empty(lead + (n_mels, frames), dtype=torch.float32, device=spec.device)
+    with torch.cuda.device(spec.device):
+        L.check(L.load().sda_mel_power_f32(_p(spec), frames * n_freqs * 2, n_freqs * 2, rows, frames, n_freqs, _p(fb), n_mels,
+                                           -1.0 if log_eps is None else float(log_eps), _p(out), n_mels * frames, frames, _st()),
+                "mel_power")
+    return out

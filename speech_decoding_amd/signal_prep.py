@@ -16,22 +16,31 @@ S = reduced input rate, N = reduced output rate, B = bank^T; the FIR filter is t
 consecutive frames grouped into one, which `window_matrix` does for any bank.  `brain_preproc` and `speech_embeddings` compose
 the three calls as the reference's dataset classes do.  Device tensors only: there is no CPU path.
 
+The second speech representation of the paper (the log-mel spectrogram of its regression and "Deep Mel" baselines, which the
+reference leaves to torchaudio on the host) is the same kernel once more: an STFT frame is the matrix window x DFT applied
+to windows hop_length apart (S = hop_length, K = n_fft, N = 2 (n_fft / 2 + 1), `stft_matrix`, `stft`), and one more kernel,
+`sda_mel_power_f32` (csrc/mel_power.hip), takes the power, applies the mel filterbank and the log and stores
+(features, frames): `mel_spectrogram`, `log_mel`, `mel_embeddings`.
+
 Parity.  Neither mne nor torchaudio can be installed next to this build, so bit-parity with `mne.filter.create_filter` and
 with `torchaudio.functional.resample` is UNPINNED: `bandpass_taps` follows mne's documented "firwin" design rule and
 `sinc_resample_bank` torchaudio's documented `sinc_interp_hann` kernel, and both are tested against float64 restatements of
-those rules, not against the libraries.  `fir_filter` takes arbitrary taps, so a user with mne can pass mne's own
+those rules, not against the libraries.  The same holds for `stft_matrix` (torch.stft with a periodic Hann window,
+`normalized="window"`) and `mel_filterbank` (`torchaudio.functional.melscale_fbanks`, HTK scale, no normalisation).  `fir_filter` takes arbitrary taps, so a user with mne can pass mne's own
 (`mne.filter.create_filter(...)`).
 """
 from __future__ import annotations
 
 import math
+import warnings
 from functools import lru_cache
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import lib as L
+from . import ops
 from .wav2vec2 import resample_fft
 
 MAX_GROUP = 64          # largest G window_group considers = the kernel's output tile width
@@ -236,3 +245,136 @@ def speech_embeddings(embedder, wave: torch.Tensor, sample_rate: int, preprocs, 
             embedder.taps = taps
     rate_after = audio_resample_rate * emb.shape[-1] / wave16.shape[-1]
     return resample_fft(emb, up=preprocs["brain_resample_rate"] / rate_after)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# log-mel speech features: the STFT on the window GEMM, then sda_mel_power_f32
+# ---------------------------------------------------------------------------------------------------------------
+@lru_cache(maxsize=16)
+def _stft_matrix(n_fft: int, win_length: int, normalized: bool) -> np.ndarray:
+    if n_fft < 1 or not 1 <= win_length <= n_fft:
+        raise ValueError("stft_matrix: n_fft >= 1 and 1 <= win_length <= n_fft")
+    w = np.zeros(n_fft, dtype=np.float64)
+    left = (n_fft - win_length) // 2
+    w[left:left + win_length] = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(win_length, dtype=np.float64) / win_length)
+    c = math.sqrt(float((w * w).sum())) if normalized else 1.0
+    k = np.arange(n_fft, dtype=np.int64)[:, None]
+    b = np.arange(n_fft // 2 + 1, dtype=np.int64)[None, :]
+    ang = 2 * np.pi * ((b * k) % n_fft).astype(np.float64) / n_fft      # the angle reduced in integers: exact zeros, exact symmetry
+    B = np.empty((n_fft, 2 * (n_fft // 2 + 1)), dtype=np.float64)
+    B[:, 0::2] = w[:, None] * np.cos(ang) / c
+    B[:, 1::2] = -w[:, None] * np.sin(ang) / c
+    B.setflags(write=False)
+    return B
+
+
+def stft_matrix(n_fft: int, win_length: Optional[int] = None, normalized: bool = True) -> np.ndarray:
+    """One STFT frame as a matrix, float64 (n_fft, 2 (n_fft // 2 + 1)): frame @ B = the one-sided spectrum of the windowed
+    frame, real and imaginary parts interleaved,
+        B[k, 2 b] = w[k] cos(2 pi ((b k) mod n_fft) / n_fft) / c,     B[k, 2 b + 1] = -w[k] sin(2 pi ((b k) mod n_fft) / n_fft) / c.
+    w = the periodic Hann window 0.5 - 0.5 cos(2 pi k / win_length) (torch.hann_window's default), zero-padded to n_fft on both
+    sides with (n_fft - win_length) // 2 on the left when shorter, as torch.stft centres it; c = sqrt(sum w^2) when `normalized`
+    (torchaudio's Spectrogram(normalized=True) = "window": the spectrum divided by the window's L2 norm), else 1.  Parity with
+    torch.stft's own output: unpinned (module docstring)."""
+    n_fft = int(n_fft)
+    return _stft_matrix(n_fft, n_fft if win_length is None else int(win_length), bool(normalized))
+
+
+_warned_empty_filters = False
+
+
+@lru_cache(maxsize=16)
+def _mel_filterbank(n_freqs: int, f_min: float, f_max: float, n_mels: int, sample_rate: int) -> np.ndarray:
+    if n_freqs < 1 or n_mels < 1 or not 0 <= f_min < f_max:
+        raise ValueError("mel_filterbank: n_freqs >= 1, n_mels >= 1, 0 <= f_min < f_max")
+    all_freqs = np.linspace(0, sample_rate // 2, n_freqs)
+    m_min, m_max = 2595.0 * math.log10(1.0 + f_min / 700.0), 2595.0 * math.log10(1.0 + f_max / 700.0)
+    f_pts = 700.0 * (10.0 ** (np.linspace(m_min, m_max, n_mels + 2) / 2595.0) - 1.0)
+    f_diff = f_pts[1:] - f_pts[:-1]
+    slopes = f_pts[None, :] - all_freqs[:, None]                        # (n_freqs, n_mels + 2)
+    down = -slopes[:, :-2] / f_diff[:-1]
+    up = slopes[:, 2:] / f_diff[1:]
+    fb = np.maximum(0.0, np.minimum(down, up))
+    fb.setflags(write=False)
+    return fb
+
+
+def mel_filterbank(n_freqs: int, f_min: float, f_max: float, n_mels: int, sample_rate: int) -> np.ndarray:
+    """`torchaudio.functional.melscale_fbanks(n_freqs, f_min, f_max, n_mels, sample_rate, norm=None, mel_scale="htk")` by its
+    documented rule, float64 (n_freqs, n_mels): all_freqs = linspace(0, sample_rate // 2, n_freqs); mel(f) = 2595 log10(1 + f / 700);
+    n_mels + 2 points equally spaced in mel from f_min to f_max, mapped back to Hz as f_pts; triangles
+        fb[b, j] = max(0, min((all_freqs[b] - f_pts[j]) / (f_pts[j + 1] - f_pts[j]), (f_pts[j + 2] - all_freqs[b]) / (f_pts[j + 2] - f_pts[j + 1]))).
+    A filter narrower than the bin spacing can contain no bin and is then all zero (at n_fft = 512, 16 kHz, 120 filters some of
+    the lowest are): torchaudio only warns, and so does this, once.  Parity with torchaudio's own array: unpinned."""
+    global _warned_empty_filters
+    fb = _mel_filterbank(int(n_freqs), float(f_min), float(f_max), int(n_mels), int(sample_rate))
+    empty = int((fb.max(axis=0) == 0.0).sum())
+    if empty and not _warned_empty_filters:
+        _warned_empty_filters = True
+        warnings.warn(f"mel_filterbank: {empty} of {n_mels} mel filters contain no frequency bin and are all zero "
+                      f"(n_freqs = {n_freqs} may be too low for n_mels = {n_mels})")
+    return fb
+
+
+def stft(wave: torch.Tensor, n_fft: int = 512, hop_length: int = 128, win_length: Optional[int] = None, normalized: bool = True,
+         center: bool = True) -> torch.Tensor:
+    """`torch.stft(wave, n_fft, hop_length, win_length, window=hann_window(win_length), center=center, pad_mode="reflect",
+    normalized=False, onesided=True)` divided by the window's L2 norm when `normalized` (torchaudio's Spectrogram), as real
+    pairs: (..., L) -> fp32 (..., frames, n_freqs = n_fft // 2 + 1, 2) — FRAME-major, the layout the window GEMM leaves and
+    `sda_mel_power_f32` reads (torch.stft returns (..., n_freqs, frames)).  center: n_fft // 2 samples of EVEN reflection per side
+    (x[p], ..., x[1] | x | x[-2], ..., x[-1 - p]; not the odd extension of fir_filter), which needs L > n_fft // 2 as in torch;
+    frames = 1 + L // hop_length.  Without it L >= n_fft and frames = 1 + (L - n_fft) // hop_length.  `stft_matrix` through
+    `_apply_bank`: S = hop_length, K = n_fft, N = 2 n_freqs."""
+    _check_device(wave, "stft")
+    n_fft, hop = int(n_fft), int(hop_length)
+    if n_fft < 1 or hop < 1:
+        raise L.SdaError("stft: n_fft >= 1 and hop_length >= 1")
+    n = wave.shape[-1]
+    rows = wave.reshape(-1, n).float()
+    if center:
+        p = n_fft // 2
+        if n <= p:
+            raise L.SdaError(f"stft: reflection padding of {p} samples needs more than {p} samples, got {n}")
+        rows = torch.cat([rows[:, 1:p + 1].flip(-1), rows, rows[:, n - 1 - p:n - 1].flip(-1)], dim=1)
+    elif n < n_fft:
+        raise L.SdaError(f"stft: {n} samples are fewer than n_fft = {n_fft}")
+    frames = 1 + (rows.shape[1] - n_fft) // hop
+    B = stft_matrix(n_fft, win_length, normalized)
+    y = _apply_bank(rows, B.T, hop, frames)
+    return y.contiguous().reshape(wave.shape[:-1] + (frames, n_fft // 2 + 1, 2))
+
+
+def mel_spectrogram(wave: torch.Tensor, sample_rate: int = 16000, n_fft: int = 512, hop_length: int = 128, n_mels: int = 120,
+                    f_min: float = 0.0, f_max: Optional[float] = None, normalized: bool = True,
+                    log_eps: Optional[float] = None) -> torch.Tensor:
+    """`torchaudio.transforms.MelSpectrogram(sample_rate, n_fft, hop_length=hop_length, f_min=f_min, f_max=f_max, n_mels=n_mels,
+    power=2.0, normalized=normalized)` (Hann window of n_fft, centred, reflect padding, HTK mel scale, no filterbank
+    normalisation; f_max = sample_rate // 2 when None), (..., L) -> fp32 (..., n_mels, 1 + L // hop_length): `stft`, then
+    `sda_mel_power_f32` with `mel_filterbank`.  log_eps (>= 0) returns log(log_eps + mel) instead — the paper's compression with
+    1e-5 (`log_mel`).  The defaults are the paper's: 120 mel bands of a 512-point STFT every 128 samples (8 ms) at 16 kHz."""
+    spec = stft(wave, n_fft, hop_length, None, normalized, True)
+    fmax = float(int(sample_rate) // 2) if f_max is None else float(f_max)
+    fb = mel_filterbank(int(n_fft) // 2 + 1, f_min, fmax, n_mels, sample_rate)
+    return ops.mel_power(spec, torch.from_numpy(fb.astype(np.float32)).to(spec.device), log_eps)
+
+
+def log_mel(wave: torch.Tensor, sample_rate: int = 16000, n_fft: int = 512, hop_length: int = 128, n_mels: int = 120,
+            f_min: float = 0.0, f_max: Optional[float] = None, normalized: bool = True, eps: float = 1e-5) -> torch.Tensor:
+    """log(eps + mel_spectrogram(wave, ...)), the log inside the kernel: fp32 (..., n_mels, frames)."""
+    return mel_spectrogram(wave, sample_rate, n_fft, hop_length, n_mels, f_min, f_max, normalized, log_eps=eps)
+
+
+def mel_embeddings(wave: torch.Tensor, sample_rate: int, preprocs, audio_resample_rate: int = 16000) -> torch.Tensor:
+    """One audio file (1, L) at sample_rate -> float64 (n_mels, frames at brain_resample_rate): the sibling of
+    `speech_embeddings` for the log-mel representation — resample to 16 kHz (preprocs["lowpass_filter_width"]), `log_mel`,
+    FFT-resample from the frame rate audio_resample_rate / hop_length (125 Hz) to preprocs["brain_resample_rate"].  The optional
+    preprocs["mel"] = {n_mels, n_fft, hop_length, eps} overrides the paper's 120 / 512 / 128 / 1e-5 (configs/config.yaml does
+    not list the key)."""
+    _check_device(wave, "mel_embeddings")
+    if wave.dim() != 2 or wave.shape[0] != 1:
+        raise L.SdaError("mel_embeddings: a (1, L) waveform")
+    mel = dict(preprocs["mel"]) if "mel" in preprocs else {}
+    n_mels, n_fft, hop = int(mel.get("n_mels", 120)), int(mel.get("n_fft", 512)), int(mel.get("hop_length", 128))
+    wave16 = resample_audio(wave, sample_rate, audio_resample_rate, lowpass_filter_width=int(preprocs["lowpass_filter_width"]))
+    emb = log_mel(wave16, audio_resample_rate, n_fft, hop, n_mels, eps=float(mel.get("eps", 1e-5)))[0]      # (n_mels, frames)
+    return resample_fft(emb, up=preprocs["brain_resample_rate"] * hop / audio_resample_rate)
