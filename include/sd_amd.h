@@ -37,7 +37,8 @@ extern "C" {
                                   sda_clip_dz serves more than 256 speech rows (256 x 256 tiles); SDA_CONV_WIDE_TILES
                                   (still 4, additions only: sda_robust_stats / sda_robust_stats_scratch_bytes, sda_scale_clamp_rows,
                                   sda_gather_baseline_windows — the Brennan2018 input path; sda_window_gemm_f32 — FIR filter / sinc resampler;
-                                  sda_mel_power_f32 — power, mel filterbank and log behind the STFT) */
+                                  sda_mel_power_f32 — power, mel filterbank and log behind the STFT;
+                                  sda_conv_tile_co / sda_wgrad_tile_m — the output-channel tile rules, asked instead of mirrored) */
 #define SDA_ROW_PAD 16
 #define SDA_CH_ALIGN 64
 
@@ -196,6 +197,9 @@ typedef struct sda_conv_args {
 } sda_conv_args;
 int sda_conv_gemm(const sda_conv_args* a, void* stream);
 int sda_conv_n_t_tiles(int T);
+/* output-channel tile (160 / 128 / 64) of the tile-per-workgroup kernels for Cout_p channels, kernel size KS, with or without a
+ * `stats` buffer: what sda_conv_gemm dispatches on when neither SDA_CONV_FLAT_TILES nor SDA_CONV_WIDE_TILES applies.  Host only. */
+int sda_conv_tile_co(int Cout_p, int KS, int has_stats);
 /* number of [2][Cout_p] rows of `stats` a launch with these parameters writes */
 int sda_conv_stats_rows(int B, int T, int KS, int Cout_p, int flags);
 
@@ -312,6 +316,8 @@ typedef struct sda_wgrad_args {
   int flags;              /* SDA_WGRAD_FLAT_ROWS */
 } sda_wgrad_args;
 int sda_wgrad_gemm(const sda_wgrad_args* a, void* stream);
+/* output-channel (row) tile (160 / 128 / 64) sda_wgrad_gemm dispatches on for Cout_p channels.  Host only. */
+int sda_wgrad_tile_m(int Cout_p);
 /* dst[i] = sum_s src[s][i] in fixed order */
 int sda_reduce_slabs(const float* src, float* dst, int nslabs, long n, void* stream);
 /* The loss's similarity matmul (loss.py:68) on 256 x 256 output tiles, 16-bit storage (csrc/sim_gemm.hip):

@@ -673,12 +673,11 @@ static int dispatch_conv(const sda_conv_args& a, hipStream_t st) {
     return -1;
   }
   if (a.flags & SDA_EPI_GLU) { set_error("conv_gemm: SDA_EPI_GLU needs SDA_CONV_FLAT_TILES, kernel size 3 and Cout_p % 160 == 0"); return -1; }
-  // 1x1 convs whose width divides both ways (640): 128-channel tiles (conv_final1 forward 125 -> 113 us, conv_final2's data
-  // gradient 225 -> 195 us; the k = 3 convs and the statistics-row contract stay on 160)
-  if (a.KS == 1 && a.Cout_p % 128 == 0 && !a.stats) return dispatch_conv_nt<E, 128>(a, st);
-  if (a.Cout_p % 160 == 0) return dispatch_conv_nt<E, 160>(a, st);
-  if (a.Cout_p % 128 == 0) return dispatch_conv_nt<E, 128>(a, st);
-  return dispatch_conv_nt<E, 64>(a, st);
+  switch (sda_conv_tile_co(a.Cout_p, a.KS, a.stats != nullptr)) {
+    case 128: return dispatch_conv_nt<E, 128>(a, st);    // (128 before 160: the order the kernels are instantiated in, so the code object's layout)
+    case 160: return dispatch_conv_nt<E, 160>(a, st);
+    default: return dispatch_conv_nt<E, 64>(a, st);
+  }
 }
 
 }  // namespace sda
@@ -686,6 +685,13 @@ static int dispatch_conv(const sda_conv_args& a, hipStream_t st) {
 using namespace sda;
 
 extern "C" int sda_conv_n_t_tiles(int T) { return (T + TILE_T - 1) / TILE_T; }
+
+extern "C" int sda_conv_tile_co(int Cout_p, int KS, int has_stats) {
+  // 1x1 convs whose width divides both ways (640): 128-channel tiles (conv_final1 forward 125 -> 113 us, conv_final2's data
+  // gradient 225 -> 195 us; the k = 3 convs and the statistics-row contract stay on 160)
+  if (KS == 1 && Cout_p % 128 == 0 && !has_stats) return 128;
+  return Cout_p % 160 == 0 ? 160 : Cout_p % 128 == 0 ? 128 : 64;
+}
 
 extern "C" int sda_conv_gemm(const sda_conv_args* a, void* stream) {
   if (!a || !a->x || !a->w || (!a->y && !a->partial)) { set_error("conv_gemm: null argument"); return -1; }

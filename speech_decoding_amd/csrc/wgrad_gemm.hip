@@ -439,14 +439,18 @@ static int dispatch_wgrad_m(const sda_wgrad_args& a, hipStream_t st) {
 
 template <typename E>
 static int dispatch_wgrad(const sda_wgrad_args& a, hipStream_t st) {
-  if (a.Cout_p % 160 == 0) return dispatch_wgrad_m<E, 160>(a, st);
-  if (a.Cout_p % 128 == 0) return dispatch_wgrad_m<E, 128>(a, st);
-  return dispatch_wgrad_m<E, 64>(a, st);
+  switch (sda_wgrad_tile_m(a.Cout_p)) {
+    case 160: return dispatch_wgrad_m<E, 160>(a, st);
+    case 128: return dispatch_wgrad_m<E, 128>(a, st);
+    default: return dispatch_wgrad_m<E, 64>(a, st);
+  }
 }
 
 }  // namespace sda
 
 using namespace sda;
+
+extern "C" int sda_wgrad_tile_m(int Cout_p) { return Cout_p % 160 == 0 ? 160 : Cout_p % 128 == 0 ? 128 : 64; }
 
 extern "C" int sda_wgrad_gemm(const sda_wgrad_args* a, void* stream) {
   if (!a || !a->dy || !a->x || (!a->g && !a->out_e)) { set_error("wgrad_gemm: null argument"); return -1; }

@@ -88,6 +88,7 @@ SIGNATURES = {
     "sda_unpack_vector": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "sda_conv_gemm": (i32, [C.POINTER(ConvArgs), vp]),
     "sda_conv_n_t_tiles": (i32, [i32]),
+    "sda_conv_tile_co": (i32, [i32, i32, i32]),
     "sda_conv_stats_rows": (i32, [i32, i32, i32, i32, i32]),
     "sda_bn_finalize": (i32, [vp, i32, f64, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "sda_reduce_stats": (i32, [vp, i32, vp, vp, i32, vp]),
@@ -114,6 +115,7 @@ SIGNATURES = {
     "sda_gelu_backward_colsum": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "sda_colsum": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "sda_wgrad_gemm": (i32, [C.POINTER(WgradArgs), vp]),
+    "sda_wgrad_tile_m": (i32, [i32]),
     "sda_reduce_slabs": (i32, [vp, vp, i32, i64, vp]),
     "sda_sa_weights_forward": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "sda_sa_scratch_floats": (i32, [i32, i32, i32]),

@@ -497,11 +497,33 @@ class KernelTimer:
 TIMER: Optional[KernelTimer] = None
 
 
+def _launch(family: str, label, fn, a, what: str):
+    """L.check(fn(&a, stream), what): one GEMM launch.  With the kernel timer on for `family` it runs between two HIP events on the
+    CURRENT stream (the side stream in backward), recorded under label() = ((family, dtype name, tile, KS), algorithmic FLOPs)."""
+    timed = TIMER is not None and family in TIMER.families
+    if timed:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    L.check(fn(C.byref(a), _st()), what)
+    if timed:
+        e1.record()
+        TIMER.records.append((*label(), e0, e1))
+
+
 def conv_tile_co(Cout_p: int, KS: int = 3, stats: bool = False) -> int:
-    """Output-channel tile sda_conv_gemm picks (labels of the kernel timer; mirrors dispatch_conv in conv_gemm.hip)."""
-    if KS == 1 and Cout_p % 128 == 0 and not stats:
-        return 128
-    return 160 if Cout_p % 160 == 0 else (128 if Cout_p % 128 == 0 else 64)
+    """Output-channel tile of sda_conv_gemm's tile-per-workgroup kernels (the kernel timer's labels, linear_rows' ksplit)."""
+    return L.load().sda_conv_tile_co(Cout_p, KS, int(stats))
+
+
+def conv_args(x, w, y, *, B, T, Cin_p, Cout_p, KS, dil, x_pitch, w_pitch, x_rows_limit, dtype, flags=0, bias=None, res=None,
+              y_pre=None, widx=None, stats=None, bn_x=None, bn_coef=None, glu_out=None, glu_gate=None,
+              x_row0=L.ROW_PAD, x_sample_rows=None, w_rows_limit=None, ksplit=1, partial=None) -> L.ConvArgs:
+    """Every field of one sda_conv_gemm descriptor, from device addresses (ints or None), extents, pitches, flags and a dtype code.
+    Row layout (the defaults): frame t of sample b is row b * rows_tp(T) + ROW_PAD + t of x, fully padded weights, one K slice.
+    Plain matrix / view: the caller gives x_row0, x_sample_rows (from one of the B problems to the next), w_rows_limit, ksplit, partial."""
+    return L.ConvArgs(x, w, bias, res, y, y_pre, widx, stats, partial, bn_x, bn_coef, glu_out, glu_gate, B, T, Cin_p, Cout_p, KS, dil,
+                      x_pitch, w_pitch, x_row0, L.rows_tp(T) if x_sample_rows is None else x_sample_rows, x_rows_limit,
+                      Cout_p if w_rows_limit is None else w_rows_limit, ksplit, flags, dtype)   # (the struct's field order: the cheap way)
 
 
 def conv_gemm(x, w, y, *, B, T, KS, dil, bias=None, res=None, y_pre=None, widx=None, stats=None, gelu=False,
@@ -511,7 +533,6 @@ def conv_gemm(x, w, y, *, B, T, KS, dil, bias=None, res=None, y_pre=None, widx=N
     gelu_bwd_u (flat 1x1 only, SDA_EPI_GELU_BWD): y = round(conv) * GELU'(gelu_bwd_u), `stats` = per-unit column sums.
     row_sumsq (flat 1x1 only, SDA_EPI_ROW_SUMSQ): float (rows, Cout_p / 128) buffer of per-row partial sums of squares."""
     _need_cuda(x, w, y)
-    a = L.ConvArgs()
     if gelu_bwd_u is not None:
         if bn_x is not None or gelu_bwd_u.shape != y.shape or stats is None:
             raise L.SdaError("conv_gemm: gelu_bwd_u needs the shape of y and a stats buffer")
@@ -523,40 +544,29 @@ def conv_gemm(x, w, y, *, B, T, KS, dil, bias=None, res=None, y_pre=None, widx=N
             raise L.SdaError("conv_gemm: row_sumsq must be float (rows, Cout_p / 128) and excludes stats")
         flags |= L.EPI_ROW_SUMSQ
         stats = row_sumsq
-    a.x, a.w, a.bias, a.res, a.y, a.y_pre = _p(x), _p(w), _p(bias), _p(res), _p(y), _p(y_pre)
-    a.widx, a.stats, a.partial = _p(widx), _p(stats), None
-    a.bn_x, a.bn_coef = _p(bn_x), _p(bn_coef)
     glu = bool(flags & L.EPI_GLU)        # y (and y_pre = the gate) are half as wide as the conv's output channels
     Cout_p = 2 * y.shape[1] if glu else y.shape[1]
+    glu_out, glu_gate = glu_bwd if glu_bwd is not None else (None, None)
     if glu_bwd is not None:              # (out, gate) of the GLU this conv's output is the gradient of: y = [d value | d gate]
         flags |= L.EPI_GLU_BWD
         Cout_p = y.shape[1] // 2
-        if glu_bwd[0].shape[1] != Cout_p or glu_bwd[1].shape != glu_bwd[0].shape or stats is None:
+        if glu_out.shape[1] != Cout_p or glu_gate.shape != glu_out.shape or stats is None:
             raise L.SdaError("conv_gemm: glu_bwd needs (out, gate) of the conv's width and a stats buffer")
-        a.glu_out, a.glu_gate = _p(glu_bwd[0]), _p(glu_bwd[1])
-    a.B, a.T, a.Cin_p, a.Cout_p, a.KS, a.dil = B, T, x.shape[1], Cout_p, KS, dil
     if glu and (res is not None or stats is not None or bn_x is not None or (y_pre is not None and y_pre.shape != y.shape)):
         raise L.SdaError("conv_gemm: EPI_GLU takes no residual / statistics and a gate buffer of y's shape")
     if bn_x is not None and gelu_bwd_u is None and (bn_x.shape != y.shape or bn_coef is None or bn_coef.numel() != 4 * y.shape[1] or stats is None):
         raise L.SdaError("conv_gemm: bn_x needs the shape of y, a [4][Cout_p] coefficient table and a stats buffer")
     if w.shape[-1] != x.shape[1] or w.shape[-2] != Cout_p or w.shape[-3] != KS:
         raise L.SdaError(f"conv_gemm: weight {tuple(w.shape)} does not match x {tuple(x.shape)} / y {tuple(y.shape)}")
-    a.x_pitch, a.w_pitch = x.shape[1], w.shape[-1]
-    a.x_row0, a.x_sample_rows, a.x_rows_limit = L.ROW_PAD, L.rows_tp(T), x.shape[0]
     if x.shape[0] < L.rows_alloc(B, T) or y.shape[0] < L.rows_alloc(B, T):
         raise L.SdaError("conv_gemm: RL buffers too small for (B, T)")
-    a.w_rows_limit, a.ksplit = Cout_p, 1
-    a.flags, a.dtype = (L.EPI_GELU if gelu else 0) | flags, dt_code(x.dtype)
-    if TIMER is not None and "conv_gemm" in TIMER.families:
-        cin, cout = alg_dims if alg_dims is not None else (x.shape[1], y.shape[1])
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        L.check(L.load().sda_conv_gemm(C.byref(a), _st()), "conv_gemm")
-        e1.record()
-        TIMER.records.append((("conv_gemm", str(x.dtype).replace("torch.", ""), conv_tile_co(Cout_p, KS, stats is not None), KS),
-                              2.0 * B * T * KS * cin * cout, e0, e1))
-        return y
-    L.check(L.load().sda_conv_gemm(C.byref(a), _st()), "conv_gemm")
+    a = conv_args(_p(x), _p(w), _p(y), B=B, T=T, Cin_p=x.shape[1], Cout_p=Cout_p, KS=KS, dil=dil, x_pitch=x.shape[1],
+                  w_pitch=w.shape[-1], x_rows_limit=x.shape[0], dtype=dt_code(x.dtype), flags=(L.EPI_GELU if gelu else 0) | flags,
+                  bias=_p(bias), res=_p(res), y_pre=_p(y_pre), widx=_p(widx), stats=_p(stats), bn_x=_p(bn_x), bn_coef=_p(bn_coef),
+                  glu_out=_p(glu_out), glu_gate=_p(glu_gate))
+    cin, cout = alg_dims if alg_dims is not None else (x.shape[1], y.shape[1])
+    _launch("conv_gemm", lambda: (("conv_gemm", str(x.dtype).replace("torch.", ""), conv_tile_co(Cout_p, KS, stats is not None), KS),
+                                  2.0 * B * T * KS * cin * cout), L.load().sda_conv_gemm, a, "conv_gemm")
     return y
 
 
@@ -574,6 +584,10 @@ def conv_stats_rows(B: int, T: int, KS: int, Cout_p: int, flags: int = 0) -> int
 SIM_GEMM_TILES256 = True
 
 
+def k_slab(dtype) -> int:
+    return 32 if dtype == torch.float32 else 64      # Elem<E>::SLAB of sda_conv_gemm: a split-K slice is a whole number of these
+
+
 def splitk_plan(dtype, M: int, N: int, K: int, pitch: int):
     """(tiles256, ksplit) matmul_nt_splitk runs an (M x N) product over K with: sim_gemm.hip's 256 x 256 tiles (16-bit storage) or
     conv_gemm's split-K matrix mode, and the number of K slices."""
@@ -583,10 +597,8 @@ def splitk_plan(dtype, M: int, N: int, K: int, pitch: int):
         ks = L.load().sda_sim_gemm_ksplit(M, N, K, dt_code(dtype))
         if ks > 0:
             return True, ks
-    slab = 32 if dtype == torch.float32 else 64
-    nslab = K // slab
-    tile_co = 160 if Np % 160 == 0 else (128 if Np % 128 == 0 else 64)
-    tiles = ((M + 127) // 128) * (Np // tile_co)
+    nslab = K // k_slab(dtype)
+    tiles = ((M + 127) // 128) * (Np // splitk_tile_co(Np))      # (the planning count, not conv_tile_co(Np, 1): see splitk_tile_co)
     ksplit = max(1, min(nslab, (512 + tiles - 1) // tiles))
     if nslab <= 64:                 # a short contraction (SpatialAttention's weights: 2048 deep, 270 x 256 outputs): the slab sum
         ksplit = min(ksplit, 16)    # has few threads, each walking every slab — 64 slabs cost 30 us on the step's start chain
@@ -603,12 +615,8 @@ def matmul_nt_splitk_into(xm: torch.Tensor, wm: torch.Tensor, M: int, N: int, K:
     if tiles256:
         L.check(L.load().sda_sim_gemm(_p(xm), _p(wm), _p(dst), M, N, Np, K, pitch, ksplit, dt_code(xm.dtype), _st()), "sim_gemm")
     else:
-        a = L.ConvArgs()
-        a.x, a.w, a.bias, a.res, a.y, a.y_pre, a.widx, a.stats = _p(xm), _p(wm), None, None, None, None, None, None
-        a.partial = _p(dst)
-        a.B, a.T, a.Cin_p, a.Cout_p, a.KS, a.dil = 1, M, K, Np, 1, 0
-        a.x_pitch, a.w_pitch, a.x_row0, a.x_sample_rows, a.x_rows_limit = pitch, pitch, 0, 0, M
-        a.w_rows_limit, a.ksplit, a.flags, a.dtype = N, ksplit, 0, dt_code(xm.dtype)
+        a = conv_args(_p(xm), _p(wm), None, B=1, T=M, Cin_p=K, Cout_p=Np, KS=1, dil=0, x_pitch=pitch, w_pitch=pitch, x_rows_limit=M,
+                      dtype=dt_code(xm.dtype), x_row0=0, x_sample_rows=0, w_rows_limit=N, ksplit=ksplit, partial=_p(dst))
         L.check(L.load().sda_conv_gemm(C.byref(a), _st()), "conv_gemm(split-K)")
     if ksplit > 1:
         L.check(L.load().sda_reduce_slabs(_p(partial), _p(out), ksplit, M * Np, _st()), "reduce_slabs")
@@ -756,14 +764,19 @@ WGRAD_TARGET_WGS = 256      # workgroups per weight-gradient launch, split over 
 
 
 def wgrad_tile_m(Cout_p: int) -> int:
-    """Row tile sda_wgrad_gemm picks for Cout_p output channels (mirrors dispatch_wgrad in wgrad_gemm.hip)."""
-    return 160 if Cout_p % 160 == 0 else (128 if Cout_p % 128 == 0 else 64)
+    """Row tile sda_wgrad_gemm picks for Cout_p output channels."""
+    return L.load().sda_wgrad_tile_m(Cout_p)
 
 
 def wgrad_ntiles(Cout_p: int, Cin_p: int, tile_n: int = 64) -> int:
     """Output tiles of one segment AS THE CALLER'S PLANNING COUNTS THEM: row tiles x (Cin_p / tile_n).  The kernel's own column
     tile is 64 for kernel size 3 and 128 for kernel size 1 (Cin_p % 128 == 0); most call sites count 64 for both."""
     return (Cout_p // wgrad_tile_m(Cout_p)) * (Cin_p // tile_n)
+
+
+def splitk_tile_co(Np: int) -> int:
+    """Tile AS splitk_plan COUNTS IT, kept for bit-stability (it decides ksplit): at Np = 640 the kernel, conv_tile_co(Np, 1), takes 128."""
+    return 160 if Np % 160 == 0 else (128 if Np % 128 == 0 else 64)
 
 
 def uniform_segment_count(B: int, ntiles: int) -> int:
@@ -793,34 +806,32 @@ def bias_grad(cs, C, glu_half=0, glu_half_p=0):
     return unpack_vector(cs, C, glu_half, glu_half_p)
 
 
+def wgrad_args(dy, x, *, B, T, Cout_p, Cin_p, KS, dil, dy_pitch, x_pitch, rows_limit, dtype, flags=0, g=None, perm=None,
+               seg_start=None, nseg=1, row0=L.ROW_PAD, sample_rows=None, dy_zero_row=0, out_e=None, out_pitch=0, co_valid=0,
+               sub=None, rscale=None, acc_scale=None, out_scale=None) -> L.WgradArgs:
+    """Every field of one sda_wgrad_gemm descriptor, from device addresses (ints or None), extents, pitches, flags and a dtype code.
+    Slabs (the defaults): row-layout dy and x (row 0 is dy's all-zero row), one fp32 [KS][Cout_p][Cin_p] slab of g per sample segment.
+    Typed: matrices of T rows (row0 = sample_rows = 0, dy_zero_row an all-zero row of dy), co_valid scaled rows of out_e, out_pitch apart."""
+    return L.WgradArgs(dy, x, g, out_e, sub, rscale, out_scale, perm, seg_start, nseg, B, T, Cout_p, Cin_p, KS, dil, dy_pitch, x_pitch,
+                       out_pitch, row0, L.rows_tp(T) if sample_rows is None else sample_rows, rows_limit, dy_zero_row, co_valid, dtype,
+                       acc_scale, flags)                                                        # (the struct's field order: the cheap way)
+
+
 def wgrad_gemm(dy, x, *, B, T, KS, dil, perm=None, seg_start=None, nseg=1, alg_dims=None, flat_rows=False):
     """fp32 slabs (nseg, KS, Cout_p, Cin_p) of dy^T x over the RL rows of the samples in each segment.
     alg_dims = (Cin, Cout) unpadded, only used to count algorithmic FLOPs when the timer is on.
     flat_rows: the caller guarantees that dy's pad rows (the 16 rows in front of every sample) are zero — true for every
     row-layout buffer the kernels of this library write (they only ever write valid rows of zero-initialised buffers) —
     so a segment of consecutive samples is contracted as one run of rows in whole K-chunks (SDA_WGRAD_FLAT_ROWS)."""
-    a = L.WgradArgs()
     g = torch.empty((nseg, KS, dy.shape[1], x.shape[1]), dtype=torch.float32, device=x.device)
-    a.dy, a.x, a.g, a.out_e, a.sub, a.rscale, a.out_scale = _p(dy), _p(x), _p(g), None, None, None, None
-    a.perm, a.seg_start = _p(perm), _p(seg_start)
-    a.nseg, a.B, a.T, a.Cout_p, a.Cin_p, a.KS, a.dil = nseg, B, T, dy.shape[1], x.shape[1], KS, dil
-    a.dy_pitch, a.x_pitch, a.out_pitch = dy.shape[1], x.shape[1], 0
-    a.row0, a.sample_rows, a.rows_limit, a.dy_zero_row = L.ROW_PAD, L.rows_tp(T), x.shape[0], 0
-    a.co_valid, a.dtype, a.acc_scale = 0, dt_code(x.dtype), None
-    a.flags = L.WGRAD_FLAT_ROWS if flat_rows else 0      # (with `perm`: every sample as whole chunks across its own padding)
     if nseg > 1 and seg_start is None:
         raise L.SdaError("wgrad_gemm: nseg > 1 needs seg_start")
-    if TIMER is not None and "wgrad_gemm" in TIMER.families:   # events go on the CURRENT stream (the side stream in backward)
-        cin, cout = alg_dims if alg_dims is not None else (x.shape[1], dy.shape[1])
-        tile_m = wgrad_tile_m(dy.shape[1])
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        L.check(L.load().sda_wgrad_gemm(C.byref(a), _st()), "wgrad_gemm")
-        e1.record()
-        TIMER.records.append((("wgrad_gemm", str(x.dtype).replace("torch.", ""), tile_m, KS),
-                              2.0 * B * T * KS * cin * cout, e0, e1))
-        return g
-    L.check(L.load().sda_wgrad_gemm(C.byref(a), _st()), "wgrad_gemm")
+    a = wgrad_args(_p(dy), _p(x), B=B, T=T, Cout_p=dy.shape[1], Cin_p=x.shape[1], KS=KS, dil=dil, dy_pitch=dy.shape[1],
+                   x_pitch=x.shape[1], rows_limit=x.shape[0], dtype=dt_code(x.dtype), g=_p(g), perm=_p(perm), seg_start=_p(seg_start),
+                   nseg=nseg, flags=L.WGRAD_FLAT_ROWS if flat_rows else 0)   # (with `perm`: every sample as whole chunks across its own padding)
+    cin, cout = alg_dims if alg_dims is not None else (x.shape[1], dy.shape[1])
+    _launch("wgrad_gemm", lambda: (("wgrad_gemm", str(x.dtype).replace("torch.", ""), wgrad_tile_m(dy.shape[1]), KS),
+                                   2.0 * B * T * KS * cin * cout), L.load().sda_wgrad_gemm, a, "wgrad_gemm")
     return g
 
 
@@ -836,16 +847,11 @@ def reduce_slabs(slabs: torch.Tensor) -> torch.Tensor:
 def matmul_tn_typed(G, Ym, out, sub, rscale, *, M_rows, N_valid, K_cols, pitch, out_scale=None, acc_scale=None):
     """out[j][k] = out_scale * (acc_scale[j] * sum_i G[i][j] * Ym[i][k] - rscale[j] * sub[j][k])   (typed rows with `pitch`).
     G may be a column slice of a wider matrix: its row stride is the pitch read, its width the columns served."""
-    a = L.WgradArgs()
-    a.acc_scale = _p(acc_scale)
-    a.dy, a.x, a.g, a.out_e, a.sub, a.rscale, a.out_scale = _p(G), _p(Ym), None, _p(out), _p(sub), _p(rscale), _p(out_scale)
-    a.perm, a.seg_start = None, None
-    a.nseg, a.B, a.T, a.Cout_p, a.Cin_p, a.KS, a.dil = 1, 1, M_rows, G.shape[1], K_cols, 1, 0
-    a.dy_pitch, a.x_pitch, a.out_pitch = G.stride(0), pitch, pitch
     if G.shape[0] < M_rows + 1:
         raise L.SdaError("matmul_tn_typed: G needs one trailing all-zero row")
-    a.row0, a.sample_rows, a.rows_limit, a.dy_zero_row = 0, 0, M_rows, M_rows
-    a.co_valid, a.dtype = N_valid, dt_code(Ym.dtype)
+    a = wgrad_args(_p(G), _p(Ym), B=1, T=M_rows, Cout_p=G.shape[1], Cin_p=K_cols, KS=1, dil=0, dy_pitch=G.stride(0), x_pitch=pitch,
+                   rows_limit=M_rows, dtype=dt_code(Ym.dtype), row0=0, sample_rows=0, dy_zero_row=M_rows, out_e=_p(out),
+                   out_pitch=pitch, co_valid=N_valid, sub=_p(sub), rscale=_p(rscale), acc_scale=_p(acc_scale), out_scale=_p(out_scale))
     L.check(L.load().sda_wgrad_gemm(C.byref(a), _st()), "wgrad_gemm(typed)")
     return out
 
@@ -1020,16 +1026,11 @@ def gemm_view(x_ptr: int, w_ptr: int, y_ptr: int, *, rows: int, K: int, Cout_p: 
     addresses: conv_gemm with kernel size 1 in matrix mode.  Row r of x starts at x_ptr + (x_row0 + r) * x_pitch elements
     and is K elements long, so x_pitch < K gives overlapping rows (an im2col view of a strided Conv1d); w row co starts at
     w_ptr + co * w_pitch.  y rows have Cout_p elements.  The caller guarantees every address touched is allocated."""
-    a = L.ConvArgs()
-    a.x, a.w, a.bias, a.res, a.y, a.y_pre = x_ptr, w_ptr, _p(bias), res_ptr, y_ptr, None
-    a.widx, a.stats, a.partial, a.bn_x, a.bn_coef = _p(widx), None, None, None, None
-    a.B, a.T, a.Cin_p, a.Cout_p, a.KS, a.dil = batch, rows, K, Cout_p, 1, 0
-    a.x_pitch, a.w_pitch = x_pitch, w_pitch
     # `batch` independent problems of `rows` rows each, `sample_rows` view rows apart (x and y alike); widx[b] picks the
     # b-th problem's weight matrix out of w [nW][Cout_p][w_pitch]
-    a.x_row0, a.x_sample_rows, a.x_rows_limit = x_row0, (rows + L.ROW_PAD if sample_rows is None else sample_rows), x_rows_limit
-    a.w_rows_limit, a.ksplit = (Cout_p if w_rows_limit is None else w_rows_limit), 1
-    a.flags, a.dtype = (L.EPI_GELU if gelu else 0), dt_code(dtype)
+    a = conv_args(x_ptr, w_ptr, y_ptr, B=batch, T=rows, Cin_p=K, Cout_p=Cout_p, KS=1, dil=0, x_pitch=x_pitch, w_pitch=w_pitch,
+                  x_rows_limit=x_rows_limit, dtype=dt_code(dtype), flags=L.EPI_GELU if gelu else 0, bias=_p(bias), res=res_ptr,
+                  widx=_p(widx), x_row0=x_row0, x_sample_rows=sample_rows, w_rows_limit=w_rows_limit)
     L.check(L.load().sda_conv_gemm(C.byref(a), _st()), "conv_gemm(view)")
 
 
@@ -1068,26 +1069,24 @@ def w2v_mean4(a, b, c, d, T, Cc):
     return out
 
 
+def linear_rows_ksplit(T: int, Cout_p: int, Cin_p: int, dtype) -> int:
+    """K slices linear_rows cuts its contraction into (256 workgroups at the most); < 2: the direct path, no scratch."""
+    return min(Cin_p // k_slab(dtype), max(1, 256 // (n_t_tiles(T) * (Cout_p // conv_tile_co(Cout_p, 1)))))
+
+
 def linear_rows(x, w, y, T, *, bias=None, res=None, gelu=False, scratch=None):
     """y = f(x W^T + bias) + res on ONE row-layout sample of T frames (w packed (1, 1, Cout_p, Cin_p)).  Few frames make
     few output tiles (a 1024-wide layer at T = 299 is 24 workgroups): then the contraction is split over workgroups
     (sda_conv_gemm's split-K slabs) and a small epilogue kernel sums the slabs and applies bias / GELU / residual."""
     Cout_p, Cin_p = w.shape[-2], w.shape[-1]
-    tiles = ((T + 127) // 128) * (Cout_p // conv_tile_co(Cout_p, 1))
-    nslab = Cin_p // (32 if x.dtype == torch.float32 else 64)
-    ksplit = min(nslab, max(1, 256 // tiles))
+    ksplit = linear_rows_ksplit(T, Cout_p, Cin_p, x.dtype)
     if ksplit < 2:
         return conv_gemm(x, w, y, B=1, T=T, KS=1, dil=0, bias=bias, res=res, gelu=gelu)
     need = ksplit * T * Cout_p
     if scratch is None or scratch.numel() < need:
         scratch = torch.empty(need, dtype=torch.float32, device=x.device)
-    a = L.ConvArgs()
-    a.x, a.w, a.bias, a.res, a.y, a.y_pre, a.widx, a.stats = _p(x), _p(w), None, None, None, None, None, None
-    a.partial, a.bn_x, a.bn_coef = _p(scratch), None, None
-    a.B, a.T, a.Cin_p, a.Cout_p, a.KS, a.dil = 1, T, Cin_p, Cout_p, 1, 0
-    a.x_pitch, a.w_pitch = x.shape[1], Cin_p
-    a.x_row0, a.x_sample_rows, a.x_rows_limit = L.ROW_PAD, L.rows_tp(T), x.shape[0]
-    a.w_rows_limit, a.ksplit, a.flags, a.dtype = Cout_p, ksplit, 0, dt_code(x.dtype)
+    a = conv_args(_p(x), _p(w), None, B=1, T=T, Cin_p=Cin_p, Cout_p=Cout_p, KS=1, dil=0, x_pitch=x.shape[1], w_pitch=Cin_p,
+                  x_rows_limit=x.shape[0], dtype=dt_code(x.dtype), ksplit=ksplit, partial=_p(scratch))
     L.check(L.load().sda_conv_gemm(C.byref(a), _st()), "conv_gemm(split-K)")
     L.check(L.load().sda_splitk_epilogue(_p(scratch), ksplit, _p(bias), _p(res), _p(y), T, Cout_p, int(gelu), dt_code(x.dtype), _st()),
             "splitk_epilogue")

@@ -421,8 +421,7 @@ def test_split_k_partials(ops, dtype, cin, cout, T):
     wp = ops.pack_conv_weight(q(torch.randn(cout, cin, 1, generator=g) / math.sqrt(cin), dtype).to(DEV), Cop, Cip, dtype)
     bias = ops.pack_vector(torch.randn(cout, generator=g).to(DEV), Cop)
     res = rows_of(ops, q(torch.randn(1, cout, T, generator=g), dtype), dtype)
-    tiles = ((T + 127) // 128) * (Cop // ops.conv_tile_co(Cop, 1))
-    ksplit = min(Cip // (32 if dtype == torch.float32 else 64), max(1, 256 // tiles))
+    ksplit = ops.linear_rows_ksplit(T, Cop, Cip, dtype)
     assert ksplit >= 2
 
     def launch(o, s):

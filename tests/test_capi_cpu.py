@@ -51,6 +51,17 @@ def test_layout_helpers_agree_with_python_mirror(lib):
     assert L.sda_conv_n_t_tiles(360) == 3 and L.sda_conv_n_t_tiles(128) == 1
 
 
+def test_tile_rules_are_the_library_s(lib):
+    """The output-channel tile of the tile-per-workgroup kernels, asked of the library that dispatches on it (ops.conv_tile_co /
+    ops.wgrad_tile_m: timer labels, weight-gradient segment counts, linear_rows' ksplit)."""
+    from speech_decoding_amd import ops
+    for (Cout_p, KS, stats), tile in {(320, 3, 0): 160, (640, 3, 0): 160, (640, 1, 0): 128, (640, 1, 1): 160, (320, 1, 0): 160,
+                                      (256, 1, 0): 128, (1024, 3, 0): 128, (192, 3, 0): 64}.items():
+        assert lib.load().sda_conv_tile_co(Cout_p, KS, stats) == tile == ops.conv_tile_co(Cout_p, KS, bool(stats))
+    assert [lib.load().sda_wgrad_tile_m(c) for c in (320, 640, 256, 1024, 192)] == [160, 160, 128, 128, 64]
+    assert [ops.wgrad_tile_m(c) for c in (320, 640, 256, 1024, 192)] == [160, 160, 128, 128, 64]
+
+
 def test_struct_layout_matches_c(lib, tmp_path):
     """sizeof/offsetof of the two argument structs as the C compiler sees them vs the ctypes mirror."""
     src = tmp_path / "probe.c"

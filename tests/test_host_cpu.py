@@ -96,7 +96,17 @@ def test_layout_normalisation():
     assert torch.allclose(out, O.normalise_positions(raw))
 
 
-def test_uniform_and_subject_segments():
+@pytest.fixture(scope="module")
+def lib():
+    """The built library: the row tile ops.wgrad_ntiles counts with is asked of it."""
+    from speech_decoding_amd import lib as L
+    if not os.path.exists(L.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    return L
+
+
+def test_uniform_and_subject_segments(lib):
     from speech_decoding_amd import ops
     from speech_decoding_amd.engine import EncoderDims, EncoderEngine, block_dilations
     assert [block_dilations(k) for k in range(5)] == [(1, 2, 2), (4, 8, 2), (16, 1, 2), (2, 4, 2), (8, 16, 2)]
@@ -122,7 +132,6 @@ def test_uniform_and_subject_segments():
             assert ops.subject_slices(B, present, ops.wgrad_ntiles(d.D1p, d.D1p, 64)) == r_three                                 # blocks
     # where D1p is a multiple of 128 the two three-conv call sites count different column tiles, on purpose (bit-stability)
     assert ops.subject_slices(64, 1, ops.wgrad_ntiles(256, 256, 128)) == 64 and ops.subject_slices(64, 1, ops.wgrad_ntiles(256, 256, 64)) == 32
-    assert [ops.wgrad_tile_m(c) for c in (320, 640, 256, 1024, 192)] == [160, 160, 128, 128, 64]
 
 
 @pytest.mark.parametrize("S,r,B", [(27, 1, 256), (1, 26, 512), (3, 2, 8), (4, 5, 13), (2, 3, 2)])

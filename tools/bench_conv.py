@@ -37,7 +37,7 @@ def main():
                 print(f"conv {str(dtype)[6:]:8s} {cin}->{cout} k{KS} {name:28s} {us:8.1f} us  {fl/us/1e6:7.1f} TF", flush=True)
             if KS == 3 or cout == 1024:
                 dy = ops.new_rows(B, T, cout, dtype, dev); dy.normal_()
-                tile_m = 160 if cout % 160 == 0 else 128
+                tile_m = ops.wgrad_tile_m(cout)
                 ntiles = (cout // tile_m) * (cin // 64)
                 nseg = max(1, min(B, round(int(os.environ.get("WGS", 256)) / ntiles)))
                 import numpy as np
