@@ -38,6 +38,7 @@ extern "C" {
                                   (still 4, additions only: sda_robust_stats / sda_robust_stats_scratch_bytes, sda_scale_clamp_rows,
                                   sda_gather_baseline_windows — the Brennan2018 input path; sda_window_gemm_f32 — FIR filter / sinc resampler;
                                   sda_mel_power_f32 — power, mel filterbank and log behind the STFT;
+                                  sda_stft_fft_f32 — the STFT as a power-of-two FFT;
                                   sda_conv_tile_co / sda_wgrad_tile_m — the output-channel tile rules, asked instead of mirrored) */
 #define SDA_ROW_PAD 16
 #define SDA_CH_ALIGN 64
@@ -579,6 +580,23 @@ int sda_window_gemm_f32(const float* x, long x_row_stride, int rows, long frames
  * (sda_last_error) and launch nothing. */
 int sda_mel_power_f32(const float* spec, long spec_row_stride, long spec_pitch, int rows, long frames, int n_freqs,
                       const float* fb, int n_mels, float log_eps, float* out, long out_row_stride, long out_pitch, void* stream);
+
+/* ---- The STFT as a power-of-two FFT (ABI 4, addition): the alternative to sda_window_gemm_f32 with the window x DFT matrix
+ * (csrc/stft_fft.hip), for r < rows, m < frames, b < n_freqs = n_fft / 2 + 1
+ *     X[r][m][b] = sum_{k < n_fft} window[k] * x[r][m * hop + k] * exp(-2 pi i b k / n_fft)
+ *     out[r][m * out_pitch + 2 b] = Re X[r][m][b],     out[r][m * out_pitch + 2 b + 1] = Im X[r][m][b]
+ * fp32 in and out: a half-size complex transform of z[k] = y[2 k] + i y[2 k + 1], y = window * x (Stockham radix-4 passes, one
+ * radix-2 pass when log2(n_fft / 2) is odd), then the real-FFT split step.  x: rows x_row_stride elements apart, of which
+ * x[r][0 ... (frames - 1) * hop + n_fft - 1] is read and nothing else.  window: n_fft floats (normalisation and any zero padding
+ * of a shorter window folded in by the caller).  twiddle: n_fft / 2 pairs (cos(2 pi j / n_fft), -sin(2 pi j / n_fft)), j < n_fft / 2.
+ * out: rows out_row_stride elements apart, frame m at m * out_pitch; exactly the 2 * n_freqs floats of each frame are written
+ * (with out_pitch = 2 * n_freqs: the layout the window GEMM leaves and sda_mel_power_f32 reads); the imaginary parts of bin 0
+ * and of the Nyquist bin are exact zeros.  n_fft a power of two, 32 <= n_fft <= 2048; any hop, rows, frames >= 1; no alignment
+ * beyond the element's.  No atomics: the same bits on every call.  Null pointers, non-positive sizes, an unsupported n_fft,
+ * out_pitch < 2 * n_freqs, out_row_stride < (frames - 1) * out_pitch + 2 * n_freqs and x_row_stride < (frames - 1) * hop + n_fft
+ * return -1 (sda_last_error) and launch nothing. */
+int sda_stft_fft_f32(const float* x, long x_row_stride, int rows, long frames, int hop, int n_fft, const float* window,
+                     const float* twiddle, float* out, long out_row_stride, long out_pitch, void* stream);
 
 #ifdef __cplusplus
 }

@@ -149,6 +149,7 @@ SIGNATURES = {
     "sda_input_grad": (i32, [vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp]),
     "sda_window_gemm_f32": (i32, [vp, i64, i32, i64, i32, i32, vp, i32, vp, i64, vp]),
     "sda_mel_power_f32": (i32, [vp, i64, i64, i32, i64, i32, vp, i32, f32, vp, i64, i64, vp]),
+    "sda_stft_fft_f32": (i32, [vp, i64, i32, i64, i32, i32, vp, vp, vp, i64, i64, vp]),
 }
 MSE_PARTIALS = 2048      # SDA_MSE_PARTIALS: doubles of sda_mse_forward's scratch
 

@@ -1114,3 +1114,33 @@ def mel_power(spec: torch.Tensor, fb: torch.Tensor, log_eps: Optional[float] = N
                                            -1.0 if log_eps is None else float(log_eps), _p(out), n_mels * frames, frames, _st()),
                 "mel_power")
     return out
+
+
+STFT_FFT_SIZES = (32, 64, 128, 256, 512, 1024, 2048)     # the n_fft `sda_stft_fft_f32` is instantiated for
+
+
+def stft_fft_frames_per_workgroup(n_fft: int) -> int:
+    """Frames one workgroup of `sda_stft_fft_f32` owns (csrc/stft_fft.hip: SF_SAMPLES / n_fft, at most SF_MAX_FRAMES)."""
+    return min(4096 // int(n_fft), 32)
+
+
+def stft_fft(rows_padded: torch.Tensor, window: torch.Tensor, twiddle: torch.Tensor, frames: int, hop: int, n_fft: int) -> torch.Tensor:
+    """`sda_stft_fft_f32` (csrc/stft_fft.hip): rows_padded (rows, >= (frames - 1) hop + n_fft) contiguous fp32, window (n_fft,)
+    and twiddle (n_fft / 2, 2) = (cos, -sin)(2 pi j / n_fft) contiguous fp32 -> fp32 (rows, frames, n_fft / 2 + 1, 2):
+    the one-sided spectrum of window * frame, frames `hop` samples apart, in the layout `mel_power` reads."""
+    _need_cuda(rows_padded, window, twiddle)
+    n_fft, hop, frames = int(n_fft), int(hop), int(frames)
+    if n_fft not in STFT_FFT_SIZES:
+        raise L.SdaError(f"stft_fft: n_fft = {n_fft} is not one of {STFT_FFT_SIZES} (no fallback)")
+    for t in (rows_padded, window, twiddle):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise L.SdaError("stft_fft: contiguous fp32 tensors")
+    if rows_padded.dim() != 2 or tuple(window.shape) != (n_fft,) or tuple(twiddle.shape) != (n_fft // 2, 2):
+        raise L.SdaError(f"stft_fft: rows (rows, L), window (n_fft,) and twiddle (n_fft / 2, 2), got {tuple(rows_padded.shape)}, "
+                         f"{tuple(window.shape)} and {tuple(twiddle.shape)}")
+    rows, n_freqs = rows_padded.shape[0], n_fft // 2 + 1
+    out = torch.empty((rows, frames, n_freqs, 2), dtype=torch.float32, device=rows_padded.device)
+    with torch.cuda.device(rows_padded.device):
+        L.check(L.load().sda_stft_fft_f32(_p(rows_padded), rows_padded.shape[1], rows, frames, hop, n_fft, _p(window), _p(twiddle),
+                                          _p(out), frames * n_freqs * 2, n_freqs * 2, _st()), "stft_fft")
+    return out

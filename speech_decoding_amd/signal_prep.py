@@ -20,7 +20,8 @@ The second speech representation of the paper (the log-mel spectrogram of its re
 reference leaves to torchaudio on the host) is the same kernel once more: an STFT frame is the matrix window x DFT applied
 to windows hop_length apart (S = hop_length, K = n_fft, N = 2 (n_fft / 2 + 1), `stft_matrix`, `stft`), and one more kernel,
 `sda_mel_power_f32` (csrc/mel_power.hip), takes the power, applies the mel filterbank and the log and stores
-(features, frames): `mel_spectrogram`, `log_mel`, `mel_embeddings`.
+(features, frames): `mel_spectrogram`, `log_mel`, `mel_embeddings`.  With algorithm="fft" the STFT runs on a power-of-two FFT
+kernel instead, `sda_stft_fft_f32` (csrc/stft_fft.hip; `stft_window`, `fft_twiddles`); the default is the window GEMM.
 
 Parity.  Neither mne nor torchaudio can be installed next to this build, so bit-parity with `mne.filter.create_filter` and
 with `torchaudio.functional.resample` is UNPINNED: `bandpass_taps` follows mne's documented "firwin" design rule and
@@ -248,16 +249,61 @@ def speech_embeddings(embedder, wave: torch.Tensor, sample_rate: int, preprocs, 
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# log-mel speech features: the STFT on the window GEMM, then sda_mel_power_f32
+# log-mel speech features: the STFT on the window GEMM (or, algorithm="fft", on sda_stft_fft_f32), then sda_mel_power_f32
 # ---------------------------------------------------------------------------------------------------------------
 @lru_cache(maxsize=16)
-def _stft_matrix(n_fft: int, win_length: int, normalized: bool) -> np.ndarray:
+def _stft_window(n_fft: int, win_length: int) -> Tuple[np.ndarray, float]:
+    """(the zero-padded periodic Hann window, its L2 norm)"""
     if n_fft < 1 or not 1 <= win_length <= n_fft:
         raise ValueError("stft_matrix: n_fft >= 1 and 1 <= win_length <= n_fft")
     w = np.zeros(n_fft, dtype=np.float64)
     left = (n_fft - win_length) // 2
     w[left:left + win_length] = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(win_length, dtype=np.float64) / win_length)
-    c = math.sqrt(float((w * w).sum())) if normalized else 1.0
+    w.setflags(write=False)
+    return w, math.sqrt(float((w * w).sum()))
+
+
+def stft_window(n_fft: int, win_length: Optional[int] = None, normalized: bool = True) -> np.ndarray:
+    """The window of `stft_matrix` on its own, float64 (n_fft,): w / c with w the periodic Hann window of win_length zero-padded
+    to n_fft ((n_fft - win_length) // 2 on the left) and c = sqrt(sum w^2) when `normalized`, else 1 — what the FFT path
+    multiplies each frame by, so that both paths use one definition."""
+    n_fft = int(n_fft)
+    w, norm = _stft_window(n_fft, n_fft if win_length is None else int(win_length))
+    out = w / (norm if normalized else 1.0)
+    out.setflags(write=False)
+    return out
+
+
+@lru_cache(maxsize=16)
+def _fft_twiddles(n_fft: int) -> np.ndarray:
+    if n_fft < 2 or n_fft % 2:
+        raise ValueError("fft_twiddles: an even n_fft >= 2")
+    j = np.arange(n_fft // 2, dtype=np.int64)
+    # the angle reduced in integers to the first octant, as _stft_matrix reduces b k mod n_fft: j = 0 gives exactly (1, 0),
+    # j = n_fft / 4 exactly (0, -1), j = n_fft / 8 equal magnitudes (cos and sin of one and the same angle pi / 4)
+    q, r = np.divmod(8 * j, n_fft)                                      # octant q < 4, 8 j = q n_fft + r
+    odd = q % 2 == 1
+    ang = 2 * np.pi * np.where(odd, n_fft - r, r).astype(np.float64) / (8 * n_fft)      # in [0, pi / 4]
+    c, sn = np.cos(ang), np.sin(ang)
+    c[odd & (r == 0)] = sn[odd & (r == 0)] = math.sqrt(0.5)            # pi / 4 itself: libm's cos and sin differ in the last bit
+    cos = np.select([q == 0, q == 1, q == 2, q == 3], [c, sn, -sn, -c])
+    sin = np.select([q == 0, q == 1, q == 2, q == 3], [sn, c, c, sn])
+    tw = np.stack([cos, -sin], axis=1)
+    tw[tw == 0] = 0.0                                                   # no negative zeros
+    tw.setflags(write=False)
+    return tw
+
+
+def fft_twiddles(n_fft: int) -> np.ndarray:
+    """The table `sda_stft_fft_f32` takes, float64 (n_fft / 2, 2), read-only and cached: row j = (cos, -sin)(2 pi j / n_fft) =
+    exp(-2 pi i j / n_fft).  It serves the half-size complex transform (every second row) and the real-FFT split step."""
+    return _fft_twiddles(int(n_fft))
+
+
+@lru_cache(maxsize=16)
+def _stft_matrix(n_fft: int, win_length: int, normalized: bool) -> np.ndarray:
+    w, norm = _stft_window(n_fft, win_length)
+    c = norm if normalized else 1.0
     k = np.arange(n_fft, dtype=np.int64)[:, None]
     b = np.arange(n_fft // 2 + 1, dtype=np.int64)[None, :]
     ang = 2 * np.pi * ((b * k) % n_fft).astype(np.float64) / n_fft      # the angle reduced in integers: exact zeros, exact symmetry
@@ -316,15 +362,31 @@ def mel_filterbank(n_freqs: int, f_min: float, f_max: float, n_mels: int, sample
     return fb
 
 
+STFT_ALGORITHMS = ("gemm", "fft")
+
+
+def check_stft_algorithm(algorithm: str, n_fft: int) -> str:
+    """The argument check of `stft(..., algorithm=)`, which needs no device: "gemm" (any n_fft) or "fft" (the sizes
+    `sda_stft_fft_f32` is built for); anything else raises — there is no silent fallback from one to the other."""
+    if algorithm not in STFT_ALGORITHMS:
+        raise L.SdaError(f"stft: algorithm {algorithm!r} is not one of {STFT_ALGORITHMS}")
+    if algorithm == "fft" and int(n_fft) not in ops.STFT_FFT_SIZES:
+        raise L.SdaError(f"stft: algorithm 'fft' takes n_fft in {ops.STFT_FFT_SIZES}, got {n_fft} (no fallback to 'gemm')")
+    return algorithm
+
+
 def stft(wave: torch.Tensor, n_fft: int = 512, hop_length: int = 128, win_length: Optional[int] = None, normalized: bool = True,
-         center: bool = True) -> torch.Tensor:
+         center: bool = True, algorithm: str = "gemm") -> torch.Tensor:
     """`torch.stft(wave, n_fft, hop_length, win_length, window=hann_window(win_length), center=center, pad_mode="reflect",
     normalized=False, onesided=True)` divided by the window's L2 norm when `normalized` (torchaudio's Spectrogram), as real
     pairs: (..., L) -> fp32 (..., frames, n_freqs = n_fft // 2 + 1, 2) — FRAME-major, the layout the window GEMM leaves and
     `sda_mel_power_f32` reads (torch.stft returns (..., n_freqs, frames)).  center: n_fft // 2 samples of EVEN reflection per side
     (x[p], ..., x[1] | x | x[-2], ..., x[-1 - p]; not the odd extension of fir_filter), which needs L > n_fft // 2 as in torch;
     frames = 1 + L // hop_length.  Without it L >= n_fft and frames = 1 + (L - n_fft) // hop_length.  `stft_matrix` through
-    `_apply_bank`: S = hop_length, K = n_fft, N = 2 n_freqs."""
+    `_apply_bank`: S = hop_length, K = n_fft, N = 2 n_freqs.  algorithm="fft" computes the same frames with `sda_stft_fft_f32`
+    (csrc/stft_fft.hip; n_fft a power of two in 32 ... 2048) from `stft_window` and `fft_twiddles` instead: the same shape, dtype
+    and layout, values within the two paths' rounding."""
+    check_stft_algorithm(algorithm, n_fft)
     _check_device(wave, "stft")
     n_fft, hop = int(n_fft), int(hop_length)
     if n_fft < 1 or hop < 1:
@@ -339,6 +401,11 @@ def stft(wave: torch.Tensor, n_fft: int = 512, hop_length: int = 128, win_length
     elif n < n_fft:
         raise L.SdaError(f"stft: {n} samples are fewer than n_fft = {n_fft}")
     frames = 1 + (rows.shape[1] - n_fft) // hop
+    if algorithm == "fft":
+        w = ops.UPLOADER.upload("stft.window", stft_window(n_fft, win_length, normalized).astype(np.float32), rows.device)
+        tw = ops.UPLOADER.upload("stft.twiddle", fft_twiddles(n_fft).astype(np.float32), rows.device)
+        y = ops.stft_fft(rows.contiguous(), w, tw, frames, hop, n_fft)
+        return y.reshape(wave.shape[:-1] + (frames, n_fft // 2 + 1, 2))
     B = stft_matrix(n_fft, win_length, normalized)
     y = _apply_bank(rows, B.T, hop, frames)
     return y.contiguous().reshape(wave.shape[:-1] + (frames, n_fft // 2 + 1, 2))
@@ -346,35 +413,38 @@ def stft(wave: torch.Tensor, n_fft: int = 512, hop_length: int = 128, win_length
 
 def mel_spectrogram(wave: torch.Tensor, sample_rate: int = 16000, n_fft: int = 512, hop_length: int = 128, n_mels: int = 120,
                     f_min: float = 0.0, f_max: Optional[float] = None, normalized: bool = True,
-                    log_eps: Optional[float] = None) -> torch.Tensor:
+                    log_eps: Optional[float] = None, algorithm: str = "gemm") -> torch.Tensor:
     """`torchaudio.transforms.MelSpectrogram(sample_rate, n_fft, hop_length=hop_length, f_min=f_min, f_max=f_max, n_mels=n_mels,
     power=2.0, normalized=normalized)` (Hann window of n_fft, centred, reflect padding, HTK mel scale, no filterbank
     normalisation; f_max = sample_rate // 2 when None), (..., L) -> fp32 (..., n_mels, 1 + L // hop_length): `stft`, then
     `sda_mel_power_f32` with `mel_filterbank`.  log_eps (>= 0) returns log(log_eps + mel) instead — the paper's compression with
-    1e-5 (`log_mel`).  The defaults are the paper's: 120 mel bands of a 512-point STFT every 128 samples (8 ms) at 16 kHz."""
-    spec = stft(wave, n_fft, hop_length, None, normalized, True)
+    1e-5 (`log_mel`).  The defaults are the paper's: 120 mel bands of a 512-point STFT every 128 samples (8 ms) at 16 kHz.
+    `algorithm` is `stft`'s."""
+    spec = stft(wave, n_fft, hop_length, None, normalized, True, algorithm)
     fmax = float(int(sample_rate) // 2) if f_max is None else float(f_max)
     fb = mel_filterbank(int(n_fft) // 2 + 1, f_min, fmax, n_mels, sample_rate)
     return ops.mel_power(spec, torch.from_numpy(fb.astype(np.float32)).to(spec.device), log_eps)
 
 
 def log_mel(wave: torch.Tensor, sample_rate: int = 16000, n_fft: int = 512, hop_length: int = 128, n_mels: int = 120,
-            f_min: float = 0.0, f_max: Optional[float] = None, normalized: bool = True, eps: float = 1e-5) -> torch.Tensor:
+            f_min: float = 0.0, f_max: Optional[float] = None, normalized: bool = True, eps: float = 1e-5,
+            algorithm: str = "gemm") -> torch.Tensor:
     """log(eps + mel_spectrogram(wave, ...)), the log inside the kernel: fp32 (..., n_mels, frames)."""
-    return mel_spectrogram(wave, sample_rate, n_fft, hop_length, n_mels, f_min, f_max, normalized, log_eps=eps)
+    return mel_spectrogram(wave, sample_rate, n_fft, hop_length, n_mels, f_min, f_max, normalized, log_eps=eps, algorithm=algorithm)
 
 
 def mel_embeddings(wave: torch.Tensor, sample_rate: int, preprocs, audio_resample_rate: int = 16000) -> torch.Tensor:
     """One audio file (1, L) at sample_rate -> float64 (n_mels, frames at brain_resample_rate): the sibling of
     `speech_embeddings` for the log-mel representation — resample to 16 kHz (preprocs["lowpass_filter_width"]), `log_mel`,
     FFT-resample from the frame rate audio_resample_rate / hop_length (125 Hz) to preprocs["brain_resample_rate"].  The optional
-    preprocs["mel"] = {n_mels, n_fft, hop_length, eps} overrides the paper's 120 / 512 / 128 / 1e-5 (configs/config.yaml does
-    not list the key)."""
+    preprocs["mel"] = {n_mels, n_fft, hop_length, eps, algorithm} overrides the paper's 120 / 512 / 128 / 1e-5 and the STFT's
+    "gemm" (configs/config.yaml does not list the key)."""
     _check_device(wave, "mel_embeddings")
     if wave.dim() != 2 or wave.shape[0] != 1:
         raise L.SdaError("mel_embeddings: a (1, L) waveform")
     mel = dict(preprocs["mel"]) if "mel" in preprocs else {}
     n_mels, n_fft, hop = int(mel.get("n_mels", 120)), int(mel.get("n_fft", 512)), int(mel.get("hop_length", 128))
     wave16 = resample_audio(wave, sample_rate, audio_resample_rate, lowpass_filter_width=int(preprocs["lowpass_filter_width"]))
-    emb = log_mel(wave16, audio_resample_rate, n_fft, hop, n_mels, eps=float(mel.get("eps", 1e-5)))[0]      # (n_mels, frames)
+    emb = log_mel(wave16, audio_resample_rate, n_fft, hop, n_mels, eps=float(mel.get("eps", 1e-5)),
+                  algorithm=str(mel.get("algorithm", "gemm")))[0]                                             # (n_mels, frames)
     return resample_fft(emb, up=preprocs["brain_resample_rate"] * hop / audio_resample_rate)
