@@ -416,6 +416,34 @@ int sda_clip_ranks(const float* logits, const float* diag, int32_t* cnt, int Bm,
 long sda_retrieval_scores_floats(int n, int M, int chunk_cols);
 int sda_retrieval_select(const float* S, const float* qsq, const float* csq, const int64_t* labels, int64_t* indices,
                          float* scores, int32_t* ranks, int n, int M, int k, int chunk_cols, void* stream);
+/* Class-level decoding on the same matrix: the M candidates fall into C classes (words), given as a CSR index built on the
+ * host — order[M], the candidates sorted by class (ascending candidate index inside a class), and offsets[C + 1]; class c owns
+ * order[offsets[c] ... offsets[c + 1]) and may be empty.  With the logit l[i][j] = scale * score[i][j] (score as above, the
+ * product rounded once to fp32), sda_retrieval_class_reduce writes for every row i < n and class c < C
+ *     out[i * out_pitch + c] = f(i, c) - row_lse[i]
+ *     mode 0 "sum":  f = m + log sum_{j in c} exp(l[i][j] - m), m = max_{j in c} l[i][j] — the class's OWN maximum, so a class
+ *                    far below the row's best one keeps its value instead of underflowing to -inf
+ *     mode 1 "mean": the "sum" value - log(members of c)         mode 2 "max": m         an empty class: -inf in every mode
+ *     row_lse[i]   = log-sum-exp over the classes, in class order, of the "sum" values = log sum_j exp(l[i][j])
+ * so "sum" gives log-probabilities that sum to one over the classes.  Columns c >= C of a row (out_pitch >= C) are NOT written.
+ * S, qsq, csq, n, M, chunk_cols as for sda_retrieval_select.  expf / logf at full precision; every sum is taken in an order
+ * fixed by (order, offsets) alone — a class of up to 256 members by 8 adjacent lanes (lane a: members a, a + 8, ...; xor tree
+ * 4, 2, 1), a larger one by the 1024 threads of the row's workgroup (thread t: members t, t + 1024, ...; xor tree inside each
+ * wave, then the waves in order) — and there are no floating-point atomics: the same call gives the same bits.  An index of
+ * `order` outside [0, M) is clamped into the bank, offsets are clamped into [0, M]: nothing is read past the row.
+ * sda_retrieval_pool_rows pools rows that are repetitions of one item: group g owns rows[group_offsets[g] ...
+ * group_offsets[g + 1]) (the same CSR form, G groups over N rows, built on the host) and
+ *     out[g * out_pitch + c] = log( (1 / members of g) * sum_{r in g} exp(V[r * v_pitch + c]) ),   c < C,
+ * rows in list order, with the column's own maximum; a column that is -inf in every row of the group (and an empty group)
+ * gives -inf, never NaN.  Top-k and ranks over classes: sda_retrieval_select on the value matrix with M := C,
+ * chunk_cols := pad64(C) = the pitch and unit norms (v / max(1 * 1, 1e-8) is v; -inf forms a valid key and comes last).
+ * Both refuse, before any launch: null pointers, n / N, M, C, G < 1, a chunk_cols that is no positive multiple of 64, S not
+ * 16-byte aligned, a pitch below C, a scale that is not positive and finite, an unknown mode. */
+int sda_retrieval_class_reduce(const float* S, const float* qsq, const float* csq, const int32_t* order, const int32_t* offsets,
+                               float* out, float* row_lse, long out_pitch, int n, int M, int C, int chunk_cols, float scale,
+                               int mode, void* stream);
+int sda_retrieval_pool_rows(const float* V, long v_pitch, const int32_t* rows, const int32_t* group_offsets, float* out,
+                            long out_pitch, int N, int G, int C, void* stream);
 /* data parallelism: merge of the per-rank row statistics of the loss (all = the all-gathered [world][3][Bg] table of
  * (row max, row sum exp(l - max), positive's logit or 0) over each rank's block of brain columns): lse[i] = log-sum-exp of global
  * speech row i over the columns of ALL ranks, diag[i] = its positive's logit (utils/loss.py:79's two cross-entropies at the

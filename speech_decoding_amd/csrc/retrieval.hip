@@ -47,6 +47,14 @@ __device__ __forceinline__ float key_score(u64 key) {
   return __uint_as_float((b & 0x80000000u) ? (b ^ 0x80000000u) : ~b);
 }
 
+// &S[i][j] (j < M) of the chunk-major matrix: chunk j / chunk_cols, whose pitch is chunk_cols or, for the last one, pad64 of
+// what is left.  The one place that knows the layout: the selection and the class reduction both read through it.
+__device__ __forceinline__ const float* score_ptr(const float* S, int n, int M, int chunk_cols, int i, int j) {
+  const int c = j / chunk_cols, jc = j - c * chunk_cols, rem = M - c * chunk_cols;
+  const int pitch = rem >= chunk_cols ? chunk_cols : (rem + 63) / 64 * 64;
+  return S + (size_t)c * n * chunk_cols + (size_t)i * pitch + jc;
+}
+
 // descending bitonic sort of buf[0, n), n a power of two <= RS_CAP; every thread of the workgroup calls it
 __device__ inline void sort_desc(u64* buf, int n, int tid) {
   for (int size = 2; size <= n; size <<= 1) {
@@ -79,11 +87,7 @@ __global__ __launch_bounds__(RS_THREADS) void retrieval_select_kernel(
   const float qn = sqrtf(qsq[i]);
 
   // columns j .. j + 3 (j % 4 == 0, j < M) of row i; the chunk's pitch is a multiple of 64, so the 16 bytes are in the row
-  auto group_ptr = [&](int j) -> const float* {
-    const int c = j / chunk_cols, jc = j - c * chunk_cols, rem = M - c * chunk_cols;
-    const int pitch = rem >= chunk_cols ? chunk_cols : (rem + 63) / 64 * 64;
-    return S + (size_t)c * n * chunk_cols + (size_t)i * pitch + jc;
-  };
+  auto group_ptr = [&](int j) -> const float* { return score_ptr(S, n, M, chunk_cols, i, j); };
   auto load = [&](int j, Group& g) {
     g.dot = f32x4{0.f, 0.f, 0.f, 0.f};
     if (j < M) g.dot = *reinterpret_cast<const f32x4*>(group_ptr(j));
@@ -164,6 +168,208 @@ __global__ __launch_bounds__(RS_THREADS) void retrieval_select_kernel(
   if (ranks && tid == 0) ranks[i] = labelled ? *sh_rank : -1;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Class-level decoding: the bank's M candidates fall into C classes (words), given as a CSR index — order[M], the bank rows
+// sorted by class, and offsets[C + 1].  With the logit l[i][j] = scale * cosine(i, j), class c of row i gets
+//     "sum"   f = m_c + log sum_{j in c} exp(l - m_c),  m_c the class's OWN maximum      (log of its probability mass)
+//     "mean"  that minus log n_c,      "max"  m_c,      an empty class -inf
+// and the value written is f - LSE_i, LSE_i the log-sum-exp over classes of the "sum" values (= over the row's M logits).
+//
+// One workgroup of 1024 threads per query row.  Classes are dealt, CR_GROUPS at a time in class order, to groups of CR_LANES
+// adjacent lanes (word frequencies are Zipf-like: most classes have a handful of members, a wave per class would idle): lane a
+// of the group takes members a, a + CR_LANES, ... in index order, gathering S[i][order[p]] (the first CR_REG of them stay in
+// registers, so a class of up to CR_LANES * CR_REG members is gathered once; a longer one is gathered again for the second
+// pass), and the group combines its lanes' maxima and partial sums in a fixed xor tree (4, 2, 1).  A class of more than CR_BIG
+// members is left to the whole workgroup (its flag is parked in LDS; every CR_DEFER steps the workgroup meets at a barrier and takes
+// the parked classes one by one, so the steps in between run without a barrier): thread t takes members t, t + 1024, ..., combined by a xor tree inside each wave
+// (32 ... 1) and then wave 0 ... 15 in order.  Which path a class takes and where each member's term enters the sum depend on
+// (order, offsets) alone: no atomics, the same bits on every call.  LSE_i goes the workgroup's way over the C "sum" values,
+// which are parked in the row's output until it is known; "max" then walks the classes a second time for the maxima alone.
+// Measured on the MI355X (tools/bench_class_decode.py: 256 rows x 32768 candidates in 4096 Zipf-sized classes): 172 us for "sum",
+// 3 % of one read of the score block at the copy rate — the gathers are 4-byte loads at the end of a dependent chain, and a
+// median class of 2 members leaves most of its 8 lanes idle; an LDS image of the row (128 KB at this size) was not tried
+// because it bounds M.  The same pooling as a torch scatter chain takes 2.3 ms.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int CR_THREADS = 1024;
+constexpr int CR_WAVES = CR_THREADS / 64;
+constexpr int CR_LANES = 8;                        // lanes that share one class
+constexpr int CR_GROUPS = CR_THREADS / CR_LANES;   // classes in flight per step
+constexpr int CR_REG = 4;                          // members per lane kept in registers between the two passes
+constexpr int CR_BIG = 256;                        // a class above this many members is reduced by the whole workgroup
+constexpr int CR_DEFER = 64;                       // steps whose big classes are parked (flags in LDS) before the workgroup turns to them
+enum { CR_SUM = 0, CR_MEAN = 1, CR_MAX = 2 };
+
+__device__ __forceinline__ float group_max(float v) {
+#pragma unroll
+  for (int off = CR_LANES / 2; off; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int off = CR_LANES / 2; off; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+// every thread of the workgroup calls these; sh holds CR_WAVES floats
+__device__ __forceinline__ float block_max(float v, float* sh, int tid) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  __syncthreads();
+  if ((tid & 63) == 0) sh[tid >> 6] = v;
+  __syncthreads();
+  float t = sh[0];
+#pragma unroll
+  for (int w = 1; w < CR_WAVES; ++w) t = fmaxf(t, sh[w]);
+  return t;
+}
+__device__ __forceinline__ float block_sum(float v, float* sh, int tid) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
+  __syncthreads();
+  if ((tid & 63) == 0) sh[tid >> 6] = v;
+  __syncthreads();
+  float t = sh[0];
+#pragma unroll
+  for (int w = 1; w < CR_WAVES; ++w) t += sh[w];
+  return t;
+}
+
+struct ClassRow {                                  // what one workgroup reads of its query row
+  const float* S; const float* csq; const int* order; const int* offsets;
+  int n, M, C, chunk_cols, i;
+  float qn, scale;
+  // logit of the row against member p of the index; an index outside the bank is clamped into it (never read past the row)
+  __device__ __forceinline__ float logit(int p) const {
+    const int j = min(max(order[p], 0), M - 1);
+    return __fmul_rn(scale, cosine(*score_ptr(S, n, M, chunk_cols, i, j), qn, csq[j]));   // a product of its own: no FMA with l - m
+  }
+  __device__ __forceinline__ void span(int c, int& lo, int& hi) const {
+    lo = min(max(offsets[c], 0), M);
+    hi = min(max(offsets[c + 1], lo), M);
+  }
+};
+
+// row[c] = the class's "sum" value (MAXONLY: its maximum - lse) for every class c < C; all 1024 threads call it together
+template <bool MAXONLY>
+__device__ __forceinline__ void reduce_classes(const ClassRow& r, float* __restrict__ row, float lse, float* sh_red, u64* sh_mask,
+                                               int tid) {
+  const int grp = tid / CR_LANES, lane = tid % CR_LANES;
+  for (int base0 = 0; base0 < r.C; base0 += CR_DEFER * CR_GROUPS) {
+    // up to CR_DEFER steps without a barrier: the waves drift apart and hide each other's gather latency
+    for (int t = 0; t < CR_DEFER && base0 + t * CR_GROUPS < r.C; ++t) {
+      const int c = base0 + t * CR_GROUPS + grp;
+      int lo = 0, hi = 0;
+      if (c < r.C) r.span(c, lo, hi);
+      const bool big = hi - lo > CR_BIG;
+      if (big) hi = lo;                            // not this group's: see below
+      float v[CR_REG], m = -INFINITY;
+#pragma unroll
+      for (int e = 0; e < CR_REG; ++e) {
+        const int p = lo + lane + e * CR_LANES;
+        v[e] = p < hi ? r.logit(p) : -INFINITY;
+        m = fmaxf(m, v[e]);
+      }
+      for (int p = lo + lane + CR_REG * CR_LANES; p < hi; p += CR_LANES) m = fmaxf(m, r.logit(p));
+      m = group_max(m);
+      float f = m;
+      if (!MAXONLY) {
+        float s = 0.f;
+#pragma unroll
+        for (int e = 0; e < CR_REG; ++e)
+          if (lo + lane + e * CR_LANES < hi) s += expf(v[e] - m);
+        for (int p = lo + lane + CR_REG * CR_LANES; p < hi; p += CR_LANES) s += expf(r.logit(p) - m);
+        s = group_sum(s);
+        f = hi > lo ? m + logf(s) : -INFINITY;
+      }
+      if (lane == 0 && c < r.C && !big) row[c] = MAXONLY ? f - lse : f;
+      const u64 flags = __ballot(big);             // the step's big classes: the groups' flags, one ballot per wave
+      if ((tid & 63) == 0) sh_mask[t * CR_WAVES + (tid >> 6)] = flags;
+    }
+    __syncthreads();
+    // the big classes of these steps, one after the other, by everybody
+    for (int t = 0; t < CR_DEFER && base0 + t * CR_GROUPS < r.C; ++t) {
+      for (int w = 0; w < CR_WAVES; ++w) {
+        u64 mk = sh_mask[t * CR_WAVES + w] & 0x0101010101010101ull;   // lane 0 of each group
+        while (mk) {
+          const int bit = __ffsll((long long)mk) - 1;
+          mk &= mk - 1;
+          const int cb = base0 + t * CR_GROUPS + w * (64 / CR_LANES) + bit / CR_LANES;
+          int blo, bhi;
+          r.span(cb, blo, bhi);
+          const float v0 = blo + tid < bhi ? r.logit(blo + tid) : -INFINITY;
+          float bm = v0;
+          for (int p = blo + tid + CR_THREADS; p < bhi; p += CR_THREADS) bm = fmaxf(bm, r.logit(p));
+          bm = block_max(bm, sh_red, tid);
+          float bf = bm;
+          if (!MAXONLY) {
+            float s = blo + tid < bhi ? expf(v0 - bm) : 0.f;
+            for (int p = blo + tid + CR_THREADS; p < bhi; p += CR_THREADS) s += expf(r.logit(p) - bm);
+            s = block_sum(s, sh_red, tid);
+            bf = bm + logf(s);
+          }
+          if (tid == 0) row[cb] = MAXONLY ? bf - lse : bf;
+        }
+      }
+    }
+    __syncthreads();                               // everybody has read the flags before the next steps write their own
+  }
+}
+
+__global__ __launch_bounds__(CR_THREADS) void retrieval_class_reduce_kernel(
+    const float* __restrict__ S, const float* __restrict__ qsq, const float* __restrict__ csq, const int* __restrict__ order,
+    const int* __restrict__ offsets, float* __restrict__ out, float* __restrict__ row_lse, const long pitch, const int n, const int M,
+    const int C, const int chunk_cols, const float scale, const int mode) {
+  __shared__ float sh_red[CR_WAVES];
+  __shared__ u64 sh_mask[CR_DEFER * CR_WAVES];
+  const int tid = threadIdx.x, i = blockIdx.x;
+  const ClassRow r{S, csq, order, offsets, n, M, C, chunk_cols, i, sqrtf(qsq[i]), scale};
+  float* row = out + (size_t)i * pitch;
+  reduce_classes<false>(r, row, 0.f, sh_red, sh_mask, tid);
+  __syncthreads();                                 // the row's "sum" values, written by other threads, are read below
+  // LSE over classes: thread t takes classes t, t + 1024, ... in order (at least one class has a member, so F is finite)
+  float F = -INFINITY;
+  for (int c = tid; c < C; c += CR_THREADS) F = fmaxf(F, row[c]);
+  F = block_max(F, sh_red, tid);
+  float s = 0.f;
+  for (int c = tid; c < C; c += CR_THREADS) s += expf(row[c] - F);
+  s = block_sum(s, sh_red, tid);
+  const float lse = F + logf(s);
+  if (tid == 0) row_lse[i] = lse;
+  if (mode == CR_MAX) {
+    __syncthreads();                               // the last read of the "sum" values is behind everybody
+    reduce_classes<true>(r, row, lse, sh_red, sh_mask, tid);
+    return;
+  }
+  for (int c = tid; c < C; c += CR_THREADS) {      // each thread rewrites the values it has just read itself
+    float f = row[c];
+    if (mode == CR_MEAN) {
+      int lo, hi;
+      r.span(c, lo, hi);
+      f = hi > lo ? f - logf((float)(hi - lo)) : -INFINITY;
+    }
+    row[c] = f - lse;
+  }
+}
+
+// out[g][c] = log mean_{r in group g} exp(V[r][c]): the rows of group g are rows[goff[g] ... goff[g + 1]), taken in that order
+// with the column's own maximum; a column that is -inf in every row stays -inf (no -inf - -inf).  Threads run along c.
+constexpr int PR_THREADS = 256;
+__global__ __launch_bounds__(PR_THREADS) void retrieval_pool_rows_kernel(
+    const float* __restrict__ V, const long v_pitch, const int* __restrict__ rows, const int* __restrict__ goff,
+    float* __restrict__ out, const long out_pitch, const int N, const int C, const int ctiles) {
+  const int g = blockIdx.x / ctiles, c = (blockIdx.x % ctiles) * PR_THREADS + threadIdx.x;
+  if (c >= C) return;
+  const int lo = min(max(goff[g], 0), N), hi = min(max(goff[g + 1], lo), N);
+  float m = -INFINITY;
+  for (int p = lo; p < hi; ++p) m = fmaxf(m, V[(size_t)min(max(rows[p], 0), N - 1) * v_pitch + c]);
+  float res = -INFINITY;
+  if (m > -INFINITY) {
+    float s = 0.f;
+    for (int p = lo; p < hi; ++p) s += expf(V[(size_t)min(max(rows[p], 0), N - 1) * v_pitch + c] - m);
+    res = (m + logf(s)) - logf((float)(hi - lo));
+  }
+  out[(size_t)g * out_pitch + c] = res;
+}
+
 long scores_floats(int n, int M, int chunk_cols) {
   const long full = M / chunk_cols, rem = M - full * chunk_cols;
   return (long)n * (full * chunk_cols + (rem + 63) / 64 * 64);
@@ -202,4 +408,39 @@ extern "C" int sda_retrieval_select(const float* S, const float* qsq, const floa
                      reinterpret_cast<const long long*>(labels), reinterpret_cast<long long*>(indices), scores, ranks, n, M, k,
                      chunk_cols);
   return check_launch("retrieval_select");
+}
+
+extern "C" int sda_retrieval_class_reduce(const float* S, const float* qsq, const float* csq, const int32_t* order,
+                                          const int32_t* offsets, float* out, float* row_lse, long out_pitch, int n, int M, int C,
+                                          int chunk_cols, float scale, int mode, void* stream) {
+  if (!S || !qsq || !csq || !order || !offsets || !out || !row_lse) { set_error("retrieval_class_reduce: null argument"); return -1; }
+  if (n < 1 || M < 1 || M > 0x7FFF0000 || C < 1) { set_error("retrieval_class_reduce: n, C >= 1 and 1 <= M <= 0x7FFF0000"); return -1; }
+  if (chunk_cols < 64 || chunk_cols % 64 != 0) { set_error("retrieval_class_reduce: chunk_cols must be a positive multiple of 64"); return -1; }
+  if (((uintptr_t)S & 15) != 0 || (((uintptr_t)out | (uintptr_t)row_lse | (uintptr_t)qsq | (uintptr_t)csq | (uintptr_t)order | (uintptr_t)offsets) & 3) != 0) {
+    set_error("retrieval_class_reduce: the score matrix must be 16-byte aligned, every other array 4-byte aligned");
+    return -1;
+  }
+  if (out_pitch < C) { set_error("retrieval_class_reduce: out_pitch = %ld below C = %d", out_pitch, C); return -1; }
+  if (!(scale > 0.f) || !(scale <= 3.402823466e38f)) { set_error("retrieval_class_reduce: scale must be positive and finite"); return -1; }
+  if (mode != CR_SUM && mode != CR_MEAN && mode != CR_MAX) { set_error("retrieval_class_reduce: mode %d (0 sum, 1 mean, 2 max)", mode); return -1; }
+  hipLaunchKernelGGL(retrieval_class_reduce_kernel, dim3((unsigned)n), dim3(CR_THREADS), 0, (hipStream_t)stream, S, qsq, csq,
+                     reinterpret_cast<const int*>(order), reinterpret_cast<const int*>(offsets), out, row_lse, out_pitch, n, M, C,
+                     chunk_cols, scale, mode);
+  return check_launch("retrieval_class_reduce");
+}
+
+extern "C" int sda_retrieval_pool_rows(const float* V, long v_pitch, const int32_t* rows, const int32_t* group_offsets, float* out,
+                                       long out_pitch, int N, int G, int C, void* stream) {
+  if (!V || !rows || !group_offsets || !out) { set_error("retrieval_pool_rows: null argument"); return -1; }
+  if (N < 1 || G < 1 || C < 1) { set_error("retrieval_pool_rows: N, G, C >= 1"); return -1; }
+  if (v_pitch < C || out_pitch < C) { set_error("retrieval_pool_rows: a pitch below C = %d", C); return -1; }
+  if ((((uintptr_t)V | (uintptr_t)rows | (uintptr_t)group_offsets | (uintptr_t)out) & 3) != 0) {
+    set_error("retrieval_pool_rows: every array must be 4-byte aligned");
+    return -1;
+  }
+  const long ctiles = ((long)C + PR_THREADS - 1) / PR_THREADS;
+  if (ctiles * G > 0x7FFFFFFFl) { set_error("retrieval_pool_rows: G x ceil(C / %d) exceeds the grid", PR_THREADS); return -1; }
+  hipLaunchKernelGGL(retrieval_pool_rows_kernel, dim3((unsigned)(ctiles * G)), dim3(PR_THREADS), 0, (hipStream_t)stream, V, v_pitch,
+                     reinterpret_cast<const int*>(rows), reinterpret_cast<const int*>(group_offsets), out, out_pitch, N, C, (int)ctiles);
+  return check_launch("retrieval_pool_rows");
 }

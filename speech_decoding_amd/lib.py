@@ -135,6 +135,8 @@ SIGNATURES = {
     "sda_clip_ranks": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "sda_retrieval_scores_floats": (i64, [i32, i32, i32]),
     "sda_retrieval_select": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "sda_retrieval_class_reduce": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, i32, vp]),
+    "sda_retrieval_pool_rows": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, vp]),
     "sda_clip_dz_supported":(i32, [i32, i32, i64, i32]),
     "sda_clip_dz": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, i32, i32, i64, i32, vp]),
     "sda_param_gemm": (i32, [C.POINTER(PgemmArgs), vp]),

@@ -504,6 +504,15 @@ class Classifier(nn.Module):
         return retrieve(Z, bank, k=k, labels=labels)
 
     @torch.no_grad()
+    def decode_classes(self, Z: torch.Tensor, bank, classes, **kw):
+        """Word-level decoding of brain segments: the QUERIES are the brain embeddings Z (N, F, T), the CANDIDATES the speech
+        segments of `bank`, `classes` says which word each candidate is an instance of (a retrieval.ClassIndex or the M class
+        ids); returns retrieval.retrieve_classes(Z, bank, classes, **kw) — for each brain segment (or, with groups=, each group
+        of repetitions) the k most probable words and, with labels=, the rank of the one it heard."""
+        from .retrieval import retrieve_classes
+        return retrieve_classes(Z, bank, classes, **kw)
+
+    @torch.no_grad()
     def forward(self, Z: torch.Tensor, Y: torch.Tensor, test: bool = False):
         cnt = self.ranks(Z, Y).cpu().numpy()
         return float((cnt == 0).mean()), np.mean(cnt < 10)

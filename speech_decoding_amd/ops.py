@@ -1016,6 +1016,58 @@ def retrieval_select(S, qsq, csq, n: int, M: int, k: int, chunk_cols: Optional[i
     return indices, scores, (ranks if labels is not None else None)
 
 
+CLASS_MODES = {"sum": 0, "mean": 1, "max": 2}
+
+
+def retrieval_class_reduce(S, qsq, csq, order, offsets, n: int, M: int, C: int, scale: float, mode: str = "sum",
+                           chunk_cols: Optional[int] = None, out=None, row_lse=None):
+    """Class values of n query rows over the raw dot products S (chunk-major, as retrieval_select reads them): the M candidates
+    fall into C classes given as the CSR index order [M] / offsets [C + 1] (device int32) -> (out (n, pad64(C)) fp32 of which
+    columns [0, C) are written: log-sum-exp ("sum"), that minus log n_c ("mean") or the maximum ("max") of scale * cosine over
+    the class, minus the row's log-sum-exp; row_lse (n,) fp32).  See sd_amd.h.  `out` (rows of a larger matrix, any pitch >= C)
+    and `row_lse` may be handed in."""
+    _need_cuda(S, qsq, csq, order, offsets, out, row_lse)
+    if mode not in CLASS_MODES:
+        raise L.SdaError(f"retrieval_class_reduce: mode {mode!r}; one of {sorted(CLASS_MODES)}")
+    chunk_cols = L.pad_channels(M) if chunk_cols is None else chunk_cols
+    if S.dtype != torch.float32 or not S.is_contiguous() or S.numel() < retrieval_scores_floats(n, M, chunk_cols):
+        raise L.SdaError("retrieval_class_reduce: S must be a contiguous fp32 buffer of retrieval_scores_floats(n, M, chunk_cols) floats")
+    for t, cnt, name in ((qsq, n, "qsq"), (csq, M, "csq")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < cnt:
+            raise L.SdaError(f"retrieval_class_reduce: {name} must hold {cnt} contiguous fp32 values")
+    for t, cnt, name in ((order, M, "order"), (offsets, C + 1, "offsets")):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < cnt:
+            raise L.SdaError(f"retrieval_class_reduce: {name} must hold {cnt} contiguous int32 values")
+    dev = S.device
+    out = torch.empty((n, L.pad_channels(C)), dtype=torch.float32, device=dev) if out is None else out
+    row_lse = torch.empty(n, dtype=torch.float32, device=dev) if row_lse is None else row_lse
+    if (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] < n or out.shape[1] < C or out.stride(1) != 1
+            or out.stride(0) < out.shape[1]):
+        raise L.SdaError("retrieval_class_reduce: out must be n fp32 rows of at least C contiguous columns")
+    if row_lse.dtype != torch.float32 or not row_lse.is_contiguous() or row_lse.numel() < n:
+        raise L.SdaError("retrieval_class_reduce: row_lse must hold n contiguous fp32 values")
+    L.check(L.load().sda_retrieval_class_reduce(_p(S), _p(qsq), _p(csq), _p(order), _p(offsets), _p(out), _p(row_lse),
+                                                out.stride(0), n, M, C, chunk_cols, float(scale), CLASS_MODES[mode], _st()),
+            "retrieval_class_reduce")
+    return out, row_lse
+
+
+def retrieval_pool_rows(V, rows, group_offsets, N: int, G: int, C: int, out=None):
+    """out[g][c] = log mean exp of V[r][c] over the rows r of group g (rows [N] / group_offsets [G + 1], device int32: the row
+    list sorted by group, see sd_amd.h) for c < C; V (N, >= C) fp32 rows -> out (G, pad64(C)) fp32, columns >= C not written."""
+    _need_cuda(V, rows, group_offsets, out)
+    out = torch.empty((G, L.pad_channels(C)), dtype=torch.float32, device=V.device) if out is None else out
+    for t, cnt in ((V, N), (out, G)):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < cnt or t.shape[1] < C or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+            raise L.SdaError("retrieval_pool_rows: V and out must be fp32 rows of at least C contiguous columns")
+    for t, cnt, name in ((rows, N, "rows"), (group_offsets, G + 1, "group_offsets")):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < cnt:
+            raise L.SdaError(f"retrieval_pool_rows: {name} must hold {cnt} contiguous int32 values")
+    L.check(L.load().sda_retrieval_pool_rows(_p(V), V.stride(0), _p(rows), _p(group_offsets), _p(out), out.stride(0), N, G, C, _st()),
+            "retrieval_pool_rows")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # wav2vec 2.0 embedder stages (csrc/w2v2.hip) and the raw GEMM form of conv_gemm they share
 # ---------------------------------------------------------------------------------------------------------------

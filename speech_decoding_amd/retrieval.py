@@ -11,6 +11,11 @@ with no widened copy, none for an encoder's row-layout view; sda_rows_sumsq), th
 N x M score matrix is never held whole: see plan_blocks.  Which side is "query" is the caller's choice — brain segments against
 a speech bank (`Classifier.decode`) or the other way round; under torch.distributed every rank decodes its own queries
 against its own bank and no collective is issued.  No gradients: both entry points run under no_grad.
+
+Word-level decoding sits on the same blocked score matrix: a `ClassIndex` says which class (word) every candidate is an
+instance of, and `retrieve_classes` pools each row's scores per class on the device (sda_retrieval_class_reduce: a segmented
+log-sum-exp at the loss's temperature, each class with its own maximum), pools repeated queries (sda_retrieval_pool_rows) and
+runs the same selection kernel over classes instead of candidates.
 """
 from __future__ import annotations
 
@@ -130,13 +135,29 @@ def plan_blocks(N: int, M: int, K: int, dtype, scratch_bytes: int):
     multiplied once, so the GEMM work does not depend on the blocking.  mc starts at the whole bank and is halved (in multiples
     of 256, the GEMM's tile) while the K slices the GEMM would like do not fit; what still does not fit is run in fewer slices.
     The plan depends only on its arguments and the device's CU count, so one call always computes the same bits."""
+    return _plan(N, M, K, dtype, scratch_bytes, 0)
+
+
+def plan_class_blocks(N: int, M: int, C: int, K: int, dtype, scratch_bytes: int):
+    """plan_blocks for retrieve_classes: a block of nb queries holds, beside its nb x pad64(M) scores, its nb x pad64(C) class
+    values; the two together take at most half of scratch_bytes and the K slices' partial sums the rest, so
+    4 nb (pad64(M) + pad64(C)) + 4 ksplit nb mc (the last term only when ksplit > 1) <= scratch_bytes.  ValueError when one
+    query row's scores and class values do not fit twice."""
+    return _plan(N, M, K, dtype, scratch_bytes, L.pad_channels(C))
+
+
+def _plan(N: int, M: int, K: int, dtype, scratch_bytes: int, class_cols: int):
     Mp = L.pad_channels(M)
-    if scratch_bytes < 8 * Mp:
+    row = 4 * (Mp + class_cols)                  # bytes one query row holds between the GEMM and the selection
+    if scratch_bytes < 2 * row:
+        if class_cols:
+            raise ValueError(f"retrieve_classes: scratch_bytes={scratch_bytes} does not hold one query's scores over the bank "
+                             f"and its class values twice ({2 * row} bytes)")
         raise ValueError(f"retrieve: scratch_bytes={scratch_bytes} does not hold one query's scores over the bank twice ({8 * Mp} bytes)")
-    nb = min(N, scratch_bytes // 2 // (4 * Mp))
+    nb = min(N, scratch_bytes // 2 // row)
     if nb >= 256:
         nb = nb // 256 * 256
-    budget = scratch_bytes - 4 * nb * Mp
+    budget = scratch_bytes - nb * row
     mc = Mp
     if dtype == torch.float32:
         # fp32 storage runs on conv_gemm's matrix mode: a chunk's operand stays inside 2 GB, the spans that mode is run at
@@ -215,3 +236,189 @@ def retrieve(queries: torch.Tensor, bank: SpeechBank, k: int = 10, labels=None, 
         ops.retrieval_select(S, qsq[i0:], csq, n, M, k, mc, labels=None if labels is None else labels[i0:],
                              indices=indices[i0:], scores=scores[i0:], ranks=None if ranks is None else ranks[i0:])
     return Retrieval(indices, scores, ranks)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# word-level decoding: the bank's candidates fall into classes; a class's score is the softmax mass of all its instances
+# ---------------------------------------------------------------------------------------------------------------------------
+MAX_M = 0x7FFF0000  # the selection kernel's column limit
+REDUCE_MODES = ("sum", "mean", "max")
+
+
+class ClassIndex:
+    """Which class (word) each of a bank's M candidates belongs to, as the CSR index the class kernels read.  `classes`: M
+    integer class ids in bank order (list, numpy array or tensor).  Built once on the host with a stable numpy sort:
+    order (M,) int32, the bank rows sorted by class and ascending inside a class; offsets (C + 1,) int32; counts (C,) int64,
+    with C = num_classes or max id + 1.  Classes without a member are allowed.  order and offsets are uploaded to `device` the
+    first time a kernel asks for them (order_dev, offsets_dev) and stay there."""
+
+    def __init__(self, classes, num_classes: Optional[int] = None, device="cuda"):
+        arr = classes.detach().cpu().numpy() if torch.is_tensor(classes) else np.asarray(classes)
+        if arr.ndim != 1 or arr.shape[0] < 1:
+            raise ValueError("ClassIndex: classes must be M >= 1 class ids, one per bank row")
+        if arr.dtype.kind not in "iu":
+            raise ValueError(f"ClassIndex: class ids must be integers, got {arr.dtype}")
+        if arr.shape[0] > MAX_M:
+            raise ValueError(f"ClassIndex: M={arr.shape[0]} above {MAX_M:#x}")
+        if num_classes is not None and (isinstance(num_classes, bool) or int(num_classes) != num_classes or num_classes < 1):
+            raise ValueError(f"ClassIndex: num_classes={num_classes} must be a positive integer")
+        if arr.dtype.kind == "i" and (arr < 0).any():
+            raise ValueError("ClassIndex: negative class id")
+        top = int(arr.max())
+        C = top + 1 if num_classes is None else int(num_classes)
+        if top >= C:
+            raise ValueError(f"ClassIndex: class id {top} outside [0, num_classes={C})")
+        if C > MAX_M:
+            raise ValueError(f"ClassIndex: {C} classes above {MAX_M:#x}")
+        arr = arr.astype(np.int64)
+        self.M, self.C = int(arr.shape[0]), C
+        self.classes = arr
+        self.order = np.argsort(arr, kind="stable").astype(np.int32)
+        self.counts = np.bincount(arr, minlength=C).astype(np.int64)
+        self.offsets = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int32)
+        self.device = torch.device(device)
+        self._dev = None
+
+    def __len__(self) -> int:
+        return self.M
+
+    def _upload(self):
+        if self._dev is None:
+            if self.device.type != "cuda":
+                raise L.SdaError("ClassIndex: the class kernels run on the MI355X device (there is no CPU path)")
+            self._dev = (torch.from_numpy(self.order).to(self.device), torch.from_numpy(self.offsets).to(self.device))
+        return self._dev
+
+    @property
+    def order_dev(self) -> torch.Tensor:
+        return self._upload()[0]
+
+    @property
+    def offsets_dev(self) -> torch.Tensor:
+        return self._upload()[1]
+
+
+class ClassRetrieval(NamedTuple):
+    """classes (R, k) int64: the k best classes of every result row, best first (value descending, lower class id first on
+    equal values; classes without a member carry -inf and come last); log_probs (R, k) fp32: their values (log-probabilities
+    for reduce="sum"); ranks (R,) int32 or None: classes that beat the true one (0 = top-1; -1 for a device label outside
+    [0, C)); matrix (R, C) fp32 or None: the whole value matrix (return_matrix=True).  R = N, or G with groups.  All on the
+    device."""
+    classes: torch.Tensor
+    log_probs: torch.Tensor
+    ranks: Optional[torch.Tensor]
+    matrix: Optional[torch.Tensor]
+
+    def accuracy(self, k: int) -> float:
+        """Share of result rows whose true class is among the k best (reads the ranks back)."""
+        if self.ranks is None:
+            raise ValueError("ClassRetrieval.accuracy: retrieve_classes() was called without labels")
+        return float(((self.ranks >= 0) & (self.ranks < k)).float().mean())
+
+
+def _group_index(groups, N: int):
+    """groups (N ids in [0, G), every group non-empty) -> (rows (N,) int32 sorted by group, ascending inside; offsets (G + 1,))."""
+    arr = groups.detach().cpu().numpy() if torch.is_tensor(groups) else np.asarray(groups)
+    if arr.shape != (N,) or arr.dtype.kind not in "iu":
+        raise ValueError(f"retrieve_classes: groups must be {N} integer group ids")
+    if (arr < 0).any():
+        raise ValueError("retrieve_classes: negative group id")
+    arr = arr.astype(np.int64)
+    counts = np.bincount(arr)
+    if (counts == 0).any():
+        raise ValueError(f"retrieve_classes: group {int(np.argmin(counts))} has no query (groups are 0 ... G - 1, none empty)")
+    return np.argsort(arr, kind="stable").astype(np.int32), np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+
+
+@torch.no_grad()
+def retrieve_classes(queries: torch.Tensor, bank: SpeechBank, classes, k: int = 10, scale: float = 1.0, reduce: str = "sum",
+                     labels=None, groups=None, return_matrix: bool = False, scratch_bytes: int = 1 << 30) -> ClassRetrieval:
+    """Word-level decoding: score the N segments of `queries` against every candidate of `bank`, pool the scores of the
+    candidates of one class, and return the k best CLASSES of each query (ClassRetrieval).  `classes`: a ClassIndex over the
+    bank's M rows, or the M class ids themselves.  The logit of query i against candidate j is scale * cos(i, j), cos the
+    similarity retrieve() uses and `scale` a positive finite float (a trained CLIPLoss: float(loss.temp.exp())); class c gets
+        reduce="sum":  logsumexp of its members' logits (its probability mass)      "mean": that minus log n_c
+        reduce="max":  its best member's logit                                     a class without members: -inf
+    minus the log-sum-exp of the row's M logits, so "sum" returns log-probabilities that sum to one over the classes.
+    `groups` (N integer ids in [0, G), none empty, or None): queries of one group are repetitions of one item — the same
+    stimulus heard by several subjects or several times; their values are pooled as log mean exp per class and the result has
+    G rows.  Groups may be interleaved.  `labels`: the true class per result row (N, or G with groups), host (range-checked
+    here, IndexError) or device (checked by the kernel: rank -1), as in retrieve().
+    Memory: `scratch_bytes` bounds a query block's scores, its class values and the GEMM's partial sums (plan_class_blocks).
+    With `groups` or `return_matrix` the (N x pad64(C)) fp32 value matrix — and with groups the (G x pad64(C)) pooled one — is
+    held whole: that is a result-sized allocation outside the bound.  No gradients, no collective; the same call returns the
+    same bits."""
+    if not isinstance(bank, SpeechBank):
+        raise ValueError("retrieve_classes: bank must be a SpeechBank")
+    if not torch.is_tensor(queries) or queries.dim() != 3 or queries.shape[0] < 1:
+        raise ValueError("retrieve_classes: queries must be an (N, F, T) tensor with N >= 1")
+    N, F, T = queries.shape
+    if (F, T) != (bank.F, bank.T):
+        raise ValueError(f"retrieve_classes: queries are (N, {F}, {T}), the bank holds ({bank.F}, {bank.T}) segments")
+    M = len(bank)
+    if M == 0:
+        raise ValueError("retrieve_classes: the bank is empty")
+    index = classes if isinstance(classes, ClassIndex) else ClassIndex(classes, device=bank.device)
+    if index.M != M:
+        raise ValueError(f"retrieve_classes: the class index covers {index.M} candidates, the bank holds {M}")
+    C = index.C
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(MAX_K, C):
+        raise ValueError(f"retrieve_classes: k={k} outside 1 ... min({MAX_K}, C={C})")
+    k = int(k)
+    if isinstance(scale, bool) or not isinstance(scale, (int, float, np.floating)) or not 0.0 < float(scale) <= float(np.finfo(np.float32).max) \
+            or float(np.float32(scale)) == 0.0:
+        raise ValueError(f"retrieve_classes: scale={scale!r} must be a positive finite float")
+    if reduce not in REDUCE_MODES:
+        raise ValueError(f"retrieve_classes: reduce={reduce!r}; one of {REDUCE_MODES}")
+    gidx = None if groups is None else _group_index(groups, N)
+    R = N if gidx is None else len(gidx[1]) - 1
+    if labels is not None:
+        try:
+            labels = _checked_labels(labels, R, C)
+        except ValueError:
+            raise ValueError(f"retrieve_classes: labels must be {R} integer class ids") from None
+        except IndexError:
+            raise IndexError(f"retrieve_classes: label outside the classes' [0, {C})") from None
+    K = bank.row_elems
+    nb, mc, tiles256, ks = plan_class_blocks(N, M, C, K, bank.dtype, int(scratch_bytes))
+    if not queries.is_cuda:
+        raise L.SdaError("retrieve_classes: queries must live on the MI355X device (there is no CPU path)")
+    if queries.device != bank.rows.device:
+        raise L.SdaError(f"retrieve_classes: queries are on {queries.device}, the bank on {bank.rows.device}")
+    if queries.dtype not in ops.COMPUTE_DTYPES:
+        raise L.SdaError(f"retrieve_classes: queries of dtype {queries.dtype}; segments are float32, bfloat16 or float16")
+    dev = queries.device
+    order, offsets = index.order_dev, index.offsets_dev
+    if order.device != dev:
+        raise L.SdaError(f"retrieve_classes: the class index is on {order.device}, the queries on {dev}")
+    if isinstance(labels, np.ndarray):
+        labels = ops.upload_small(labels, dev)
+
+    Qt = ops.rows_of(queries, F, bank.dtype)[0].reshape(-1)
+    qsq = ops.rows_sumsq(Qt, N, K, K)
+    Bt, csq = bank.rows.reshape(-1), bank.norms_sq
+    Cp = L.pad_channels(C)
+    whole = gidx is not None or return_matrix                # the value matrix is kept: a result-sized allocation
+    S = torch.empty(ops.retrieval_scores_floats(nb, M, mc), dtype=torch.float32, device=dev)
+    partial = torch.empty(ks * nb * mc if ks > 1 else 0, dtype=torch.float32, device=dev)
+    V = torch.empty((N if whole else nb, Cp), dtype=torch.float32, device=dev)
+    row_lse = torch.empty(nb, dtype=torch.float32, device=dev)
+    ones = torch.ones(max(R if whole else nb, C), dtype=torch.float32, device=dev)      # unit norms: the selection divides by 1
+    top = torch.empty((R, k), dtype=torch.int64, device=dev)
+    vals = torch.empty((R, k), dtype=torch.float32, device=dev)
+    ranks = torch.empty(R, dtype=torch.int32, device=dev) if labels is not None else None
+    for i0 in range(0, N, nb):
+        n = min(nb, N - i0)
+        for c0 in range(0, M, mc):
+            m = min(mc, M - c0)
+            ops.matmul_nt_splitk_into(Qt[i0 * K:], Bt[c0 * K:], n, m, K, K, tiles256, ks, partial, S[(c0 // mc) * n * mc:])
+        Vb = V[i0:] if whole else V
+        ops.retrieval_class_reduce(S, qsq[i0:], csq, order, offsets, n, M, C, float(scale), reduce, mc, out=Vb, row_lse=row_lse)
+        if not whole:
+            ops.retrieval_select(V, ones, ones, n, C, k, Cp, labels=None if labels is None else labels[i0:],
+                                 indices=top[i0:], scores=vals[i0:], ranks=None if ranks is None else ranks[i0:])
+    if whole:
+        if gidx is not None:
+            V = ops.retrieval_pool_rows(V, torch.from_numpy(gidx[0]).to(dev), torch.from_numpy(gidx[1]).to(dev), N, R, C)
+        ops.retrieval_select(V, ones, ones, R, C, k, Cp, labels=labels, indices=top, scores=vals, ranks=ranks)
+    return ClassRetrieval(top, vals, ranks, V[:, :C] if return_matrix else None)
