@@ -73,6 +73,18 @@ def _need_cuda(*ts):
             raise L.SdaError("libsdamd kernels need device tensors (no CPU fallback)")
 
 
+def _need_values(t, dtype, count: int, msg: str, *said):
+    """`t` (None passes, as in _need_cuda) holds `count` contiguous values of `dtype` on the device, or SdaError(msg.format(*said))."""
+    if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.numel() < count or not t.is_cuda):
+        raise L.SdaError(msg.format(*said))
+
+
+def _need_fp32_rows(t, rows: int, C: int, msg: str):
+    """`t` is `rows` fp32 rows, any pitch, of at least C unit-stride columns, or SdaError(msg)."""
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < rows or t.shape[1] < C or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        raise L.SdaError(msg)
+
+
 def upload_small(array, device) -> torch.Tensor:
     """Host numpy array -> new device tensor without a memcpy (payload travels in kernel arguments)."""
     array = np.ascontiguousarray(array)
@@ -989,6 +1001,14 @@ def retrieval_scores_floats(n: int, M: int, chunk_cols: int) -> int:
     return r
 
 
+def _need_scores(who: str, S, qsq, csq, n: int, M: int, chunk_cols: int):
+    """The operands retrieval_select and retrieval_class_reduce share: the chunk-major scores and the two sides' norms."""
+    _need_values(S, torch.float32, retrieval_scores_floats(n, M, chunk_cols),
+                 "{}: S must be a contiguous fp32 buffer of retrieval_scores_floats(n, M, chunk_cols) floats", who)
+    for t, cnt, name in ((qsq, n, "qsq"), (csq, M, "csq")):
+        _need_values(t, torch.float32, cnt, "{}: {} must hold {} contiguous fp32 values", who, name, cnt)
+
+
 def retrieval_select(S, qsq, csq, n: int, M: int, k: int, chunk_cols: Optional[int] = None, labels=None, indices=None, scores=None,
                      ranks=None):
     """Top-k of n query rows over the raw dot products S (chunk-major, see sd_amd.h; chunk_cols None = one [n][pad64(M)] matrix)
@@ -996,21 +1016,15 @@ def retrieval_select(S, qsq, csq, n: int, M: int, k: int, chunk_cols: Optional[i
     n int64 candidate indices on the device.  The three outputs may be handed in (contiguous row blocks of larger results)."""
     _need_cuda(S, qsq, csq, labels)
     chunk_cols = L.pad_channels(M) if chunk_cols is None else chunk_cols
-    if S.dtype != torch.float32 or not S.is_contiguous() or S.numel() < retrieval_scores_floats(n, M, chunk_cols):
-        raise L.SdaError("retrieval_select: S must be a contiguous fp32 buffer of retrieval_scores_floats(n, M, chunk_cols) floats")
-    for t, cnt, name in ((qsq, n, "qsq"), (csq, M, "csq")):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < cnt:
-            raise L.SdaError(f"retrieval_select: {name} must hold {cnt} contiguous fp32 values")
-    if labels is not None and (labels.dtype != torch.int64 or not labels.is_contiguous() or labels.numel() < n):
-        raise L.SdaError("retrieval_select: labels must hold n contiguous int64 indices")
+    _need_scores("retrieval_select", S, qsq, csq, n, M, chunk_cols)
+    _need_values(labels, torch.int64, n, "retrieval_select: labels must hold n contiguous int64 indices")
     dev = S.device
     indices = torch.empty((n, k), dtype=torch.int64, device=dev) if indices is None else indices
     scores = torch.empty((n, k), dtype=torch.float32, device=dev) if scores is None else scores
     if labels is not None and ranks is None:
         ranks = torch.empty(n, dtype=torch.int32, device=dev)
     for t, dt, cnt in ((indices, torch.int64, n * k), (scores, torch.float32, n * k), (ranks, torch.int32, n)):
-        if t is not None and (t.dtype != dt or not t.is_contiguous() or t.numel() < cnt or not t.is_cuda):
-            raise L.SdaError("retrieval_select: an output buffer has the wrong dtype, size or layout")
+        _need_values(t, dt, cnt, "retrieval_select: an output buffer has the wrong dtype, size or layout")
     L.check(L.load().sda_retrieval_select(_p(S), _p(qsq), _p(csq), _p(labels), _p(indices), _p(scores),
                                           _p(ranks) if labels is not None else None, n, M, k, chunk_cols, _st()), "retrieval_select")
     return indices, scores, (ranks if labels is not None else None)
@@ -1030,22 +1044,14 @@ def retrieval_class_reduce(S, qsq, csq, order, offsets, n: int, M: int, C: int, 
     if mode not in CLASS_MODES:
         raise L.SdaError(f"retrieval_class_reduce: mode {mode!r}; one of {sorted(CLASS_MODES)}")
     chunk_cols = L.pad_channels(M) if chunk_cols is None else chunk_cols
-    if S.dtype != torch.float32 or not S.is_contiguous() or S.numel() < retrieval_scores_floats(n, M, chunk_cols):
-        raise L.SdaError("retrieval_class_reduce: S must be a contiguous fp32 buffer of retrieval_scores_floats(n, M, chunk_cols) floats")
-    for t, cnt, name in ((qsq, n, "qsq"), (csq, M, "csq")):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < cnt:
-            raise L.SdaError(f"retrieval_class_reduce: {name} must hold {cnt} contiguous fp32 values")
+    _need_scores("retrieval_class_reduce", S, qsq, csq, n, M, chunk_cols)
     for t, cnt, name in ((order, M, "order"), (offsets, C + 1, "offsets")):
-        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < cnt:
-            raise L.SdaError(f"retrieval_class_reduce: {name} must hold {cnt} contiguous int32 values")
+        _need_values(t, torch.int32, cnt, "retrieval_class_reduce: {} must hold {} contiguous int32 values", name, cnt)
     dev = S.device
     out = torch.empty((n, L.pad_channels(C)), dtype=torch.float32, device=dev) if out is None else out
     row_lse = torch.empty(n, dtype=torch.float32, device=dev) if row_lse is None else row_lse
-    if (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] < n or out.shape[1] < C or out.stride(1) != 1
-            or out.stride(0) < out.shape[1]):
-        raise L.SdaError("retrieval_class_reduce: out must be n fp32 rows of at least C contiguous columns")
-    if row_lse.dtype != torch.float32 or not row_lse.is_contiguous() or row_lse.numel() < n:
-        raise L.SdaError("retrieval_class_reduce: row_lse must hold n contiguous fp32 values")
+    _need_fp32_rows(out, n, C, "retrieval_class_reduce: out must be n fp32 rows of at least C contiguous columns")
+    _need_values(row_lse, torch.float32, n, "retrieval_class_reduce: row_lse must hold n contiguous fp32 values")
     L.check(L.load().sda_retrieval_class_reduce(_p(S), _p(qsq), _p(csq), _p(order), _p(offsets), _p(out), _p(row_lse),
                                                 out.stride(0), n, M, C, chunk_cols, float(scale), CLASS_MODES[mode], _st()),
             "retrieval_class_reduce")
@@ -1058,11 +1064,9 @@ def retrieval_pool_rows(V, rows, group_offsets, N: int, G: int, C: int, out=None
     _need_cuda(V, rows, group_offsets, out)
     out = torch.empty((G, L.pad_channels(C)), dtype=torch.float32, device=V.device) if out is None else out
     for t, cnt in ((V, N), (out, G)):
-        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < cnt or t.shape[1] < C or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
-            raise L.SdaError("retrieval_pool_rows: V and out must be fp32 rows of at least C contiguous columns")
+        _need_fp32_rows(t, cnt, C, "retrieval_pool_rows: V and out must be fp32 rows of at least C contiguous columns")
     for t, cnt, name in ((rows, N, "rows"), (group_offsets, G + 1, "group_offsets")):
-        if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < cnt:
-            raise L.SdaError(f"retrieval_pool_rows: {name} must hold {cnt} contiguous int32 values")
+        _need_values(t, torch.int32, cnt, "retrieval_pool_rows: {} must hold {} contiguous int32 values", name, cnt)
     L.check(L.load().sda_retrieval_pool_rows(_p(V), V.stride(0), _p(rows), _p(group_offsets), _p(out), out.stride(0), N, G, C, _st()),
             "retrieval_pool_rows")
     return out

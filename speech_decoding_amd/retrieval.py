@@ -12,10 +12,10 @@ N x M score matrix is never held whole: see plan_blocks.  Which side is "query" 
 a speech bank (`Classifier.decode`) or the other way round; under torch.distributed every rank decodes its own queries
 against its own bank and no collective is issued.  No gradients: both entry points run under no_grad.
 
-Word-level decoding sits on the same blocked score matrix: a `ClassIndex` says which class (word) every candidate is an
-instance of, and `retrieve_classes` pools each row's scores per class on the device (sda_retrieval_class_reduce: a segmented
-log-sum-exp at the loss's temperature, each class with its own maximum), pools repeated queries (sda_retrieval_pool_rows) and
-runs the same selection kernel over classes instead of candidates.
+Word-level decoding sits on the same blocked score matrix, filled by the same pass (`_ScorePass`: checks, pack, norms, scratch
+and block loop, written once): a `ClassIndex` says which class (word) every candidate is an instance of, and `retrieve_classes`
+pools each row's scores per class on the device (sda_retrieval_class_reduce: a segmented log-sum-exp at the loss's temperature,
+each class with its own maximum), pools repeated queries (sda_retrieval_pool_rows) and selects over classes with the same kernel.
 """
 from __future__ import annotations
 
@@ -171,18 +171,89 @@ def _plan(N: int, M: int, K: int, dtype, scratch_bytes: int, class_cols: int):
     return nb, mc, tiles256, ks
 
 
-def _checked_labels(labels, N: int, M: int):
-    """Device labels as an int64 device tensor; host labels, range-checked, as an int64 numpy array (uploaded later)."""
+def _checked_k(who: str, k, what: str = "", size: int = MAX_K) -> int:
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(MAX_K, size):
+        raise ValueError(f"{who}: k={k} outside 1 ... " + (f"min({MAX_K}, {what}={size})" if what else f"{MAX_K}"))
+    return int(k)
+
+
+def _checked_labels(who: str, labels, N: int, size: int, noun: str, whose: str):
+    """Device labels as an int64 device tensor; host labels, range-checked, as an int64 numpy array (uploaded later).  `noun`
+    ("bank indices" / "class ids") and `whose` ("the bank's" / "the classes'") word the caller's messages."""
     if torch.is_tensor(labels) and labels.is_cuda:
         if labels.dim() != 1 or labels.shape[0] != N or labels.dtype.is_floating_point or labels.dtype == torch.bool:
-            raise ValueError(f"retrieve: labels must be {N} integer bank indices")
-        return labels.to(torch.int64).contiguous()          # checked by the kernel: a value outside the bank gives rank -1
+            raise ValueError(f"{who}: labels must be {N} integer {noun}")
+        return labels.to(torch.int64).contiguous()          # checked by the kernel: a value outside [0, size) gives rank -1
     arr = labels.detach().numpy() if torch.is_tensor(labels) else np.asarray(labels)
     if arr.shape != (N,) or arr.dtype.kind not in "iu":
-        raise ValueError(f"retrieve: labels must be {N} integer bank indices")
-    if (arr < 0).any() or (arr >= M).any():
-        raise IndexError(f"retrieve: label outside the bank's [0, {M})")
+        raise ValueError(f"{who}: labels must be {N} integer {noun}")
+    if (arr < 0).any() or (arr >= size).any():
+        raise IndexError(f"{who}: label outside {whose} [0, {size})")
     return arr.astype(np.int64)
+
+
+class _ScorePass:
+    """The blocked score pass under retrieve and retrieve_classes (`who`: the name in every message), in the order both keep:
+    __init__ checks the shared arguments and the caller then its own and its plan (ValueError, nothing is touched); on_device
+    refuses what the kernels cannot read (SdaError); start touches the device first: host labels go up, the queries are packed,
+    their norms taken, the scratch allocated; blocks() fills S with one block of queries' scores after the other."""
+
+    def __init__(self, who: str, queries: torch.Tensor, bank: SpeechBank, k=None):
+        if not isinstance(bank, SpeechBank):
+            raise ValueError(f"{who}: bank must be a SpeechBank")
+        if not torch.is_tensor(queries) or queries.dim() != 3 or queries.shape[0] < 1:
+            raise ValueError(f"{who}: queries must be an (N, F, T) tensor with N >= 1")
+        N, F, T = queries.shape
+        if (F, T) != (bank.F, bank.T):
+            raise ValueError(f"{who}: queries are (N, {F}, {T}), the bank holds ({bank.F}, {bank.T}) segments")
+        if k is not None:                                   # retrieve holds k to MAX_K before it looks at the bank's size
+            self.k = _checked_k(who, k)
+        if len(bank) == 0:
+            raise ValueError(f"{who}: the bank is empty")
+        self.who, self.queries, self.bank = who, queries, bank
+        self.N, self.F, self.M, self.K = N, F, len(bank), bank.row_elems
+
+    def on_device(self) -> torch.device:
+        who, queries = self.who, self.queries
+        if not queries.is_cuda:
+            raise L.SdaError(f"{who}: queries must live on the MI355X device (there is no CPU path)")
+        if queries.device != self.bank.rows.device:
+            raise L.SdaError(f"{who}: queries are on {queries.device}, the bank on {self.bank.rows.device}")
+        if queries.dtype not in ops.COMPUTE_DTYPES:
+            raise L.SdaError(f"{who}: queries of dtype {queries.dtype}; segments are float32, bfloat16 or float16")
+        return queries.device
+
+    def start(self, plan, labels=None):
+        """Takes the (nb, mc, tiles256, ksplit) of plan_blocks / plan_class_blocks; returns the labels as the kernels read them."""
+        self.nb, self.mc, self.tiles256, self.ks = nb, mc, _, ks = plan
+        N, K, bank, dev = self.N, self.K, self.bank, self.queries.device
+        if isinstance(labels, np.ndarray):
+            labels = ops.upload_small(labels, dev)
+        self.Qt = ops.rows_of(self.queries, self.F, bank.dtype)[0].reshape(-1)
+        self.qsq = ops.rows_sumsq(self.Qt, N, K, K)
+        self.Bt, self.csq = bank.rows.reshape(-1), bank.norms_sq
+        self.S = torch.empty(ops.retrieval_scores_floats(nb, self.M, mc), dtype=torch.float32, device=dev)
+        self.partial = torch.empty(ks * nb * mc if ks > 1 else 0, dtype=torch.float32, device=dev)
+        return labels
+
+    def chunk(self, c0: int, n: int) -> torch.Tensor:
+        """S from an n-row block's scores against bank row c0 (a multiple of mc) on.  S is chunk-major, one [n][pad64(m)] matrix
+        per chunk of m bank rows: this offset and score_ptr in csrc/retrieval.hip are the two places that say so."""
+        mc = self.mc
+        return self.S[(c0 // mc) * n * mc:]
+
+    def fill(self, i0: int = 0) -> int:
+        """Fill S with the raw dot products of queries i0 ... i0 + n - 1 against the whole bank, one GEMM per chunk; returns n."""
+        M, K, mc, Qt, Bt = self.M, self.K, self.mc, self.Qt, self.Bt
+        n = min(self.nb, self.N - i0)
+        for c0 in range(0, M, mc):
+            ops.matmul_nt_splitk_into(Qt[i0 * K:], Bt[c0 * K:], n, min(mc, M - c0), K, K, self.tiles256, self.ks, self.partial, self.chunk(c0, n))
+        return n
+
+    def blocks(self):
+        """(i0, n) of every block of queries in turn, S filled for it."""
+        for i0 in range(0, self.N, self.nb):
+            yield i0, self.fill(i0)
 
 
 @torch.no_grad()
@@ -192,48 +263,19 @@ def retrieve(queries: torch.Tensor, bank: SpeechBank, k: int = 10, labels=None, 
     whole bank.  Labels on the host are checked here (IndexError); labels on the device are checked by the kernel, which
     reports -1 for one outside the bank, because nothing is read back: the results are device tensors.  `scratch_bytes`
     bounds the temporary memory (plan_blocks); the same call with the same arguments returns the same bits."""
-    if not isinstance(bank, SpeechBank):
-        raise ValueError("retrieve: bank must be a SpeechBank")
-    if not torch.is_tensor(queries) or queries.dim() != 3 or queries.shape[0] < 1:
-        raise ValueError("retrieve: queries must be an (N, F, T) tensor with N >= 1")
-    N, F, T = queries.shape
-    if (F, T) != (bank.F, bank.T):
-        raise ValueError(f"retrieve: queries are (N, {F}, {T}), the bank holds ({bank.F}, {bank.T}) segments")
-    if isinstance(k, bool) or int(k) != k or not 1 <= k <= MAX_K:
-        raise ValueError(f"retrieve: k={k} outside 1 ... {MAX_K}")
-    M, k = len(bank), int(k)
-    if M == 0:
-        raise ValueError("retrieve: the bank is empty")
-    if k > M:
-        raise ValueError(f"retrieve: k={k} outside 1 ... min({MAX_K}, M={M})")
+    sp = _ScorePass("retrieve", queries, bank, k)
+    N, M = sp.N, sp.M
+    k = _checked_k("retrieve", sp.k, "M", M)
     if labels is not None:
-        labels = _checked_labels(labels, N, M)
-    K = bank.row_elems
-    nb, mc, tiles256, ks = plan_blocks(N, M, K, bank.dtype, int(scratch_bytes))
-    if not queries.is_cuda:
-        raise L.SdaError("retrieve: queries must live on the MI355X device (there is no CPU path)")
-    if queries.device != bank.rows.device:
-        raise L.SdaError(f"retrieve: queries are on {queries.device}, the bank on {bank.rows.device}")
-    if queries.dtype not in ops.COMPUTE_DTYPES:
-        raise L.SdaError(f"retrieve: queries of dtype {queries.dtype}; segments are float32, bfloat16 or float16")
-    dev = queries.device
-    if isinstance(labels, np.ndarray):
-        labels = ops.upload_small(labels, dev)
-
-    Qt = ops.rows_of(queries, F, bank.dtype)[0].reshape(-1)
-    qsq = ops.rows_sumsq(Qt, N, K, K)
-    Bt, csq = bank.rows.reshape(-1), bank.norms_sq
-    S = torch.empty(ops.retrieval_scores_floats(nb, M, mc), dtype=torch.float32, device=dev)
-    partial = torch.empty(ks * nb * mc if ks > 1 else 0, dtype=torch.float32, device=dev)
+        labels = _checked_labels("retrieve", labels, N, M, "bank indices", "the bank's")
+    plan = plan_blocks(N, M, sp.K, bank.dtype, int(scratch_bytes))
+    dev = sp.on_device()
+    labels = sp.start(plan, labels)
     indices = torch.empty((N, k), dtype=torch.int64, device=dev)
     scores = torch.empty((N, k), dtype=torch.float32, device=dev)
     ranks = torch.empty(N, dtype=torch.int32, device=dev) if labels is not None else None
-    for i0 in range(0, N, nb):
-        n = min(nb, N - i0)
-        for c0 in range(0, M, mc):
-            m = min(mc, M - c0)
-            ops.matmul_nt_splitk_into(Qt[i0 * K:], Bt[c0 * K:], n, m, K, K, tiles256, ks, partial, S[(c0 // mc) * n * mc:])
-        ops.retrieval_select(S, qsq[i0:], csq, n, M, k, mc, labels=None if labels is None else labels[i0:],
+    for i0, n in sp.blocks():
+        ops.retrieval_select(sp.S, sp.qsq[i0:], sp.csq, n, M, k, sp.mc, labels=None if labels is None else labels[i0:],
                              indices=indices[i0:], scores=scores[i0:], ranks=None if ranks is None else ranks[i0:])
     return Retrieval(indices, scores, ranks)
 
@@ -348,23 +390,13 @@ def retrieve_classes(queries: torch.Tensor, bank: SpeechBank, classes, k: int = 
     With `groups` or `return_matrix` the (N x pad64(C)) fp32 value matrix — and with groups the (G x pad64(C)) pooled one — is
     held whole: that is a result-sized allocation outside the bound.  No gradients, no collective; the same call returns the
     same bits."""
-    if not isinstance(bank, SpeechBank):
-        raise ValueError("retrieve_classes: bank must be a SpeechBank")
-    if not torch.is_tensor(queries) or queries.dim() != 3 or queries.shape[0] < 1:
-        raise ValueError("retrieve_classes: queries must be an (N, F, T) tensor with N >= 1")
-    N, F, T = queries.shape
-    if (F, T) != (bank.F, bank.T):
-        raise ValueError(f"retrieve_classes: queries are (N, {F}, {T}), the bank holds ({bank.F}, {bank.T}) segments")
-    M = len(bank)
-    if M == 0:
-        raise ValueError("retrieve_classes: the bank is empty")
+    sp = _ScorePass("retrieve_classes", queries, bank)
+    N, M = sp.N, sp.M
     index = classes if isinstance(classes, ClassIndex) else ClassIndex(classes, device=bank.device)
     if index.M != M:
         raise ValueError(f"retrieve_classes: the class index covers {index.M} candidates, the bank holds {M}")
     C = index.C
-    if isinstance(k, bool) or int(k) != k or not 1 <= k <= min(MAX_K, C):
-        raise ValueError(f"retrieve_classes: k={k} outside 1 ... min({MAX_K}, C={C})")
-    k = int(k)
+    k = _checked_k("retrieve_classes", k, "C", C)
     if isinstance(scale, bool) or not isinstance(scale, (int, float, np.floating)) or not 0.0 < float(scale) <= float(np.finfo(np.float32).max) \
             or float(np.float32(scale)) == 0.0:
         raise ValueError(f"retrieve_classes: scale={scale!r} must be a positive finite float")
@@ -373,47 +405,24 @@ def retrieve_classes(queries: torch.Tensor, bank: SpeechBank, classes, k: int = 
     gidx = None if groups is None else _group_index(groups, N)
     R = N if gidx is None else len(gidx[1]) - 1
     if labels is not None:
-        try:
-            labels = _checked_labels(labels, R, C)
-        except ValueError:
-            raise ValueError(f"retrieve_classes: labels must be {R} integer class ids") from None
-        except IndexError:
-            raise IndexError(f"retrieve_classes: label outside the classes' [0, {C})") from None
-    K = bank.row_elems
-    nb, mc, tiles256, ks = plan_class_blocks(N, M, C, K, bank.dtype, int(scratch_bytes))
-    if not queries.is_cuda:
-        raise L.SdaError("retrieve_classes: queries must live on the MI355X device (there is no CPU path)")
-    if queries.device != bank.rows.device:
-        raise L.SdaError(f"retrieve_classes: queries are on {queries.device}, the bank on {bank.rows.device}")
-    if queries.dtype not in ops.COMPUTE_DTYPES:
-        raise L.SdaError(f"retrieve_classes: queries of dtype {queries.dtype}; segments are float32, bfloat16 or float16")
-    dev = queries.device
+        labels = _checked_labels("retrieve_classes", labels, R, C, "class ids", "the classes'")
+    plan = plan_class_blocks(N, M, C, sp.K, bank.dtype, int(scratch_bytes))
+    dev = sp.on_device()
     order, offsets = index.order_dev, index.offsets_dev
     if order.device != dev:
         raise L.SdaError(f"retrieve_classes: the class index is on {order.device}, the queries on {dev}")
-    if isinstance(labels, np.ndarray):
-        labels = ops.upload_small(labels, dev)
-
-    Qt = ops.rows_of(queries, F, bank.dtype)[0].reshape(-1)
-    qsq = ops.rows_sumsq(Qt, N, K, K)
-    Bt, csq = bank.rows.reshape(-1), bank.norms_sq
-    Cp = L.pad_channels(C)
+    labels = sp.start(plan, labels)
+    nb, Cp = sp.nb, L.pad_channels(C)
     whole = gidx is not None or return_matrix                # the value matrix is kept: a result-sized allocation
-    S = torch.empty(ops.retrieval_scores_floats(nb, M, mc), dtype=torch.float32, device=dev)
-    partial = torch.empty(ks * nb * mc if ks > 1 else 0, dtype=torch.float32, device=dev)
     V = torch.empty((N if whole else nb, Cp), dtype=torch.float32, device=dev)
     row_lse = torch.empty(nb, dtype=torch.float32, device=dev)
     ones = torch.ones(max(R if whole else nb, C), dtype=torch.float32, device=dev)      # unit norms: the selection divides by 1
     top = torch.empty((R, k), dtype=torch.int64, device=dev)
     vals = torch.empty((R, k), dtype=torch.float32, device=dev)
     ranks = torch.empty(R, dtype=torch.int32, device=dev) if labels is not None else None
-    for i0 in range(0, N, nb):
-        n = min(nb, N - i0)
-        for c0 in range(0, M, mc):
-            m = min(mc, M - c0)
-            ops.matmul_nt_splitk_into(Qt[i0 * K:], Bt[c0 * K:], n, m, K, K, tiles256, ks, partial, S[(c0 // mc) * n * mc:])
+    for i0, n in sp.blocks():
         Vb = V[i0:] if whole else V
-        ops.retrieval_class_reduce(S, qsq[i0:], csq, order, offsets, n, M, C, float(scale), reduce, mc, out=Vb, row_lse=row_lse)
+        ops.retrieval_class_reduce(sp.S, sp.qsq[i0:], sp.csq, order, offsets, n, M, C, float(scale), reduce, sp.mc, out=Vb, row_lse=row_lse)
         if not whole:
             ops.retrieval_select(V, ones, ones, n, C, k, Cp, labels=None if labels is None else labels[i0:],
                                  indices=top[i0:], scores=vals[i0:], ranks=None if ranks is None else ranks[i0:])

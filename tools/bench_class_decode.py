@@ -55,7 +55,7 @@ def measure(a):
     import numpy as np
     import torch
     from speech_decoding_amd import ClassIndex, SpeechBank, retrieve, retrieve_classes, lib as L, ops
-    from speech_decoding_amd.retrieval import plan_class_blocks
+    from speech_decoding_amd.retrieval import _ScorePass, plan_class_blocks
     dev = "cuda:0"
     dt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[a.dtype]
     N, M, C, F, T, k, scale = a.N, a.M, a.C, a.F, a.T, a.k, a.scale
@@ -75,14 +75,9 @@ def measure(a):
     del first
     K = bank.row_elems
     nb, mc, tiles256, ks = plan_class_blocks(N, M, C, K, dt, a.scratch)
-    n = min(nb, N)
-    Qt = ops.rows_of(queries, F, dt)[0].reshape(-1)
-    qsq = ops.rows_sumsq(Qt, N, K, K)
-    Bt, csq = bank.rows.reshape(-1), bank.norms_sq
-    S = torch.empty(ops.retrieval_scores_floats(n, M, mc), dtype=torch.float32, device=dev)
-    partial = torch.empty(ks * n * mc if ks > 1 else 0, dtype=torch.float32, device=dev)
-    for c0 in range(0, M, mc):
-        ops.matmul_nt_splitk_into(Qt, Bt[c0 * K:], n, min(mc, M - c0), K, K, tiles256, ks, partial, S[(c0 // mc) * n * mc:])
+    sp = _ScorePass("bench_class_decode", queries, bank)      # retrieve_classes()'s own pack, norms, scratch and block fill
+    sp.start((nb, mc, tiles256, ks))
+    n, qsq, csq, S = sp.fill(), sp.qsq, sp.csq, sp.S          # the first block's scores
     Cp, Mp = L.pad_channels(C), L.pad_channels(M)
     order, offsets = index.order_dev, index.offsets_dev
     V = torch.empty((n, Cp), dtype=torch.float32, device=dev)
@@ -119,7 +114,7 @@ def measure(a):
         for c0 in range(0, M, mc):
             m = min(mc, M - c0)
             mp = L.pad_channels(m)
-            dense[:, c0: c0 + m] = S[(c0 // mc) * n * mc:][: n * mp].view(n, mp)[:, :m]
+            dense[:, c0: c0 + m] = sp.chunk(c0, n)[: n * mp].view(n, mp)[:, :m]
     cls = torch.from_numpy(ids).to(dev)[None, :].expand(n, M).contiguous()
 
     def ours_chain():

@@ -42,7 +42,7 @@ def timed(fns, iters, warmup, reps=1):
 def one_size(a, M):
     import torch
     from speech_decoding_amd import SpeechBank, retrieve, lib as L, ops
-    from speech_decoding_amd.retrieval import plan_blocks
+    from speech_decoding_amd.retrieval import _ScorePass, plan_blocks
     dev = "cuda:0"
     dt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[a.dtype]
     N, F, T, k = a.N, a.F, a.T, a.k
@@ -65,19 +65,10 @@ def one_size(a, M):
     build_rows = M - min(batch, M)
     K = bank.row_elems
     nb, mc, tiles256, ks = plan_blocks(N, M, K, dt, a.scratch)
-    n = min(nb, N)
-    Qt = ops.new_rows(N, T, L.pad_channels(F), dt, dev)
-    ops.pack_rows(queries, Qt)
-    Qt = Qt.reshape(-1)
-    qsq = ops.rows_sumsq(Qt, N, K, K)
-    Bt, csq = bank.rows.reshape(-1), bank.norms_sq
-    S = torch.empty(ops.retrieval_scores_floats(n, M, mc), dtype=torch.float32, device=dev)
-    partial = torch.empty(ks * n * mc if ks > 1 else 0, dtype=torch.float32, device=dev)
-
-    def gemm():
-        for c0 in range(0, M, mc):
-            ops.matmul_nt_splitk_into(Qt, Bt[c0 * K:], n, min(mc, M - c0), K, K, tiles256, ks, partial, S[(c0 // mc) * n * mc:])
-
+    sp = _ScorePass("bench_retrieval", queries, bank)         # retrieve()'s own pack, norms, scratch and block fill
+    sp.start((nb, mc, tiles256, ks))
+    Qt, qsq, csq, S, gemm = sp.Qt, sp.qsq, sp.csq, sp.S, sp.fill      # gemm(): the first block's scores, one GEMM per chunk
+    n = gemm()
     Qm, Bm = Qt[: n * K].view(n, K), bank.rows
 
     def torch_gemm():
@@ -94,7 +85,7 @@ def one_size(a, M):
         for c0 in range(0, M, mc):
             m = min(mc, M - c0)
             mp = L.pad_channels(m)
-            plain.view(n, Mp)[:, c0: c0 + m] = S[(c0 // mc) * n * mc:][: n * mp].view(n, mp)[:, :m]
+            plain.view(n, Mp)[:, c0: c0 + m] = sp.chunk(c0, n)[: n * mp].view(n, mp)[:, :m]
     dense = plain.view(n, Mp)
     lab = labels[:n].contiguous()
     out = {}
