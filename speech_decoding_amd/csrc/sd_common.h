@@ -347,3 +347,12 @@ bool first_use_on_device(unsigned long long& done);
 int launch_cus();
 
 }  // namespace sda
+
+// Run CALL with E = the storage element of `dtype`; an unknown dtype is the entry point's error (it returns -1).
+#define SDA_DISPATCH(dtype, CALL)                                             \
+  do {                                                                        \
+    if ((dtype) == SDA_F32) { using E = float; CALL; }                        \
+    else if ((dtype) == SDA_BF16) { using E = uint16_t; CALL; }               \
+    else if ((dtype) == SDA_F16) { using E = sda::half_t; CALL; }             \
+    else { sda::set_error("unknown dtype %d", (int)(dtype)); return -1; }     \
+  } while (0)

@@ -339,14 +339,6 @@ __global__ void mean4_kernel(const E* __restrict__ a, const E* __restrict__ b, c
 
 using namespace sda;
 
-#define SDA_DISPATCH(dtype, CALL)                                   \
-  do {                                                              \
-    if ((dtype) == SDA_F32) { using E = float; CALL; }              \
-    else if ((dtype) == SDA_BF16) { using E = uint16_t; CALL; }     \
-    else if ((dtype) == SDA_F16) { using E = half_t; CALL; }        \
-    else { set_error("unknown dtype %d", (int)(dtype)); return -1; } \
-  } while (0)
-
 static inline int grid_for(long n, int per_block) {
   long g = (n + per_block - 1) / per_block;
   return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));

@@ -676,7 +676,10 @@ def bn_gelu_backward(dy, x, mean, rstd, gamma, beta, dx, B, T, scratch, count=No
     """Returns (dgamma, dbeta) summed over `count` rows (global sums when `allreduce` is given) and fills dx.
     tile_stats: per-tile (sum dg, sum dg*xhat) already produced by the conv that wrote dy (conv_gemm(bn_x=...));
     without it the sums take a pass of their own over dy and x."""
+    if dy_is_dg and tile_stats is None:
+        raise L.SdaError("bn_gelu_backward: dy_is_dg needs the statistics rows of the conv that wrote dg")
     Cp = x.shape[1]
+    n = float(count if count is not None else B * T)
     sums = torch.empty((2, Cp), dtype=torch.float32, device=x.device)
     dgamma, dbeta = sums[0], sums[1]
     lib = L.load()
@@ -684,7 +687,7 @@ def bn_gelu_backward(dy, x, mean, rstd, gamma, beta, dx, B, T, scratch, count=No
         coef = torch.empty(6 * Cp, dtype=torch.float32, device=x.device)
         fn = lib.sda_bn_gelu_backward_from_stats_dg if dy_is_dg else lib.sda_bn_gelu_backward_from_stats
         L.check(fn(_p(tile_stats), tile_stats.shape[0], _p(dy), _p(x), _p(mean), _p(rstd),
-                                                    _p(gamma), _p(beta), gamma.numel(), float(count if count is not None else B * T),
+                                                    _p(gamma), _p(beta), gamma.numel(), n,
                                                     _p(dgamma), _p(dbeta), _p(coef), _p(dx), B, T, Cp, dt_code(x.dtype), _st()),
                 "bn_gelu_backward_from_stats")
         return dgamma, dbeta
@@ -696,11 +699,9 @@ def bn_gelu_backward(dy, x, mean, rstd, gamma, beta, dx, B, T, scratch, count=No
     if allreduce is not None:
         allreduce(sums)
     coef = torch.empty(6 * Cp, dtype=torch.float32, device=x.device)
-    if dy_is_dg and tile_stats is None:
-        raise L.SdaError("bn_gelu_backward: dy_is_dg needs the statistics rows of the conv that wrote dg")
     fn = lib.sda_bn_gelu_backward_apply_dg if dy_is_dg else lib.sda_bn_gelu_backward_apply
     L.check(fn(_p(dy), _p(x), _p(mean), _p(rstd), _p(gamma), _p(beta), gamma.numel(), _p(dgamma),
-                                           _p(dbeta), float(count if count is not None else B * T), _p(coef), _p(dx), B, T, Cp,
+                                           _p(dbeta), n, _p(coef), _p(dx), B, T, Cp,
                                            dt_code(x.dtype), _st()), "bn_gelu_backward_apply")
     return dgamma, dbeta
 

@@ -1,4 +1,5 @@
 """Inputs, float64 references, tolerances and plain-torch emulations for the kernel-level tests of csrc/elementwise.hip
+(the streaming, column-sum and norm passes) and csrc/param_ops.hip (vector maps, slab reduce / unpack, Adam)
 (tests/test_elementwise_cpu.py proves on the CPU that the cases catch planted bugs, tests/test_elementwise_gpu.py holds the
 HIP kernels to the same comparisons).  Nothing here needs a GPU; every comparison helper works on tensors of any device.
 

@@ -1,5 +1,6 @@
 """Kernel-level tests of csrc/elementwise.hip on a real MI355X: BatchNorm finalize / apply (+GELU), GLU, GELU backward, the
-column sums, the slab reduce / unpack of the weight gradients, the per-sample norms and the fused Adam, each launched directly in
+column sums and the per-sample norms; and of csrc/param_ops.hip: the vector maps, the slab reduce / unpack of the weight
+gradients and the fused Adam; each launched directly in
 fp32, bf16 and fp16 and held to float64 on the operands as the kernel reads them.  Inputs, references and tolerances (each with
 its derivation) are in tests/elementwise_cases.py; tests/test_elementwise_cpu.py shows that these cases catch 21 planted bugs.
 

@@ -134,6 +134,17 @@ def test_uniform_and_subject_segments(lib):
     assert ops.subject_slices(64, 1, ops.wgrad_ntiles(256, 256, 128)) == 64 and ops.subject_slices(64, 1, ops.wgrad_ntiles(256, 256, 64)) == 32
 
 
+def test_bn_gelu_backward_refuses_dg_without_statistics_before_any_launch(lib):
+    """dy_is_dg without the statistics rows is refused on the arguments alone: no device, no stream lookup, no launch."""
+    from speech_decoding_amd import ops
+    B, T, Cp = 2, 5, 64
+    rows = torch.zeros(B * (T + 16) + 16 + 160, Cp)
+    vec = torch.ones(Cp)
+    with pytest.raises(lib.SdaError) as err:
+        ops.bn_gelu_backward(rows, rows, vec, vec, vec, vec, rows.clone(), B, T, torch.zeros(2 * Cp), tile_stats=None, dy_is_dg=True)
+    assert str(err.value) == "bn_gelu_backward: dy_is_dg needs the statistics rows of the conv that wrote dg"
+
+
 @pytest.mark.parametrize("S,r,B", [(27, 1, 256), (1, 26, 512), (3, 2, 8), (4, 5, 13), (2, 3, 2)])
 def test_subject_segments_partition_the_batch_slice_major(S, r, B):
     """Per-subject weight-gradient segments: every sample appears once, segment j*S + s holds only subject s,
