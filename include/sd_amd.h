@@ -39,7 +39,9 @@ extern "C" {
                                   sda_gather_baseline_windows — the Brennan2018 input path; sda_window_gemm_f32 — FIR filter / sinc resampler;
                                   sda_mel_power_f32 — power, mel filterbank and log behind the STFT;
                                   sda_stft_fft_f32 — the STFT as a power-of-two FFT;
-                                  sda_conv_tile_co / sda_wgrad_tile_m — the output-channel tile rules, asked instead of mirrored) */
+                                  sda_conv_tile_co / sda_wgrad_tile_m — the output-channel tile rules, asked instead of mirrored;
+                                  sda_sim_gemm_windows / sda_sim_gemm_windows_span / sda_window_sumsq — decoding against windows of
+                                  continuous speech tracks) */
 #define SDA_ROW_PAD 16
 #define SDA_CH_ALIGN 64
 
@@ -330,6 +332,27 @@ int sda_reduce_slabs(const float* src, float* dst, int nslabs, long n, void* str
 int sda_sim_gemm_ksplit(int M, int N, long K, int dtype);
 int sda_sim_gemm(const void* X, const void* W, float* partial, int M, int N, int Np, long K, long pitch, int ksplit, int dtype,
                  void* stream);
+/* The same product against WINDOWS of a table of plain rows (decoding against continuous speech tracks, retrieval.WindowBank):
+ *     partial[ks][i][j] = sum_{k in K slice ks} X[i][k] * table[starts[j] * row_elems + k],   i < M, j < Np, ks < ksplit
+ * Candidate j is the K = T * row_elems elements from table row starts[j] on, so candidates that overlap share their bytes.
+ * X: M rows x_pitch elements apart (x_pitch >= K, x_pitch % 8 == 0); table: rows of row_elems (% 64 == 0) elements; starts:
+ * N device int32 table rows; base_row: the smallest of them — the kernel addresses a candidate as the wave-uniform base
+ * table + base_row * row_elems plus a 32-bit byte offset, so the CALLER (who holds the starts on the host) guarantees
+ *     0 <= starts[j] - base_row <= sda_sim_gemm_windows_span(row_elems)        for every j < N
+ * and that every window lies inside the table; a start that breaks the first promise is clamped into it (a wrong score, no
+ * wrapped address).  Reads stay inside the windows named by starts[0, N): columns past N repeat the last candidate and are
+ * don't-care in [N, Np).  16-bit storage only: there is no fp32 window path.  Tiles, K slices (sda_sim_gemm_ksplit(M, N, K))
+ * and the slab sum (sda_reduce_slabs) are sda_sim_gemm's.  Refused before any launch: null pointers, fp32, K % 32, row_elems
+ * % 64, x_pitch < K or % 8, Np < N or % 4, ksplit outside [1, K / 32], base_row < 0, X / table / partial not 16-byte aligned. */
+int sda_sim_gemm_windows(const void* X, long x_pitch, const void* table, const int32_t* starts, int base_row, long row_elems,
+                         float* partial, int M, int N, int Np, long K, int ksplit, int dtype, void* stream);
+/* largest starts[j] - base_row one sda_sim_gemm_windows launch serves (0: row_elems is not a positive multiple of 64).  Host only. */
+long sda_sim_gemm_windows_span(long row_elems);
+/* Squared norms of such windows from the per-row sums of the table (row_sq[l] = sum of squares of table row l, fp32:
+ * sda_rows_sumsq over rows of row_elems elements):  out[m] = sum_{t < T} row_sq[starts[m] + t],  m < M.  One wavefront per
+ * candidate: lane l adds t = l, l + 64, ... in order, then the xor butterfly (sda_gather_baseline_windows' order): no atomics,
+ * the same bits on every call.  The caller guarantees starts[m] + T <= rows of row_sq.  Null pointers, M < 1, T < 1 refused. */
+int sda_window_sumsq(const float* row_sq, const int32_t* starts, float* out, int M, int T, void* stream);
 
 /* SpatialAttention weights (models.py:49-58 with SpatialDropout 81-84 folded in):
  * a = Re(z) cos + Im(z) sin; W = softmax_c(a); Wd = W * mask.  z is complex64 interleaved (re, im).

@@ -370,6 +370,21 @@ __global__ __launch_bounds__(PR_THREADS) void retrieval_pool_rows_kernel(
   out[(size_t)g * out_pitch + c] = res;
 }
 
+// Squared norm of candidate m of a windowed bank (retrieval.WindowBank): the T per-row sums from table row starts[m] on.  One
+// wavefront per candidate, in the fixed order of gather_baseline_windows_kernel (robust_rows.hip): lane l adds rows l, l + 64,
+// ... in order, then the butterfly, so a candidate's norm does not depend on its neighbours or on the call.
+__global__ __launch_bounds__(256) void window_sumsq_kernel(const float* __restrict__ row_sq, const int* __restrict__ starts,
+                                                           float* __restrict__ out, const int M, const int T) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const long m = (long)blockIdx.x * 4 + wid;
+  if (m >= M) return;
+  const float* w = row_sq + max(starts[m], 0);
+  float s = 0.f;
+  for (int t = lane; t < T; t += 64) s += w[t];
+  s = wave_sum(s);
+  if (lane == 0) out[m] = s;
+}
+
 long scores_floats(int n, int M, int chunk_cols) {
   const long full = M / chunk_cols, rem = M - full * chunk_cols;
   return (long)n * (full * chunk_cols + (rem + 63) / 64 * 64);
@@ -443,4 +458,13 @@ extern "C" int sda_retrieval_pool_rows(const float* V, long v_pitch, const int32
   hipLaunchKernelGGL(retrieval_pool_rows_kernel, dim3((unsigned)(ctiles * G)), dim3(PR_THREADS), 0, (hipStream_t)stream, V, v_pitch,
                      reinterpret_cast<const int*>(rows), reinterpret_cast<const int*>(group_offsets), out, out_pitch, N, C, (int)ctiles);
   return check_launch("retrieval_pool_rows");
+}
+
+extern "C" int sda_window_sumsq(const float* row_sq, const int32_t* starts, float* out, int M, int T, void* stream) {
+  if (!row_sq || !starts || !out) { set_error("window_sumsq: null argument"); return -1; }
+  if (M < 1 || T < 1) { set_error("window_sumsq: M, T >= 1"); return -1; }
+  if ((((uintptr_t)row_sq | (uintptr_t)starts | (uintptr_t)out) & 3) != 0) { set_error("window_sumsq: every array must be 4-byte aligned"); return -1; }
+  hipLaunchKernelGGL(window_sumsq_kernel, dim3((unsigned)(((long)M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, row_sq,
+                     reinterpret_cast<const int*>(starts), out, M, T);
+  return check_launch("window_sumsq");
 }

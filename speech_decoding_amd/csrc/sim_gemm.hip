@@ -38,10 +38,31 @@ constexpr int SG_PPW = 4;                          // 1 KB pieces per wave and s
 // The K-step runs on v_mfma_f32_32x32x16 (sd_common.h, mma32): per wave 4 (j) x 2 (i) blocks of 32 x 32, two MFMAs each per
 // K-step; the 64-byte rows' swizzle is then chunk ^ ((row >> 2) & 3) — a 16-lane service group of ds_read_b128 (conv_tile.h)
 // holds the row quads {0, 3, 5, 6} or {1, 2, 4, 7} of ONE chunk.
-template <typename E, int NS>
+//
+// WIN = true is the windowed form (sda_sim_gemm_windows): row j of the second operand is not W + j * pitch but the window of a
+// table of plain rows that starts at row starts[j], W + starts[j] * row_elems, so neighbouring candidates share their bytes.
+// Only the W-side piece offsets differ: ((starts[min(n0 + r, N - 1)] - base_row) * row_elems + swizzled chunk) * sizeof(E),
+// computed once like the others and relative to the wave-uniform base W + base_row * row_elems (base_row: the smallest start
+// of the launch, so the offsets are not negative; the caller refuses a chunk whose largest one does not fit 32 bits, and a
+// start that breaks either promise is clamped to the nearest one that keeps it: a wrong score, never a wrapped offset).  The
+// tile's column offset n0 goes into the lookup, not into the base.  X keeps its own pitch (`pitch` is then X's alone).  The
+// plain form's SimWindows is empty, so its instructions are the ones it had as a kernel of its own.  No address outside the windows
+// named by `starts` is formed: a row past N reads the LAST candidate's window (the clamp the plain form has), the K loop adds
+// k < K to a window's first element, and starts[] itself is read at indices [0, N) only.
+template <bool WIN>
+struct SimWindows {                                // the windowed form's extra kernel arguments
+  const int* starts;
+  int base_row, rel_max;
+  long row_elems;
+};
+template <>
+struct SimWindows<false> {};
+
+template <typename E, int NS, bool WIN = false>
 __global__ __launch_bounds__(512, 2) void sim_gemm_kernel(const E* __restrict__ X, const E* __restrict__ W, float* __restrict__ partial,
                                                            const int M, const int N, const int Np, const long pitch, const int nslab,
-                                                           const int ksplit, const int m_tiles, const int n_tiles) {
+                                                           const int ksplit, const int m_tiles, const int n_tiles,
+                                                           const SimWindows<WIN> win) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int SLAB = ROW_B / (int)sizeof(E);     // 32 elements per K-step
   constexpr int PER16 = Elem<E>::PER16;
@@ -80,12 +101,14 @@ __global__ __launch_bounds__(512, 2) void sim_gemm_kernel(const E* __restrict__ 
     const int sw = (pchunk ^ ((r >> 2) & 3)) * PER16;
     const long xr = min((long)r, (long)(M - 1 - m0)), wr = min((long)r, (long)(N - 1 - n0));      // clamped: never stored
     xoff[h] = (uint32_t)((xr * pitch + sw) * (long)sizeof(E));
-    woff[h] = (uint32_t)((wr * pitch + sw) * (long)sizeof(E));
+    if constexpr (WIN) woff[h] = (uint32_t)(((long)min(max(win.starts[n0 + wr] - win.base_row, 0), win.rel_max) * win.row_elems + sw) * (long)sizeof(E));
+    else woff[h] = (uint32_t)((wr * pitch + sw) * (long)sizeof(E));
   }
   const uint32_t lds_base = __builtin_amdgcn_readfirstlane(lds_addr(smem));
   // wave-uniform bases of K-step s_begin (scalar arithmetic on kernel arguments and the block index only)
   const E* xs = X + (size_t)m0 * pitch + (size_t)s_begin * SLAB;
   const E* ws = W + (size_t)n0 * pitch + (size_t)s_begin * SLAB;
+  if constexpr (WIN) ws = W + (size_t)win.base_row * win.row_elems + (size_t)s_begin * SLAB;
   // this wave's four pieces of the slab `xs` / `ws` point at, into stage `buf`; j selects the piece (compile-time in the callers)
   auto issue = [&](int buf, int j) {
     const uint32_t dst = lds_base + buf * SG_STAGE + (wid + 8 * (j & 1)) * 1024;
@@ -180,12 +203,33 @@ int launch_sim_ns(const void* X, const void* W, float* partial, int M, int N, in
   const int nslab = (int)(K / (ROW_B / (long)sizeof(E)));
   const long grid = (long)m_tiles * n_tiles * ksplit;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, st, reinterpret_cast<const E*>(X), reinterpret_cast<const E*>(W),
-                     partial, M, N, Np, pitch, nslab, ksplit, m_tiles, n_tiles);
+                     partial, M, N, Np, pitch, nslab, ksplit, m_tiles, n_tiles, SimWindows<false>{});
   return check_launch("sim_gemm");
 }
 template <typename E>
 int launch_sim(const void* X, const void* W, float* partial, int M, int N, int Np, long K, long pitch, int ksplit, hipStream_t st) {
   return launch_sim_ns<E, SG_NS>(X, W, partial, M, N, Np, K, pitch, ksplit, st);
+}
+
+template <typename E>
+int launch_sim_windows(const void* X, long x_pitch, const void* table, const int32_t* starts, int base_row, long row_elems, float* partial,
+                       int M, int N, int Np, long K, int ksplit, hipStream_t st) {
+  constexpr int lds = SG_NS * SG_STAGE;
+  static unsigned long long attr_done = 0;        // per device
+  auto kern = sim_gemm_kernel<E, SG_NS, true>;
+  if (first_use_on_device(attr_done)) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+      set_error("sim_gemm_windows: cannot reserve %d bytes of LDS", lds);
+      return -3;
+    }
+  }
+  const int m_tiles = (M + SG_TILE - 1) / SG_TILE, n_tiles = (N + SG_TILE - 1) / SG_TILE;
+  const int nslab = (int)(K / (ROW_B / (long)sizeof(E)));
+  const long grid = (long)m_tiles * n_tiles * ksplit;
+  const SimWindows<true> win{reinterpret_cast<const int*>(starts), base_row, (int)sda_sim_gemm_windows_span(row_elems), row_elems};
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, st, reinterpret_cast<const E*>(X), reinterpret_cast<const E*>(table),
+                     partial, M, N, Np, x_pitch, nslab, ksplit, m_tiles, n_tiles, win);
+  return check_launch("sim_gemm_windows");
 }
 
 }  // namespace
@@ -218,4 +262,27 @@ extern "C" int sda_sim_gemm(const void* X, const void* W, float* partial, int M,
   hipStream_t st = (hipStream_t)stream;
   return dtype == SDA_BF16 ? launch_sim<uint16_t>(X, W, partial, M, N, Np, K, pitch, ksplit, st)
                            : launch_sim<half_t>(X, W, partial, M, N, Np, K, pitch, ksplit, st);
+}
+
+extern "C" int sda_sim_gemm_windows(const void* X, long x_pitch, const void* table, const int32_t* starts, int base_row, long row_elems,
+                                    float* partial, int M, int N, int Np, long K, int ksplit, int dtype, void* stream) {
+  if (!X || !table || !starts || !partial) { set_error("sim_gemm_windows: null argument"); return -1; }
+  if (dtype != SDA_BF16 && dtype != SDA_F16) { set_error("sim_gemm_windows: 16-bit storage only (there is no fp32 window path)"); return -1; }
+  if (M < 1 || N < 1 || K < 32 || K % 32 != 0 || x_pitch < K || x_pitch % 8 != 0) { set_error("sim_gemm_windows: K must be whole 64-byte K-steps, rows of X 16-byte aligned and x_pitch >= K"); return -1; }
+  if (row_elems < 64 || row_elems % 64 != 0 || base_row < 0) { set_error("sim_gemm_windows: table rows are a positive multiple of 64 elements, base_row >= 0"); return -1; }
+  if (Np < N || Np % 4 != 0) { set_error("sim_gemm_windows: the padded width must cover N in whole 16-byte groups"); return -1; }
+  if (ksplit < 1 || ksplit > K / 32) { set_error("sim_gemm_windows: ksplit out of range"); return -1; }
+  if ((long)SG_TILE * x_pitch * 2 >= (1L << 32)) { set_error("sim_gemm_windows: a 256-row tile of X spans more than 4 GB"); return -1; }
+  if ((((uintptr_t)X | (uintptr_t)table | (uintptr_t)partial) & 15) != 0 || ((uintptr_t)starts & 3) != 0) { set_error("sim_gemm_windows: X, table and partial must be 16-byte aligned, starts 4-byte aligned"); return -1; }
+  hipStream_t st = (hipStream_t)stream;
+  return dtype == SDA_BF16 ? launch_sim_windows<uint16_t>(X, x_pitch, table, starts, base_row, row_elems, partial, M, N, Np, K, ksplit, st)
+                           : launch_sim_windows<half_t>(X, x_pitch, table, starts, base_row, row_elems, partial, M, N, Np, K, ksplit, st);
+}
+
+extern "C" long sda_sim_gemm_windows_span(long row_elems) {
+  // the largest starts[j] - base_row one launch serves: its byte offset plus a swizzled 16-byte chunk of the first 64 bytes
+  // fits the 32-bit per-lane offset (0: row_elems is not a positive multiple of 64)
+  if (row_elems < 64 || row_elems % 64 != 0) return 0;
+  const long lim = ((1L << 32) / 2 - 32) / row_elems;
+  return lim > 0x7FFFFFFFL ? 0x7FFFFFFFL : lim;
 }

@@ -67,6 +67,9 @@ SIGNATURES = {
     "sda_stream_create_cumask": (i32, [vp, i32, vp]),
     "sda_sim_gemm_ksplit": (i32, [i32, i32, i64, i32]),
     "sda_sim_gemm": (i32, [vp, vp, vp, i32, i32, i32, i64, i64, i32, i32, vp]),
+    "sda_sim_gemm_windows": (i32, [vp, i64, vp, vp, i32, i64, vp, i32, i32, i32, i64, i32, i32, vp]),
+    "sda_sim_gemm_windows_span": (i64, [i64]),
+    "sda_window_sumsq": (i32, [vp, vp, vp, i32, i32, vp]),
     "sda_stream_create_priority": (i32, [i32, vp]),
     "sda_stream_destroy": (i32, [vp]),
     "sda_set_cu_limit": (i32, [i32]),

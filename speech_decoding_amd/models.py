@@ -496,7 +496,7 @@ class Classifier(nn.Module):
     @torch.no_grad()
     def decode(self, Z: torch.Tensor, bank, k: int = 10, labels=None):
         """Decode brain segments against a speech bank: the QUERIES are the brain embeddings Z (N, F, T), the CANDIDATES the
-        speech segments of `bank` (a retrieval.SpeechBank); returns retrieval.retrieve(Z, bank, k, labels) — for each brain
+        speech segments of `bank` (a retrieval.SpeechBank, or a retrieval.WindowBank of windows cut from continuous tracks); returns retrieval.retrieve(Z, bank, k, labels) — for each brain
         segment the k best speech candidates and, with `labels`, the rank of the one it heard.  forward() looks the other
         way (for each speech row, the brain columns of the batch); retrieve() serves either direction, it does not care which
         side is which."""
@@ -506,7 +506,7 @@ class Classifier(nn.Module):
     @torch.no_grad()
     def decode_classes(self, Z: torch.Tensor, bank, classes, **kw):
         """Word-level decoding of brain segments: the QUERIES are the brain embeddings Z (N, F, T), the CANDIDATES the speech
-        segments of `bank`, `classes` says which word each candidate is an instance of (a retrieval.ClassIndex or the M class
+        segments of `bank` (a retrieval.SpeechBank or retrieval.WindowBank), `classes` says which word each candidate is an instance of (a retrieval.ClassIndex or the M class
         ids); returns retrieval.retrieve_classes(Z, bank, classes, **kw) — for each brain segment (or, with groups=, each group
         of repetitions) the k most probable words and, with labels=, the rank of the one it heard."""
         from .retrieval import retrieve_classes

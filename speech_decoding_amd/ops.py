@@ -635,6 +635,50 @@ def matmul_nt_splitk_into(xm: torch.Tensor, wm: torch.Tensor, M: int, N: int, K:
     return out
 
 
+def sim_gemm_windows_span(row_elems: int) -> int:
+    """Largest start - base_row one sim_gemm_windows launch serves for table rows of `row_elems` elements (asked, not mirrored)."""
+    return L.load().sda_sim_gemm_windows_span(row_elems)
+
+
+def sim_gemm_windows_into(xm: torch.Tensor, x_pitch: int, table: torch.Tensor, starts: torch.Tensor, lo: int, hi: int, row_elems: int,
+                          M: int, N: int, K: int, ksplit: int, partial: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out[i][j] = sum_k xm[i][k] * table[starts[j] * row_elems + k] for i < M, j < N (pad64(N) columns per row): matmul_nt_splitk_into
+    against N windows of a table of plain rows (sda_sim_gemm_windows + the ordered slab sum).  `starts`: N int32 table rows on
+    the device; `lo`, `hi`: their smallest and largest, from the caller's host copy — a chunk whose span hi - lo does not fit the
+    kernel's 32-bit offset is refused here, and a window past the table's end too."""
+    _need_cuda(xm, table, starts, partial, out)
+    _need_values(starts, torch.int32, N, "sim_gemm_windows: starts must hold N contiguous int32 table rows")
+    if xm.dtype != table.dtype or not table.is_contiguous():
+        raise L.SdaError("sim_gemm_windows: X and a contiguous table of one 16-bit dtype")
+    if lo < 0 or hi < lo or hi * row_elems + K > table.numel():
+        raise L.SdaError(f"sim_gemm_windows: windows [{lo}, {hi}] x {K} elements leave the table of {table.numel()} elements")
+    if hi - lo > sim_gemm_windows_span(row_elems):
+        raise L.SdaError(f"sim_gemm_windows: the chunk's windows span table rows {lo} ... {hi}, more than 4 GB (add candidates in "
+                         "time order, or lower scratch_bytes for smaller chunks)")
+    Np = L.pad_channels(N)
+    _need_values(out, torch.float32, M * Np, "sim_gemm_windows: out must hold M * pad64(N) contiguous fp32 values")
+    if ksplit > 1:
+        _need_values(partial, torch.float32, ksplit * M * Np, "sim_gemm_windows: partial must hold ksplit * M * pad64(N) contiguous fp32 values")
+    dst = out if ksplit == 1 else partial
+    L.check(L.load().sda_sim_gemm_windows(_p(xm), x_pitch, _p(table), _p(starts), lo, row_elems, _p(dst), M, N, Np, K, ksplit,
+                                          dt_code(xm.dtype), _st()), "sim_gemm_windows")
+    if ksplit > 1:
+        L.check(L.load().sda_reduce_slabs(_p(partial), _p(out), ksplit, M * Np, _st()), "reduce_slabs")
+    return out
+
+
+def window_sumsq(row_sq: torch.Tensor, starts: torch.Tensor, M: int, T: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[m] = sum of row_sq[starts[m] ... starts[m] + T) for m < M in a fixed order (sda_window_sumsq); the caller has checked
+    the starts against the rows of row_sq."""
+    _need_cuda(row_sq, starts, out)
+    _need_values(row_sq, torch.float32, T, "window_sumsq: row_sq must be contiguous fp32 sums of at least T rows")
+    _need_values(starts, torch.int32, M, "window_sumsq: starts must hold M contiguous int32 rows")
+    out = torch.empty(M, dtype=torch.float32, device=row_sq.device) if out is None else out
+    _need_values(out, torch.float32, M, "window_sumsq: out must hold M contiguous fp32 values")
+    L.check(L.load().sda_window_sumsq(_p(row_sq), _p(starts), _p(out), M, T, _st()), "window_sumsq")
+    return out
+
+
 def matmul_nt_splitk(xm: torch.Tensor, wm: torch.Tensor, M: int, N: int, K: int, pitch: int) -> torch.Tensor:
     """S[i][j] = sum_k xm[i][k] * wm[j][k] (both K-contiguous rows with `pitch`), fp32 (M, pad64(N)) result.
     Runs conv_gemm in split-K mode + ordered slab reduction (loss.py:68)."""

@@ -12,6 +12,10 @@ N x M score matrix is never held whole: see plan_blocks.  Which side is "query" 
 a speech bank (`Classifier.decode`) or the other way round; under torch.distributed every rank decodes its own queries
 against its own bank and no collective is issued.  No gradients: both entry points run under no_grad.
 
+A `WindowBank` holds candidates that are windows of continuous speech tracks (the reference cuts its segments at word onsets out
+of one embedding track per audio file): each track is stored once as plain rows, a candidate is a row start, and the same pass
+scores them with the windowed form of the similarity GEMM (sda_sim_gemm_windows) — 16-bit storage only, nothing is materialised.
+
 Word-level decoding sits on the same blocked score matrix, filled by the same pass (`_ScorePass`: checks, pack, norms, scratch
 and block loop, written once): a `ClassIndex` says which class (word) every candidate is an instance of, and `retrieve_classes`
 pools each row's scores per class on the device (sda_retrieval_class_reduce: a segmented log-sum-exp at the loss's temperature,
@@ -128,6 +132,134 @@ class SpeechBank:
         return range(first, first + m)
 
 
+MAX_TABLE_ROWS = 0x7FFF0000        # window starts are int32 table rows
+_SUMSQ_ROWS = 32768                # table rows per sda_rows_sumsq launch (one grid row each)
+
+
+class WindowBank:
+    """M candidate segments that are WINDOWS of continuous speech tracks: candidate m is the T rows from row starts[m] on of one
+    resident table of plain rows, (L_total, pad_channels(F)) of `dtype` with the tracks back to back and the channel padding
+    zero — one audio file's embedding track is stored once however many word onsets cut windows from it, where a SpeechBank
+    stores rows_tp(T) * pad_channels(F) elements per candidate.  Beside the table: the candidates' global row starts (int32, on
+    the device and on the host), the fp32 sum of squares of every table row, and from those the candidates' fp32 squared norms.
+    retrieve, retrieve_classes and Classifier.decode* take it in a SpeechBank's place (sda_sim_gemm_windows).  16-bit storage
+    only: the windowed similarity GEMM has no fp32 form and nothing falls back to materialising the windows.  A bank filled by
+    several add_track() calls holds the same bytes and norms as one filled at once."""
+
+    def __init__(self, F: int, T: int, dtype=torch.bfloat16, device="cuda"):
+        if int(F) < 1 or int(T) < 1:
+            raise ValueError(f"WindowBank: F and T must be positive, got F={F}, T={T}")
+        if dtype == torch.float32:
+            raise ValueError("WindowBank: dtype float32; the windowed similarity GEMM serves 16-bit storage only (bfloat16 or "
+                             "float16) and nothing materialises the windows instead: use a SpeechBank for fp32 candidates")
+        if dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"WindowBank: dtype {dtype}; a window bank holds bfloat16 or float16")
+        self.F, self.T, self.dtype = int(F), int(T), dtype
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.SdaError("WindowBank lives on the MI355X device (there is no CPU path)")
+        self.row_elems = L.pad_channels(self.F)             # of ONE table row; a candidate is T of them
+        self._size, self._capacity = 0, 0                   # candidates
+        self._L, self._row_capacity = 0, 0                  # table rows
+        self._store = None              # row-layout buffer of one "sample" of _row_capacity rows: table row l is its row ROW_PAD + l
+        self._row_sq = None             # (_row_capacity,) fp32
+        self._starts = None             # (_capacity,) int32
+        self._sq = None                 # (_capacity,) fp32
+        self.starts_host = np.empty(0, dtype=np.int32)
+
+    def __len__(self) -> int:
+        return self._size
+
+    @property
+    def table(self) -> torch.Tensor:
+        """(L_total, pad_channels(F)) view of the stored tracks."""
+        re = self.row_elems
+        return self._store[L.ROW_PAD * re: (L.ROW_PAD + self._L) * re].view(self._L, re)
+
+    @property
+    def starts(self) -> torch.Tensor:
+        """(M,) int32 device tensor: the table row every candidate starts at."""
+        return self._starts[: self._size]
+
+    @property
+    def norms_sq(self) -> torch.Tensor:
+        """(M,) fp32 squared norms of the stored (rounded) candidates."""
+        return self._sq[: self._size]
+
+    @property
+    def row_norms_sq(self) -> torch.Tensor:
+        """(L_total,) fp32 sums of squares of the table's rows."""
+        return self._row_sq[: self._L]
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes the bank's contents take: the table, the starts and norms of the candidates, the per-row sums."""
+        return self._L * self.row_elems * 2 + 8 * self._size + 4 * self._L
+
+    def _reserve(self, rows: int, capacity: int):
+        """Room for `rows` table rows and `capacity` candidates; what has to grow at least doubles (SpeechBank._reserve)."""
+        L.load()
+        re = self.row_elems
+        if rows > self._row_capacity:
+            rows = max(rows, 2 * self._row_capacity)
+            store = torch.empty(L.rows_alloc(1, rows) * re, dtype=self.dtype, device=self.device)
+            row_sq = torch.empty(rows, dtype=torch.float32, device=self.device)
+            if self._L:
+                a, b = L.ROW_PAD * re, (L.ROW_PAD + self._L) * re
+                store[a:b].copy_(self._store[a:b])
+                row_sq[: self._L].copy_(self._row_sq[: self._L])
+            self._store, self._row_sq, self._row_capacity = store, row_sq, rows
+        if capacity > self._capacity:
+            capacity = max(capacity, 2 * self._capacity)
+            starts = torch.empty(capacity, dtype=torch.int32, device=self.device)
+            sq = torch.empty(capacity, dtype=torch.float32, device=self.device)
+            if self._size:
+                starts[: self._size].copy_(self._starts[: self._size])
+                sq[: self._size].copy_(self._sq[: self._size])
+            self._starts, self._sq, self._capacity = starts, sq, capacity
+
+    @torch.no_grad()
+    def add_track(self, E: torch.Tensor, starts) -> range:
+        """Append one track E (F, L) — fp32, bf16 or fp16, any strides — and the windows of T rows that begin at its rows
+        `starts` (host integers in [0, L - T], any order, duplicates allowed); returns the bank indices the windows received.
+        Add tracks, and the windows of a track, in time order where you can: a chunk of neighbouring candidates then reads
+        neighbouring table rows, which is what the caches can keep and what the 4 GB span of one GEMM launch is counted over."""
+        if not torch.is_tensor(E) or E.dim() != 2 or E.shape[0] != self.F or E.shape[1] < self.T:
+            got = tuple(E.shape) if torch.is_tensor(E) else type(E).__name__
+            raise ValueError(f"WindowBank.add_track: expected an ({self.F}, L) track with L >= {self.T}, got {got}")
+        arr = starts.detach().cpu().numpy() if torch.is_tensor(starts) else np.asarray(starts)
+        if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
+            raise ValueError("WindowBank.add_track: starts must be a one-dimensional array of integer rows")
+        rows, m, first, row0 = int(E.shape[1]), int(arr.shape[0]), self._size, self._L
+        if m and (int(arr.min()) < 0 or int(arr.max()) > rows - self.T):
+            raise IndexError(f"WindowBank.add_track: a start outside [0, L - T = {rows - self.T}]")
+        if row0 + rows > MAX_TABLE_ROWS or first + m > MAX_M:
+            raise ValueError(f"WindowBank.add_track: more than {MAX_TABLE_ROWS:#x} table rows or candidates")
+        if not E.is_cuda:
+            raise L.SdaError("WindowBank.add_track: E must live on the MI355X device (there is no CPU path)")
+        if E.device != self.device and not (self.device.index is None and E.device.index == torch.cuda.current_device()):
+            raise L.SdaError(f"WindowBank.add_track: E is on {E.device}, the bank on {self.device}")
+        if E.dtype not in ops.COMPUTE_DTYPES:
+            raise L.SdaError(f"WindowBank.add_track: E of dtype {E.dtype}; tracks are float32, bfloat16 or float16")
+        if m == 0:
+            return range(first, first)
+        self._reserve(row0 + rows, first + m)
+        re = self.row_elems
+        # the pack writes the track as the one sample of a row-layout buffer that begins ROW_PAD rows in front of its first table
+        # row: exactly the rows [row0, row0 + rows) of the table, every channel of each, and nothing else
+        ops.pack_rows(E.detach().unsqueeze(0), self._store[row0 * re:].view(-1, re))
+        table = self._store[L.ROW_PAD * re:]
+        for r0 in range(row0, row0 + rows, _SUMSQ_ROWS):
+            n = min(_SUMSQ_ROWS, row0 + rows - r0)
+            self._row_sq[r0: r0 + n].copy_(ops.rows_sumsq(table[r0 * re:], n, re, re))
+        glob = (arr.astype(np.int64) + row0).astype(np.int32)
+        self._starts[first: first + m].copy_(torch.from_numpy(glob).to(self._starts.device))
+        ops.window_sumsq(self._row_sq, self._starts[first:], m, self.T, out=self._sq[first:])
+        self.starts_host = np.concatenate([self.starts_host, glob])
+        self._size, self._L = first + m, row0 + rows
+        return range(first, first + m)
+
+
 def plan_blocks(N: int, M: int, K: int, dtype, scratch_bytes: int):
     """(nb, mc, tiles256, ksplit): queries are decoded nb rows at a time; a block's raw scores over the WHOLE bank are held
     (nb x pad64(M) fp32, at most half of scratch_bytes), filled by one GEMM per chunk of mc bank rows, each in `ksplit` K slices
@@ -198,9 +330,9 @@ class _ScorePass:
     refuses what the kernels cannot read (SdaError); start touches the device first: host labels go up, the queries are packed,
     their norms taken, the scratch allocated; blocks() fills S with one block of queries' scores after the other."""
 
-    def __init__(self, who: str, queries: torch.Tensor, bank: SpeechBank, k=None):
-        if not isinstance(bank, SpeechBank):
-            raise ValueError(f"{who}: bank must be a SpeechBank")
+    def __init__(self, who: str, queries: torch.Tensor, bank, k=None):
+        if not isinstance(bank, (SpeechBank, WindowBank)):
+            raise ValueError(f"{who}: bank must be a SpeechBank or a WindowBank")
         if not torch.is_tensor(queries) or queries.dim() != 3 or queries.shape[0] < 1:
             raise ValueError(f"{who}: queries must be an (N, F, T) tensor with N >= 1")
         N, F, T = queries.shape
@@ -211,14 +343,22 @@ class _ScorePass:
         if len(bank) == 0:
             raise ValueError(f"{who}: the bank is empty")
         self.who, self.queries, self.bank = who, queries, bank
-        self.N, self.F, self.M, self.K = N, F, len(bank), bank.row_elems
+        self.N, self.F, self.M = N, F, len(bank)
+        # the packed queries are rows of rows_tp(T) * pad_channels(F) elements.  Against a SpeechBank, whose candidates are packed
+        # the same way, the contraction runs over the whole row (pad rows are zero on both sides); against a WindowBank over the T
+        # valid rows only, from the query's ROW_PAD-th row on: the rows in front of a window belong to other candidates.
+        self.windows = isinstance(bank, WindowBank)
+        self.q_pitch = L.rows_tp(T) * L.pad_channels(F)
+        self.q_skip = L.ROW_PAD * L.pad_channels(F) if self.windows else 0
+        self.K = self.q_pitch - self.q_skip
 
     def on_device(self) -> torch.device:
         who, queries = self.who, self.queries
         if not queries.is_cuda:
             raise L.SdaError(f"{who}: queries must live on the MI355X device (there is no CPU path)")
-        if queries.device != self.bank.rows.device:
-            raise L.SdaError(f"{who}: queries are on {queries.device}, the bank on {self.bank.rows.device}")
+        held = self.bank.table if self.windows else self.bank.rows
+        if queries.device != held.device:
+            raise L.SdaError(f"{who}: queries are on {queries.device}, the bank on {held.device}")
         if queries.dtype not in ops.COMPUTE_DTYPES:
             raise L.SdaError(f"{who}: queries of dtype {queries.dtype}; segments are float32, bfloat16 or float16")
         return queries.device
@@ -226,12 +366,16 @@ class _ScorePass:
     def start(self, plan, labels=None):
         """Takes the (nb, mc, tiles256, ksplit) of plan_blocks / plan_class_blocks; returns the labels as the kernels read them."""
         self.nb, self.mc, self.tiles256, self.ks = nb, mc, _, ks = plan
-        N, K, bank, dev = self.N, self.K, self.bank, self.queries.device
+        N, bank, dev = self.N, self.bank, self.queries.device
+        if self.windows and not self.tiles256:
+            raise L.SdaError(f"{self.who}: the windowed similarity GEMM does not serve this shape (there is no other path)")
         if isinstance(labels, np.ndarray):
             labels = ops.upload_small(labels, dev)
         self.Qt = ops.rows_of(self.queries, self.F, bank.dtype)[0].reshape(-1)
-        self.qsq = ops.rows_sumsq(self.Qt, N, K, K)
-        self.Bt, self.csq = bank.rows.reshape(-1), bank.norms_sq
+        self.qsq = ops.rows_sumsq(self.Qt, N, self.q_pitch, self.q_pitch)
+        self.Bt, self.csq = (bank.table if self.windows else bank.rows).reshape(-1), bank.norms_sq
+        if self.windows:             # (smallest, largest) start of every chunk of mc candidates, from the host copy
+            self.spans = [(int(c.min()), int(c.max())) for c in (bank.starts_host[c0: c0 + mc] for c0 in range(0, self.M, mc))]
         self.S = torch.empty(ops.retrieval_scores_floats(nb, self.M, mc), dtype=torch.float32, device=dev)
         self.partial = torch.empty(ks * nb * mc if ks > 1 else 0, dtype=torch.float32, device=dev)
         return labels
@@ -244,10 +388,17 @@ class _ScorePass:
 
     def fill(self, i0: int = 0) -> int:
         """Fill S with the raw dot products of queries i0 ... i0 + n - 1 against the whole bank, one GEMM per chunk; returns n."""
-        M, K, mc, Qt, Bt = self.M, self.K, self.mc, self.Qt, self.Bt
+        M, K, mc, Bt = self.M, self.K, self.mc, self.Bt
+        Q = self.Qt[self.q_skip + i0 * self.q_pitch:]
         n = min(self.nb, self.N - i0)
         for c0 in range(0, M, mc):
-            ops.matmul_nt_splitk_into(Qt[i0 * K:], Bt[c0 * K:], n, min(mc, M - c0), K, K, self.tiles256, self.ks, self.partial, self.chunk(c0, n))
+            m = min(mc, M - c0)
+            if self.windows:
+                lo, hi = self.spans[c0 // mc]
+                ops.sim_gemm_windows_into(Q, self.q_pitch, Bt, self.bank.starts[c0: c0 + m], lo, hi, self.bank.row_elems, n, m, K,
+                                          self.ks, self.partial, self.chunk(c0, n))
+            else:
+                ops.matmul_nt_splitk_into(Q, Bt[c0 * K:], n, m, K, K, self.tiles256, self.ks, self.partial, self.chunk(c0, n))
         return n
 
     def blocks(self):
@@ -257,8 +408,8 @@ class _ScorePass:
 
 
 @torch.no_grad()
-def retrieve(queries: torch.Tensor, bank: SpeechBank, k: int = 10, labels=None, scratch_bytes: int = 1 << 30) -> Retrieval:
-    """Score the N segments of `queries` (N, F, T) against every candidate of `bank` and return the k best of each
+def retrieve(queries: torch.Tensor, bank, k: int = 10, labels=None, scratch_bytes: int = 1 << 30) -> Retrieval:
+    """Score the N segments of `queries` (N, F, T) against every candidate of `bank` (a SpeechBank or a WindowBank) and return the k best of each
     (Retrieval); with `labels` (N integer bank indices, host or device) also the rank of each query's true candidate over the
     whole bank.  Labels on the host are checked here (IndexError); labels on the device are checked by the kernel, which
     reports -1 for one outside the bank, because nothing is read back: the results are device tensors.  `scratch_bytes`
@@ -373,9 +524,9 @@ def _group_index(groups, N: int):
 
 
 @torch.no_grad()
-def retrieve_classes(queries: torch.Tensor, bank: SpeechBank, classes, k: int = 10, scale: float = 1.0, reduce: str = "sum",
+def retrieve_classes(queries: torch.Tensor, bank, classes, k: int = 10, scale: float = 1.0, reduce: str = "sum",
                      labels=None, groups=None, return_matrix: bool = False, scratch_bytes: int = 1 << 30) -> ClassRetrieval:
-    """Word-level decoding: score the N segments of `queries` against every candidate of `bank`, pool the scores of the
+    """Word-level decoding: score the N segments of `queries` against every candidate of `bank` (a SpeechBank or a WindowBank), pool the scores of the
     candidates of one class, and return the k best CLASSES of each query (ClassRetrieval).  `classes`: a ClassIndex over the
     bank's M rows, or the M class ids themselves.  The logit of query i against candidate j is scale * cos(i, j), cos the
     similarity retrieve() uses and `scale` a positive finite float (a trained CLIPLoss: float(loss.temp.exp())); class c gets
