@@ -1,0 +1,114 @@
+"""The CLIP loss's launch schedule on row-layout embeddings: one rank's logits block with its soft-max statistics, then
+(after the cross-rank merge of the row statistics) the loss share, the gradient coefficient matrix and the rank counts, and
+the two embedding gradients.  `loss.py` owns the buffers, the gathers and the autograd node around it.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from . import lib as L
+from . import ops
+
+
+@dataclass
+class ClipCtx:
+    Bm: int
+    Bn: int
+    col0: int
+    G: torch.Tensor
+    rscale: torch.Tensor
+    Yt: torch.Tensor
+    Zt: torch.Tensor
+    row_elems: int
+    dtemp: torch.Tensor
+    cscale: Optional[torch.Tensor] = None     # per-column factor taken out of G (see sda_clip_grad): the dZ GEMM's acc_scale
+    # what the speech-side gradient (clip_backward_y) needs besides: the block's logits and softmax statistics, the norms
+    logits: Optional[torch.Tensor] = None
+    row_lse: Optional[torch.Tensor] = None
+    col_lse: Optional[torch.Tensor] = None
+    ysq: Optional[torch.Tensor] = None
+    zsq: Optional[torch.Tensor] = None
+    temp: Optional[torch.Tensor] = None
+    inv_norm: float = 0.0
+
+
+def clip_forward(Yt: torch.Tensor, Zt: torch.Tensor, temp: torch.Tensor, *, Bm: int, Bn: int, T: int, col0: int = 0,
+                 reduction: str = "mean", B_global: Optional[int] = None, dist_group=None, want_grad: bool = True,
+                 ysq: Optional[torch.Tensor] = None):
+    """CLIP loss (loss.py:58-79) on RL embeddings: Yt holds the Bm (global) speech rows, Zt the Bn local
+    brain rows.  Returns (loss_local_share, logits, ranks_count, ctx).  With `dist_group`, row statistics
+    and the diagonal are merged across ranks so that the negatives span the global batch."""
+    st = clip_block_stats(Yt, Zt, temp, Bm=Bm, Bn=Bn, T=T, col0=col0, ysq=ysq)
+    if dist_group is None:                       # one process: the block IS the whole matrix, its row lse came with the logits
+        row_lse, diag = st.row_lse, st.diag
+    else:
+        from .distributed import merge_row_softmax_stats
+        row_lse, diag = merge_row_softmax_stats(st.row_max, st.row_sum, dist_group, diag=st.diag)   # diag: zero where not owned
+    return clip_block_finish(st, row_lse, diag, reduction=reduction, B_global=B_global)
+
+
+@dataclass
+class ClipBlockStats:
+    """One rank's column block before the cross-rank merge: logits (Bm, Bn) and what the merge needs."""
+    Yt: torch.Tensor
+    Zt: torch.Tensor
+    temp: torch.Tensor
+    Bm: int
+    Bn: int
+    col0: int
+    row_elems: int
+    ysq: torch.Tensor
+    zsq: torch.Tensor
+    logits: torch.Tensor
+    row_max: torch.Tensor
+    row_sum: torch.Tensor
+    col_lse: torch.Tensor
+    diag: torch.Tensor
+    row_lse: torch.Tensor          # lse of each row over this block's columns only
+
+
+def clip_block_stats(Yt, Zt, temp, *, Bm: int, Bn: int, T: int, col0: int = 0, ysq=None) -> ClipBlockStats:
+    """First half of clip_forward: norms, the (Bm x Bn) logits block of this rank's brain columns, per-row (max, sum exp)
+    over the block, per-column lse over all rows, the positives' logits.  Rank-local: no collective."""
+    Fp = Zt.shape[1]
+    row_elems = L.rows_tp(T) * Fp
+    if ysq is None:                              # (under DP the caller gathers the per-rank norms instead)
+        ysq = ops.rows_sumsq(Yt, Bm, row_elems, row_elems)
+    zsq = ops.ROW_NORMS.get(Zt, Bn)              # left by the encoder's last conv when Zt is its output buffer
+    if zsq is None:
+        zsq = ops.rows_sumsq(Zt, Bn, row_elems, row_elems)
+    S = ops.matmul_nt_splitk(Yt, Zt, Bm, Bn, row_elems, row_elems)
+    logits, row_max, row_sum, col_lse, diag, row_lse = ops.clip_logits_stats(S, ysq, zsq, temp, Bm, Bn, col0)
+    return ClipBlockStats(Yt, Zt, temp, Bm, Bn, col0, row_elems, ysq, zsq, logits, row_max, row_sum, col_lse, diag, row_lse)
+
+
+def clip_block_finish(st: ClipBlockStats, row_lse, diag, *, reduction: str = "mean", B_global: Optional[int] = None):
+    """Second half, given the row lse over the columns of ALL ranks and the positives' logits (after the merge): this rank's
+    share of the loss and of d loss / d temp, the gradient coefficient matrix, the retrieval rank counts."""
+    Yt, Zt, temp, Bm, Bn, col0, row_elems = st.Yt, st.Zt, st.temp, st.Bm, st.Bn, st.col0, st.row_elems
+    logits, col_lse, ysq, zsq = st.logits, st.col_lse, st.ysq, st.zsq
+    Bg = B_global if B_global is not None else Bm
+    inv_norm = 1.0 / (2.0 * Bg) if reduction == "mean" else 0.5
+    # G is an MFMA operand (16-bit in the 16-bit modes): it holds the O(1) part of dL/dlogits * exp(temp) / (|Y||Z|), the
+    # rest — 1e-8 at the 8-GPU shapes, far outside fp16 — comes back as a per-column fp32 factor in the dZ GEMM's epilogue
+    G, rscale, cscale, scalars = ops.clip_grad(logits, row_lse, col_lse, ysq, zsq, temp, inv_norm, col0, Yt.dtype)
+    cnt = ops.clip_ranks(logits, diag, col0)
+    ctx = ClipCtx(Bm=Bm, Bn=Bn, col0=col0, G=G, rscale=rscale, Yt=Yt, Zt=Zt, row_elems=row_elems, dtemp=scalars[1:2],
+                  cscale=cscale, logits=logits, row_lse=row_lse, col_lse=col_lse, ysq=ysq, zsq=zsq, temp=temp, inv_norm=inv_norm)
+    return scalars[0:1], logits, cnt, ctx
+
+
+def clip_backward(ctx: ClipCtx, dZt: torch.Tensor, dloss: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dZ = dloss * (diag(c) G^T Y - diag(r) Z)  (gradient of the loss share w.r.t. the local brain embeddings)."""
+    return ops.clip_dz(ctx.G, ctx.Yt, ctx.Zt, dZt, ctx.rscale, ctx.cscale, Bm=ctx.Bm, Bn=ctx.Bn, row_elems=ctx.row_elems, out_scale=dloss)
+
+
+def clip_backward_y(ctx: ClipCtx, dYt: torch.Tensor, dloss: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dY = dloss * (diag(c_y) Gy^T Z - diag(r_y) Y) on one GPU (the block is the whole matrix): the dZ product with the roles of
+    the two embeddings exchanged, on the same GEMM family (no new GEMM kernel)."""
+    Gy, part = ops.clip_grad_y(ctx.logits, ctx.row_lse, ctx.col_lse, ctx.zsq, ctx.zsq, ctx.col0, ctx.Zt.dtype)
+    rscale_y, cscale_y = ops.clip_grad_y_finish(part, ctx.ysq, ctx.zsq, ctx.temp, ctx.inv_norm, 0, ctx.Bm)
+    return ops.clip_dz(Gy, ctx.Zt, ctx.Yt, dYt, rscale_y, cscale_y, Bm=ctx.Bn, Bn=ctx.Bm, row_elems=ctx.row_elems, out_scale=dloss)

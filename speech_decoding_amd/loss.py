@@ -12,53 +12,17 @@ Also `MSELoss` (loss.py:15-25), the reference's regression objective, on the sda
 """
 from __future__ import annotations
 
-from typing import Optional
+import weakref
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
 
+from . import clip
 from . import lib as L
 from . import ops
-from . import engine as E
-
-import weakref
 
 _rank_cache = []          # [(weakref(Y), weakref(Z), Y._version, Z._version, ranks)] from the last CLIPLoss forward
-
-
-class LossState:
-    """Buffers that outlive one call, owned by ONE CLIPLoss instance (nothing is shared between instances by shape):
-    the rotating packed-speech buffers and the pending speech-side prefetch.  Every hand-out of a ring slot bumps
-    that slot's generation; a backward checks the generation it was given, so a buffer recycled by later forwards
-    raises instead of silently feeding another batch's rows into the gradient."""
-
-    def __init__(self):
-        self.rings = {}           # (key, B, C, T, dtype, device) -> [buffers, next index, generations]
-        self.prefetched = []      # at most one pending prefetch
-        self.ring_depth = 2
-        self.emulated = {}        # distributed.emulate_world: the resident stand-ins for the other ranks' speech rows
-
-    def drain(self):
-        """Wait for a pending prefetch's collectives (the speech-row all-gather issued one batch ahead and never consumed:
-        the last one of a run) and drop it.  A process group torn down while such a collective is still in flight aborts
-        the process ("terminate called without an active exception": a transport thread destroyed while joinable)."""
-        for item in self.prefetched:
-            works, done = item[7], item[8]
-            if done is not None:
-                done.synchronize()
-            for work in works:
-                work.wait()
-        if self.prefetched and torch.cuda.is_available():
-            torch.cuda.synchronize()
-        self.prefetched.clear()
-
-    def clear(self):
-        self.drain()
-        self.rings.clear()
-        self.emulated.clear()
-
-
-_DEFAULT_STATE = LossState()      # for the module-level helpers called without a CLIPLoss instance
 
 
 class RingSlot:
@@ -69,7 +33,82 @@ class RingSlot:
         self.ring, self.idx, self.gen, self.buf = ring, idx, gen, buf
 
     def valid(self) -> bool:
-        return self.ring[2][self.idx] == self.gen
+        return self.ring.gens[self.idx] == self.gen
+
+
+class Ring:
+    """Persistent RL buffers of one shape for packed inputs (no per-call 200 MB allocation + memset), in rotation so that the
+    buffer a pending backward still needs survives one further forward (e.g. an eval pass between forward and backward).
+    gens[i] counts the hand-outs of bufs[i]: a backward that comes later than that finds its slot's generation changed."""
+    __slots__ = ("bufs", "gens", "next")
+
+    def __init__(self, bufs):
+        self.bufs, self.gens, self.next = bufs, [0] * len(bufs), 0
+
+    def take(self) -> RingSlot:
+        idx = self.next % len(self.bufs)
+        self.next += 1
+        self.gens[idx] += 1
+        return RingSlot(self, idx, self.gens[idx], self.bufs[idx])
+
+
+class GatheredRows:
+    """The rows one side of the loss reads, and what must be waited for before reading them: `rows` holds `n` samples (the
+    global batch) with squared norms `sq`, this rank's own from sample `col0` on; `slot` is the ring slot that owns the rows
+    a backward will read; `works` are the collectives still filling them, `done` the event of a side stream that issued them."""
+    __slots__ = ("rows", "sq", "n", "col0", "slot", "works", "done")
+
+    def __init__(self, rows, sq, n, col0=0, slot=None, works=(), done=None):
+        self.rows, self.sq, self.n, self.col0, self.slot, self.works, self.done = rows, sq, n, col0, slot, works, done
+
+    def wait(self):
+        """The current stream waits for the side stream and for RCCL's; the host does not block."""
+        if self.done is not None:
+            torch.cuda.current_stream(self.rows.device).wait_event(self.done)
+        for work in self.works:
+            work.wait()
+
+
+class Pending(NamedTuple):
+    """A speech-side prefetch no forward has consumed yet: for which tensor object and compute dtype, and its rows."""
+    y_ref: weakref.ref
+    dtype: torch.dtype
+    rows: GatheredRows
+
+
+class LossState:
+    """Buffers that outlive one call, owned by ONE CLIPLoss instance (nothing is shared between instances by shape): the rotating
+    packed-speech buffers and the pending speech-side prefetch.  A backward checks the generation of the ring slot it was given,
+    so a buffer recycled by later forwards raises instead of silently feeding another batch's rows into the gradient."""
+
+    def __init__(self):
+        self.rings = {}           # (key, B, C, T, dtype, device) -> Ring
+        self.pending: Optional[Pending] = None
+        self.ring_depth = 2
+        self.emulated = {}        # distributed.emulate_world: the resident stand-ins (rows, norms) for the other ranks' speech rows
+
+    def drain(self):
+        """Wait for a pending prefetch's collectives (the speech-row all-gather issued one batch ahead and never consumed:
+        the last one of a run) and drop it.  A process group torn down while such a collective is still in flight aborts
+        the process ("terminate called without an active exception": a transport thread destroyed while joinable)."""
+        if self.pending is None:
+            return
+        rows = self.pending.rows
+        if rows.done is not None:
+            rows.done.synchronize()
+        for work in rows.works:
+            work.wait()
+        if torch.cuda.is_available():
+            torch.cuda.synchronize()
+        self.pending = None
+
+    def clear(self):
+        self.drain()
+        self.rings.clear()
+        self.emulated.clear()
+
+
+_DEFAULT_STATE = LossState()      # for the module-level helpers called without a CLIPLoss instance
 
 
 def _cache_ranks(Y, Z, cnt):
@@ -91,38 +130,38 @@ _rows_base = ops.rows_base      # its name while it lived here: kept for code ou
 
 
 def _ring_rows(state: LossState, key, B, Cc, T, dtype, device) -> RingSlot:
-    """Persistent RL buffers for packed inputs (no per-call 200 MB allocation + memset).  `ring_depth` buffers
-    rotate so that the buffer a pending backward still needs survives one further forward (e.g. an eval
-    pass between forward and backward); a backward that comes later than that finds its slot's generation changed."""
+    """The next slot of `state`'s ring for this key and shape; a new ring gets `ring_depth` buffers."""
     k = (key, B, Cc, T, dtype, str(device))
     ring = state.rings.get(k)
     if ring is None:
         if len(state.rings) >= 8:                  # ragged last batches etc.: keep the most recent shapes only
             state.rings.pop(next(iter(state.rings)))
-        depth = state.ring_depth
-        ring = state.rings[k] = [[ops.new_rows(B, T, L.pad_channels(Cc), dtype, device) for _ in range(depth)], 0, [0] * depth]
-    idx = ring[1] % len(ring[0])
-    ring[1] += 1
-    ring[2][idx] += 1
-    return RingSlot(ring, idx, ring[2][idx], ring[0][idx])
+        ring = state.rings[k] = Ring([ops.new_rows(B, T, L.pad_channels(Cc), dtype, device) for _ in range(state.ring_depth)])
+    return ring.take()
 
 
-def as_rows(t: torch.Tensor, B: int, Cc: int, T: int, dtype, name: str, ring_key=None, state: Optional[LossState] = None,
-            want_slot: bool = False):
-    """Return the RL buffer behind `t` (zero copy when `t` is a rows_view made by this package), else
-    pack a plain (B, C, T) tensor into an RL buffer (a rotating persistent one of `state` when `ring_key` is given).
-    With want_slot: (buffer, RingSlot or None)."""
+def _check_rows_arg(t: torch.Tensor, B: int, Cc: int, T: int, name: str):
     if tuple(t.shape) != (B, Cc, T):
         raise ValueError(f"{name}: expected shape {(B, Cc, T)}, got {tuple(t.shape)}")
     if not t.is_cuda:
         raise L.SdaError(f"{name} must live on the MI355X device (there is no CPU path)")
-    slots = []
 
-    def ring_slot(*_):                                     # pack_rows rewrites every valid row
-        slots.append(_ring_rows(state or _DEFAULT_STATE, ring_key, B, Cc, T, dtype, t.device))
-        return slots[0].buf
-    buf, _ = ops.rows_of(t, Cc, dtype, ops.new_rows if ring_key is None else ring_slot)
-    return (buf, slots[0] if slots else None) if want_slot else buf
+
+def as_rows(t: torch.Tensor, B: int, Cc: int, T: int, dtype, name: str) -> torch.Tensor:
+    """Return the RL buffer behind `t` (zero copy when `t` is a rows_view made by this package), else
+    pack a plain (B, C, T) tensor into a fresh RL buffer."""
+    _check_rows_arg(t, B, Cc, T, name)
+    return ops.rows_of(t, Cc, dtype)[0]
+
+
+def _pack_ring(state: LossState, t: torch.Tensor, B: int, Cc: int, T: int, dtype, name: str, ring_key: str):
+    """as_rows that packs into a rotating persistent buffer of `state`: (buffer, its RingSlot; None behind a rows_view)."""
+    _check_rows_arg(t, B, Cc, T, name)
+    base = ops.rows_base(t, B, Cc, T, dtype)
+    if base is not None:
+        return base, None
+    slot = _ring_rows(state, ring_key, B, Cc, T, dtype, t.device)
+    return ops.pack_rows(t.detach(), slot.buf), slot          # pack_rows rewrites every valid row
 
 
 def _dist_group():
@@ -130,45 +169,48 @@ def _dist_group():
     return active_group()
 
 
-def gather_speech_rows(Yt_local: torch.Tensor, B: int, T: int, group, async_op: bool = False,
-                       state: Optional[LossState] = None, slot: Optional[RingSlot] = None, ring_key: str = "loss.Yall",
-                       sq: Optional[torch.Tensor] = None):
-    """All-gather the packed speech rows of every rank (RCCL all_gather over xGMI; samples are contiguous
-    blocks of Tp rows, so the gather lands directly in RL order) together with their squared norms (computed
-    once, on the rank that owns the rows, unless `sq` hands them in).  Returns (Yt, ysq, Bm, col0, B_global, works, slot):
-    `slot` is the ring slot that owns the rows the backward will read (the local pack without a group, the gathered buffer
-    with one).  The same helper gathers the brain rows for the speech-side gradient (ring_key "loss.Zall")."""
-    row_elems = L.rows_tp(T) * Yt_local.shape[1]
-    ysq_local = sq if sq is not None else ops.rows_sumsq(Yt_local, B, row_elems, row_elems)
-    if group is None:
-        return Yt_local, ysq_local, B, 0, B, [], slot
-    import torch.distributed as dist
-    world, rank = dist.get_world_size(group), dist.get_rank(group)
-    Tp = L.rows_tp(T)
-    from .distributed import emulated_world
-    if world == 1 and emulated_world() > 1:
-        return _gather_emulated(Yt_local, ysq_local, B, T, group, emulated_world(), async_op, state or _DEFAULT_STATE)
-    slot = _ring_rows(state or _DEFAULT_STATE, ring_key, B * world, Yt_local.shape[1], T, Yt_local.dtype, Yt_local.device)
-    Yt = slot.buf
-    ysq = torch.empty(B * world, dtype=torch.float32, device=Yt_local.device)
-    from .distributed import side_group
-    bulk = side_group("gather", group)          # own communicator: must not queue in front of the BatchNorm all-reduces
-    w1 = dist.all_gather_into_tensor(Yt[: B * world * Tp], Yt_local[: B * Tp], group=bulk, async_op=async_op)
-    w2 = dist.all_gather_into_tensor(ysq, ysq_local, group=bulk, async_op=async_op)
-    return Yt, ysq, B * world, rank * B, B * world, ([w1, w2] if async_op else []), slot
-
-
 EMULATE_COPY_REMOTE = True      # emulated world: re-deliver the stand-in rows every step (a device copy in place of the wire)
 
 
-def _gather_emulated(Yt_local, ysq_local, B, T, group, W, async_op, state: LossState):
-    """distributed.emulate_world(W) at world size 1: this rank is rank 0 of W.  Its own rows travel through the real
-    all-gather (one rank); the (W - 1) * B rows of the other ranks are resident stand-ins (seeded N(0, 1) rows packed by
-    sda_pack_rows, norms by sda_rows_sumsq), copied into the gathered buffer every step on the stream the gather is issued
-    from — HBM sees the bytes a real gather would have landed (plus the copy's reads)."""
+def gather_speech_rows(Yt_local: torch.Tensor, B: int, T: int, group, async_op: bool = False,
+                       state: Optional[LossState] = None, slot: Optional[RingSlot] = None, ring_key: str = "loss.Yall",
+                       sq: Optional[torch.Tensor] = None) -> GatheredRows:
+    """All-gather the packed speech rows of every rank (RCCL all_gather over xGMI; samples are contiguous blocks of Tp rows, so
+    the gather lands directly in RL order) together with their squared norms (computed once, on the rank that owns the rows,
+    unless `sq` hands them in).  The record's `slot` owns the rows the backward will read (the local pack without a group, the
+    gathered buffer with one).  The same helper gathers the brain rows for the speech-side gradient (ring_key "loss.Zall").
+    distributed.emulate_world(W) at world size 1: this rank is rank 0 of W.  Its own rows travel through the real all-gather
+    (one rank); the (W - 1) * B rows of the other ranks are resident stand-ins, copied into the gathered buffer every step on
+    the stream the gather is issued from — HBM sees the bytes a real gather would have landed (plus the copy's reads)."""
+    row_elems = L.rows_tp(T) * Yt_local.shape[1]
+    sq_local = sq if sq is not None else ops.rows_sumsq(Yt_local, B, row_elems, row_elems)
+    if group is None:
+        return GatheredRows(Yt_local, sq_local, B, 0, slot)
     import torch.distributed as dist
-    from .distributed import side_group
-    Tp, Cp, dev, dt = L.rows_tp(T), Yt_local.shape[1], Yt_local.device, Yt_local.dtype
+    from .distributed import emulated_world, side_group
+    state = state or _DEFAULT_STATE
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    Tp, dev = L.rows_tp(T), Yt_local.device
+    held, remote = world, None                  # the buffer holds the rows of `held` ranks, the gather lands those of `world`
+    if world == 1 and emulated_world() > 1:
+        held = emulated_world()
+        remote = _emulated_remote(state, B, held, Yt_local.shape[1], T, Yt_local.dtype, dev)
+    slot = _ring_rows(state, ring_key, B * held, Yt_local.shape[1], T, Yt_local.dtype, dev)
+    rows, sq_all = slot.buf, torch.empty(B * held, dtype=torch.float32, device=dev)
+    bulk = side_group("gather", group)          # own communicator: must not queue in front of the BatchNorm all-reduces
+    w1 = dist.all_gather_into_tensor(rows[: B * world * Tp], Yt_local[: B * Tp], group=bulk, async_op=async_op)
+    w2 = dist.all_gather_into_tensor(sq_all[: B * world], sq_local, group=bulk, async_op=async_op)
+    if remote is not None:
+        if EMULATE_COPY_REMOTE or slot.gen == 1:
+            rows[B * Tp: held * B * Tp].copy_(remote[0])
+        sq_all[B:].copy_(remote[1])
+    return GatheredRows(rows, sq_all, B * held, rank * B, slot, [w1, w2] if async_op else [])
+
+
+def _emulated_remote(state: LossState, B, W, Cp, T, dt, dev):
+    """The resident (rows, norms) that stand in for the W - 1 other ranks of an emulated world: seeded N(0, 1) rows packed by
+    sda_pack_rows, norms by sda_rows_sumsq, made once per shape."""
+    Tp = L.rows_tp(T)
     key = ("remote", B, W, Cp, T, dt, str(dev))
     rem = state.emulated.get(key)
     if rem is None:
@@ -181,16 +223,7 @@ def _gather_emulated(Yt_local, ysq_local, B, T, group, W, async_op, state: LossS
             rows[k * B * Tp: (k + 1) * B * Tp].copy_(tmp[: B * Tp])
             nsq[k * B: (k + 1) * B] = ops.rows_sumsq(tmp, B, Tp * Cp, Tp * Cp)
         rem = state.emulated[key] = (rows, nsq)
-    slot = _ring_rows(state, "loss.Yall", B * W, Cp, T, dt, dev)
-    Yt = slot.buf
-    ysq = torch.empty(B * W, dtype=torch.float32, device=dev)
-    bulk = side_group("gather", group)
-    w1 = dist.all_gather_into_tensor(Yt[: B * Tp], Yt_local[: B * Tp], group=bulk, async_op=async_op)
-    w2 = dist.all_gather_into_tensor(ysq[:B], ysq_local, group=bulk, async_op=async_op)
-    if EMULATE_COPY_REMOTE or slot.gen == 1:
-        Yt[B * Tp: W * B * Tp].copy_(rem[0])
-    ysq[B:].copy_(rem[1])
-    return Yt, ysq, B * W, 0, B * W, ([w1, w2] if async_op else []), slot
+    return rem
 
 
 _prefetch_streams = {}    # device -> side stream the speech-side work runs on
@@ -207,7 +240,10 @@ def prefetch_speech(Y: torch.Tensor, dtype=None, global_negatives: bool = True, 
     dtype = dtype or torch.float32
     state = state or _DEFAULT_STATE
     group = _dist_group() if global_negatives else None
-    done = None
+
+    def pack_and_gather() -> GatheredRows:
+        Yt_local, slot = _pack_ring(state, Y, B, F, T, dtype, "x (speech embeddings)", "loss.Y")
+        return gather_speech_rows(Yt_local, B, T, group, async_op=True, state=state, slot=slot)
     if PREFETCH_ON_SIDE_STREAM and Y.is_cuda:
         main = torch.cuda.current_stream(Y.device)
         side = _prefetch_streams.get(str(Y.device))
@@ -217,28 +253,22 @@ def prefetch_speech(Y: torch.Tensor, dtype=None, global_negatives: bool = True, 
         ev.record(main)
         side.wait_event(ev)                       # Y itself, and the previous user of the ring buffer, are on `main`
         with torch.cuda.stream(side):
-            Yt_local, slot = as_rows(Y, B, F, T, dtype, "x (speech embeddings)", ring_key="loss.Y", state=state, want_slot=True)
-            Yt, ysq, Bm, col0, Bg, works, slot = gather_speech_rows(Yt_local, B, T, group, async_op=True, state=state, slot=slot)
-            done = torch.cuda.Event()
-            done.record(side)
-        ysq.record_stream(main)
+            g = pack_and_gather()
+            g.done = torch.cuda.Event()
+            g.done.record(side)
+        g.sq.record_stream(main)
     else:
-        Yt_local, slot = as_rows(Y, B, F, T, dtype, "x (speech embeddings)", ring_key="loss.Y", state=state, want_slot=True)
-        Yt, ysq, Bm, col0, Bg, works, slot = gather_speech_rows(Yt_local, B, T, group, async_op=True, state=state, slot=slot)
-    state.prefetched.clear()
-    state.prefetched.append((weakref.ref(Y), dtype, Yt, ysq, Bm, col0, Bg, works, done, slot))
+        g = pack_and_gather()
+    state.pending = Pending(weakref.ref(Y), dtype, g)
 
 
-def _take_prefetched(state: LossState, Y, dtype):
-    for wy, dt, Yt, ysq, Bm, col0, Bg, works, done, slot in state.prefetched:
-        if wy() is Y and dt == dtype:
-            state.prefetched.clear()
-            if done is not None:
-                torch.cuda.current_stream(Yt.device).wait_event(done)
-            for work in works:
-                work.wait()                     # current stream waits for RCCL's stream; the host does not block
-            return Yt, ysq, Bm, col0, Bg, slot
-    return None
+def _take_prefetched(state: LossState, Y, dtype) -> Optional[GatheredRows]:
+    p = state.pending
+    if p is None or p.y_ref() is not Y or p.dtype != dtype:
+        return None
+    state.pending = None
+    p.rows.wait()
+    return p.rows
 
 
 _RECYCLED = ("CLIPLoss.backward: the packed {what} rows of this forward were recycled by later forwards of the same CLIPLoss "
@@ -269,33 +299,28 @@ class _ClipFn(torch.autograd.Function):
                 if emulated_world() > 1:
                     raise L.SdaError("CLIPLoss: the emulated world (stand-in rows for the other ranks) has no gradient for the "
                                      "speech embeddings; detach x or run real ranks")
-        pre = _take_prefetched(state, Y, dtype)
-        if pre is not None:
-            Yt, ysq, Bm, col0, Bg, slot = pre
-        else:
-            Yt_local, slot = as_rows(Y, B, F, T, dtype, "x (speech embeddings)", ring_key="loss.Y", state=state, want_slot=True)
-            Yt, ysq, Bm, col0, Bg, _, slot = gather_speech_rows(Yt_local, B, T, group, state=state, slot=slot)
-        loss, logits, cnt, cctx = E.clip_forward(Yt, Zt, temp.detach(), Bm=Bm, Bn=B, T=T, col0=col0,
-                                                 reduction=module.reduction, B_global=Bg, dist_group=group, ysq=ysq)
+        yg = _take_prefetched(state, Y, dtype)
+        if yg is None:
+            Yt_local, slot = _pack_ring(state, Y, B, F, T, dtype, "x (speech embeddings)", "loss.Y")
+            yg = gather_speech_rows(Yt_local, B, T, group, state=state, slot=slot)
+        loss, logits, cnt, cctx = clip.clip_forward(yg.rows, Zt, temp.detach(), Bm=yg.n, Bn=B, T=T, col0=yg.col0,
+                                                    reduction=module.reduction, B_global=yg.n, dist_group=group, ysq=yg.sq)
         ctx.z_gather = None
         if want_y and group is not None:
             # the speech-side gradient contracts over the brain rows of ALL ranks: gather them (and their norms) now, behind
             # the rest of the step; backward waits for it
-            Zall, zsq_all, _, _, _, works, zslot = gather_speech_rows(Zt, B, T, group, async_op=True, state=state,
-                                                                      ring_key="loss.Zall", sq=cctx.zsq)
-            ctx.z_gather = (Zall, zsq_all, works, zslot)
+            ctx.z_gather = gather_speech_rows(Zt, B, T, group, async_op=True, state=state, ring_key="loss.Zall", sq=cctx.zsq)
         if group is not None:
             # one collective for both: the rank counts (exact in fp32) and the loss share -> global loss for
             # reporting (backward uses the local share)
             both = torch.cat([cnt.to(torch.float32), loss.reshape(1)])
             dist.all_reduce(both, group=group)
             cnt, loss = both[:-1].round().to(torch.int32), both[-1:]
-        ctx.cctx, ctx.shape, ctx.dtype, ctx.group = cctx, (B, F, T), dtype, group
+        ctx.cctx, ctx.shape, ctx.dtype, ctx.group, ctx.y_slot = cctx, (B, F, T), dtype, group, yg.slot
         ctx.set_materialize_grads(False)            # no zero-filled gradient for the (non-differentiable) logits output
-        ctx.y_slot = slot
         ctx.z_requires_grad = Z.requires_grad
         ctx.y_requires_grad, ctx.y_rows, ctx.y_dtype = want_y, y_rows, Y.dtype
-        _cache_ranks(Y, Z, cnt[col0: col0 + B])
+        _cache_ranks(Y, Z, cnt[yg.col0: yg.col0 + B])
         ctx.mark_non_differentiable(logits)
         return loss.reshape(()), logits
 
@@ -313,7 +338,7 @@ class _ClipFn(torch.autograd.Function):
             # a buffer of its own per backward (two pending backwards must not share one): the GEMM rewrites every sample's
             # rows, pad rows included (exact zeros), so only the slack behind the last sample needs a fill
             dZt = ops.new_rows_uninit(B, T, c.Zt.shape[1], ctx.dtype, c.Zt.device)
-            E.clip_backward(c, dZt, scale.reshape(1).contiguous())     # dloss folded into the GEMM epilogue
+            clip.clip_backward(c, dZt, scale.reshape(1).contiguous())     # dloss folded into the GEMM epilogue
             dZ = ops.rows_view(dZt, B, F, T)
         if ctx.y_requires_grad:
             dYt = _clip_dy(ctx, scale.reshape(1).contiguous())
@@ -324,25 +349,24 @@ class _ClipFn(torch.autograd.Function):
 
 def _clip_dy(ctx, scale: torch.Tensor) -> torch.Tensor:
     """The speech-side gradient of this rank's own rows as a fresh row-layout buffer (the buffer contract of the encoder's
-    outputs: pad rows, slack and pad channels zero).  One process: engine.clip_backward_y.  Data parallelism: the coefficient
+    outputs: pad rows, slack and pad channels zero).  One process: clip.clip_backward_y.  Data parallelism: the coefficient
     block of every rank is all-gathered (Gy rows of the brain samples, partial row sums), and this rank contracts its own
     speech columns against the gathered brain rows — the rows one process would compute on the global batch."""
     c = ctx.cctx
     B, F, T = ctx.shape
     dYt = ops.new_rows_uninit(B, T, c.Yt.shape[1], ctx.dtype, c.Yt.device)
     if ctx.group is None:
-        E.clip_backward_y(c, dYt, scale)
+        clip.clip_backward_y(c, dYt, scale)
         return dYt
     import torch.distributed as dist
     from .distributed import side_group
     world, rank = dist.get_world_size(ctx.group), dist.get_rank(ctx.group)
-    Zall, zsq_all, works, zslot = ctx.z_gather
-    for work in works:
-        work.wait()
-    if not zslot.valid():
+    zg = ctx.z_gather
+    zg.wait()
+    if not zg.slot.valid():
         raise L.SdaError(_RECYCLED.format(what="brain"))
     Bg, sp = c.Bm, L.pad_channels(B)
-    Gy, part = ops.clip_grad_y(c.logits, c.row_lse, c.col_lse, c.zsq, zsq_all, c.col0, ctx.dtype, seg=B, seg_pitch=sp,
+    Gy, part = ops.clip_grad_y(c.logits, c.row_lse, c.col_lse, c.zsq, zg.sq, c.col0, ctx.dtype, seg=B, seg_pitch=sp,
                                groups=world)
     Gall = torch.empty((Bg + 1, world * sp), dtype=ctx.dtype, device=Gy.device)
     ops.fill_zero_(Gall[Bg])                        # the zero row behind the contraction
@@ -350,9 +374,9 @@ def _clip_dy(ctx, scale: torch.Tensor) -> torch.Tensor:
     bulk = side_group("gather", ctx.group)
     dist.all_gather_into_tensor(Gall[:Bg], Gy[:B], group=bulk)
     dist.all_gather_into_tensor(pall, part, group=bulk)
-    rscale_y, cscale_y = ops.clip_grad_y_finish(pall, c.ysq, zsq_all, c.temp, c.inv_norm, rank * B, B)
+    rscale_y, cscale_y = ops.clip_grad_y_finish(pall, c.ysq, zg.sq, c.temp, c.inv_norm, rank * B, B)
     Yown = c.Yt[rank * B * L.rows_tp(T):]           # this rank's rows of the gathered speech buffer
-    ops.clip_dz(Gall[:, rank * sp:(rank + 1) * sp], Zall, Yown, dYt, rscale_y, cscale_y, Bm=Bg, Bn=B, row_elems=c.row_elems,
+    ops.clip_dz(Gall[:, rank * sp:(rank + 1) * sp], zg.rows, Yown, dYt, rscale_y, cscale_y, Bm=Bg, Bn=B, row_elems=c.row_elems,
                 out_scale=scale)
     return dYt
 
@@ -412,12 +436,13 @@ def retrieval_ranks(Y: torch.Tensor, Z: torch.Tensor, global_candidates: bool = 
     Yt = as_rows(Y, B, F, T, dtype, "Y")
     temp = torch.zeros(1, dtype=torch.float32, device=Zt.device)
     group = _dist_group() if global_candidates else None     # under data parallelism: the GLOBAL batch
-    Yt, ysq, Bm, col0, Bg, _, _ = gather_speech_rows(Yt, B, T, group)
-    _, _, cnt, _ = E.clip_forward(Yt, Zt, temp, Bm=Bm, Bn=B, T=T, col0=col0, B_global=Bg, dist_group=group, ysq=ysq)
+    yg = gather_speech_rows(Yt, B, T, group)
+    _, _, cnt, _ = clip.clip_forward(yg.rows, Zt, temp, Bm=yg.n, Bn=B, T=T, col0=yg.col0, B_global=yg.n, dist_group=group,
+                                     ysq=yg.sq)
     if group is not None:
         import torch.distributed as dist
         dist.all_reduce(cnt, group=group)
-    return cnt[col0: col0 + B]
+    return cnt[yg.col0: yg.col0 + B]
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -357,16 +357,16 @@ def test_pack_rows_and_gather_samples(ops, dtype, C, T, B):
 @pytest.mark.parametrize("B,F,T", [(6, 48, 130), (3, 300, 129), (12, 1000, 40)])
 def test_clip_dz_rows(ops, dtype, B, F, T):
     """The loss's embedding gradient dZ (CLIPLoss.backward writes it into new_rows_uninit)."""
-    from speech_decoding_amd import engine as E
+    from speech_decoding_amd import clip
     L = _L()
     g = torch.Generator().manual_seed(B + F)
     Fp = L.pad_channels(F)
     Y = q(torch.randn(B, F, T, generator=g), dtype)
     Yt, Zt = rows_of(ops, Y, dtype), rows_of(ops, q(0.3 * Y + torch.randn(B, F, T, generator=g), dtype), dtype)
-    _, _, _, ctx = E.clip_forward(Yt, Zt, torch.tensor([2.0], device=DEV), Bm=B, Bn=B, T=T)
+    _, _, _, ctx = clip.clip_forward(Yt, Zt, torch.tensor([2.0], device=DEV), Bm=B, Bn=B, T=T)
 
     def launch(o, s):
-        E.clip_backward(ctx, o["dZ"])
+        clip.clip_backward(ctx, o["dZ"])
     run_both(ops, B, T, [("dZ", Fp, dtype, [(0, F)])], [], launch)
 
 

@@ -256,12 +256,12 @@ def test_dz_dtemp_loss_bits_do_not_depend_on_x_requiring_grad(dtype):
 
 
 def test_x_without_grad_never_calls_the_new_entry_points(monkeypatch):
-    from speech_decoding_amd import engine, ops
+    from speech_decoding_amd import clip as clip_schedule, ops
 
     def boom(*a, **k):
         raise AssertionError("speech-side gradient kernel called although x needs no gradient")
 
-    for mod, name in ((ops, "clip_grad_y"), (ops, "clip_grad_y_finish"), (ops, "unpack_rows"), (engine, "clip_backward_y")):
+    for mod, name in ((ops, "clip_grad_y"), (ops, "clip_grad_y_finish"), (ops, "unpack_rows"), (clip_schedule, "clip_backward_y")):
         monkeypatch.setattr(mod, name, boom)
     x = randn(6, 64, 40, seed=31).to(DEV)
     y = randn(6, 64, 40, seed=32).to(DEV).requires_grad_(True)

@@ -690,7 +690,7 @@ def test_spatial_attention_weights_forward_backward(ops, dtype, D1, K, C, gemm):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("B,F,T", [(6, 32, 40), (24, 64, 100), (130, 64, 20)])
 def test_clip_loss_forward_backward_and_ranks(ops, dtype, B, F, T):
-    from speech_decoding_amd import engine as E, lib as L
+    from speech_decoding_amd import clip, lib as L
     g = torch.Generator().manual_seed(B)
     Y = q(torch.randn(B, F, T, generator=g), dtype)
     Z = q(0.3 * Y + torch.randn(B, F, T, generator=g), dtype).requires_grad_(True)
@@ -698,13 +698,13 @@ def test_clip_loss_forward_backward_and_ranks(ops, dtype, B, F, T):
     loss, logits = O.clip_loss(Y, Z, temp)
     loss.backward()
     Yt, Zt = to_rows(ops, Y, dtype), to_rows(ops, Z.detach(), dtype)
-    lg, lgts, cnt, ctx = E.clip_forward(Yt, Zt, temp.detach().to(DEV), Bm=B, Bn=B, T=T)
+    lg, lgts, cnt, ctx = clip.clip_forward(Yt, Zt, temp.detach().to(DEV), Bm=B, Bn=B, T=T)
     lt = dict(rtol=1e-4, atol=1e-4) if dtype == torch.float32 else dict(rtol=3e-2, atol=3e-2)
     np.testing.assert_allclose(lgts.cpu().numpy(), logits.detach().numpy(), **lt)
     assert abs(float(lg) - float(loss)) < (1e-4 if dtype == torch.float32 else 3e-2)
     assert abs(float(ctx.dtemp) - float(temp.grad)) < (1e-4 if dtype == torch.float32 else 3e-2) * max(1.0, abs(float(temp.grad)))
     dZt = ops.new_rows(B, T, L.pad_channels(F), dtype, DEV)
-    E.clip_backward(ctx, dZt)
+    clip.clip_backward(ctx, dZt)
     dz = from_rows(ops, dZt, B, F, T)
     scale = float(Z.grad.abs().max())
     assert float((dz - Z.grad).abs().max()) <= (2e-4 if dtype == torch.float32 else 3e-2) * scale

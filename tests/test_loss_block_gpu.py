@@ -1,7 +1,7 @@
 """The loss block of the data-parallel configurations at FULL size, on one GPU.
 
 Under data parallelism every rank computes the logits block of ALL global speech rows against ITS OWN brain columns
-(`engine.clip_block_stats`), the per-row soft-max statistics are merged across ranks (`distributed.combine_row_stats`, the
+(`clip.clip_block_stats`), the per-row soft-max statistics are merged across ranks (`distributed.combine_row_stats`, the
 arithmetic behind the one small all-gather), and each rank then forms its share of the loss, the gradient coefficient
 matrix and the gradient of its own embeddings (`clip_block_finish`, `clip_backward`).  BASELINE.json configs[2] makes that
 block 2048 speech rows x 256 local columns with a contraction of 1024 x 360 = 368 640 per pair; configs[4] 4096 x 512 with
@@ -44,7 +44,7 @@ def test_global_negative_loss_block_at_full_size(name, world, Bn, T, dtype, dist
     """distinct = ranks whose brain columns are their own data (None: all); the other ranks all hold the SAME block of
     columns (their positives still differ: rank r's column j pairs with speech row r * Bn + j), so the CPU pays for
     len(distinct) + 1 similarity blocks instead of `world` while the GPU runs every rank's full-size block."""
-    from speech_decoding_amd import engine as E
+    from speech_decoding_amd import clip
     from speech_decoding_amd import lib as L
     from speech_decoding_amd import loss as sda_loss
     from speech_decoding_amd import ops
@@ -74,7 +74,7 @@ def test_global_negative_loss_block_at_full_size(name, world, Bn, T, dtype, dist
     row_elems = L.rows_tp(T) * Yt.shape[1]
     ysq = ops.rows_sumsq(Yt, Bg, row_elems, row_elems)
     Zt = {r: sda_loss.as_rows(b.float(), Bn, F, T, tdt, "Z") for r, b in blocks.items()}
-    stats = [E.clip_block_stats(Yt, Zt[src_of[r]], temp, Bm=Bg, Bn=Bn, T=T, col0=r * Bn, ysq=ysq) for r in range(world)]
+    stats = [clip.clip_block_stats(Yt, Zt[src_of[r]], temp, Bm=Bg, Bn=Bn, T=T, col0=r * Bn, ysq=ysq) for r in range(world)]
     row_lse, diag = combine_row_stats(torch.stack([torch.stack([s.row_max, s.row_sum, s.diag]) for s in stats]))
     loss = torch.zeros(1, device=DEV)
     dtemp = torch.zeros(1, device=DEV)
@@ -88,7 +88,7 @@ def test_global_negative_loss_block_at_full_size(name, world, Bn, T, dtype, dist
     gscale = fp16_scale_for(Bg, T) if dtype == "fp16" else 1.0
     one = torch.full((1,), gscale, dtype=torch.float32, device=DEV)
     for r in range(world):
-        share, lg, c, cctx = E.clip_block_finish(stats[r], row_lse, diag, B_global=Bg)
+        share, lg, c, cctx = clip.clip_block_finish(stats[r], row_lse, diag, B_global=Bg)
         loss += share
         dtemp += cctx.dtemp
         cnt += c
@@ -96,7 +96,7 @@ def test_global_negative_loss_block_at_full_size(name, world, Bn, T, dtype, dist
         if r in check:
             dZt = torch.empty((L.rows_alloc(Bn, T), Yt.shape[1]), dtype=tdt, device=DEV)
             dZt[Bn * L.rows_tp(T):].zero_()
-            E.clip_backward(cctx, dZt, one)
+            clip.clip_backward(cctx, dZt, one)
             dZ[r] = ops.rows_view(dZt, Bn, F, T).float().cpu().reshape(Bn, N) / gscale
             assert float(dZt[: L.ROW_PAD].float().abs().max()) == 0.0          # pad rows come out as exact zeros
     torch.cuda.synchronize()

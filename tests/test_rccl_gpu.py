@@ -62,7 +62,7 @@ WORKER = textwrap.dedent("""
     # ---- bench.py --emulate-world: one rank behaving as rank 0 of W (distributed.emulate_world): the loss sees W * B speech
     # rows — its own through the real all-gather, (W - 1) * B resident stand-ins — and must equal the engine's block form on
     # exactly those rows (the tiled embedding gradient included: 288 speech rows x 96 columns, bf16)
-    from speech_decoding_amd import CLIPLoss, engine as E, lib as L, ops
+    from speech_decoding_amd import CLIPLoss, clip, lib as L, ops
     from speech_decoding_amd import loss as sda_loss
     from speech_decoding_amd.distributed import emulate_world
     class A(dict):
@@ -82,9 +82,9 @@ WORKER = textwrap.dedent("""
     Yall = ops.new_rows(W * B, T, F, torch.bfloat16, DEV)
     ops.pack_rows(Yl, Yall)
     Yall[B * Tp: W * B * Tp].copy_(rows)
-    share, logits, cnt, cctx = E.clip_forward(Yall, Zt, lossf.temp.detach(), Bm=W * B, Bn=B, T=T, col0=0, B_global=W * B)
+    share, logits, cnt, cctx = clip.clip_forward(Yall, Zt, lossf.temp.detach(), Bm=W * B, Bn=B, T=T, col0=0, B_global=W * B)
     dZt = ops.new_rows(B, T, F, torch.bfloat16, DEV)
-    E.clip_backward(cctx, dZt, torch.ones(1, device=DEV))
+    clip.clip_backward(cctx, dZt, torch.ones(1, device=DEV))
     torch.cuda.synchronize()
     assert abs(float(loss) - float(share)) <= 1e-6 * max(1.0, abs(float(share))), (float(loss), float(share))
     assert torch.equal(lossf.last_logits, logits) and tuple(logits.shape) == (W * B, B)

@@ -14,7 +14,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from speech_decoding_amd import engine as E, lib as L, ops  # noqa: E402
+from speech_decoding_amd import clip, lib as L, ops  # noqa: E402
 
 
 class Args(dict):
@@ -63,7 +63,7 @@ def one(B, F, T, dtype, iters, dev="cuda:0"):
     ops.pack_rows(Y, Yt)
     Zt = zbuf.detach()
     temp = crit.temp.detach()
-    _, _, _, c = E.clip_forward(Yt, Zt, temp, Bm=B, Bn=B, T=T)
+    _, _, _, c = clip.clip_forward(Yt, Zt, temp, Bm=B, Bn=B, T=T)
 
     def coefs():
         Gy, part = ops.clip_grad_y(c.logits, c.row_lse, c.col_lse, c.zsq, c.zsq, 0, dtype)

@@ -2,7 +2,7 @@
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from speech_decoding_amd import ops, engine as E, lib as L
+from speech_decoding_amd import ops, clip, lib as L
 
 def timeit(fn, n=10, warm=2):
     for _ in range(warm): fn()
@@ -23,9 +23,9 @@ for Bm, Bn in [(256, 256), (2048, 256)]:
     print(f"Bm={Bm} Bn={Bn}")
     print("  rows_sumsq(Y) %.1f us" % timeit(lambda: ops.rows_sumsq(Yt, Bm, re, re)))
     print("  sim gemm     %.1f us  (%.0f TF)" % ((t := timeit(lambda: ops.matmul_nt_splitk(Yt, Zt, Bm, Bn, re, re))), 2.0 * Bm * Bn * re / t / 1e6))
-    loss, logits, cnt, ctx = E.clip_forward(Yt, Zt, temp, Bm=Bm, Bn=Bn, T=T)
-    print("  clip_forward total %.1f us" % timeit(lambda: E.clip_forward(Yt, Zt, temp, Bm=Bm, Bn=Bn, T=T)))
+    loss, logits, cnt, ctx = clip.clip_forward(Yt, Zt, temp, Bm=Bm, Bn=Bn, T=T)
+    print("  clip_forward total %.1f us" % timeit(lambda: clip.clip_forward(Yt, Zt, temp, Bm=Bm, Bn=Bn, T=T)))
     dZ = ops.new_rows(Bn, T, F, dt, dev)
-    print("  dZ gemm      %.1f us  (%.0f TF)" % ((t := timeit(lambda: E.clip_backward(ctx, dZ))), 2.0 * Bm * Bn * re / t / 1e6))
+    print("  dZ gemm      %.1f us  (%.0f TF)" % ((t := timeit(lambda: clip.clip_backward(ctx, dZ))), 2.0 * Bm * Bn * re / t / 1e6))
     X = torch.randn(Bn, F, T, device=dev)
     print("  pack_rows(Y local) %.1f us" % timeit(lambda: ops.pack_rows(X, Zt)))

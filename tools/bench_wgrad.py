@@ -3,7 +3,7 @@ the two 1x1 ones (conv_final1 / conv_final2) and the loss's dZ product.  SDA_WGR
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from speech_decoding_amd import ops, engine as E, lib as L
+from speech_decoding_amd import ops, clip, lib as L
 
 def timeit(fn, n=20, warm=3):
     for _ in range(warm): fn()
@@ -36,9 +36,9 @@ for Bm, Bn in [(256, 256), (2048, 256)]:
     ops.rows_view(Yt, Bm, F, T).normal_(); ops.rows_view(Zt, Bn, F, T).normal_()
     temp = torch.tensor([5.1], device=dev)
     re = L.rows_tp(T) * F
-    loss, logits, cnt, ctx = E.clip_forward(Yt, Zt, temp, Bm=Bm, Bn=Bn, T=T)
+    loss, logits, cnt, ctx = clip.clip_forward(Yt, Zt, temp, Bm=Bm, Bn=Bn, T=T)
     dZ = ops.new_rows(Bn, T, F, dt, dev)
-    t = timeit(lambda: E.clip_backward(ctx, dZ))
+    t = timeit(lambda: clip.clip_backward(ctx, dZ))
     print(f"dZ gemm Bm={Bm} Bn={Bn}: {t:8.1f} us  ({2.0 * Bm * Bn * re / t / 1e6:.0f} TF, {(Bm + 2 * Bn) * re * 2 / t / 1e6:.2f} TB/s algorithmic)", flush=True)
     t = timeit(lambda: ops.matmul_nt_splitk(Yt, Zt, Bm, Bn, re, re))
     print(f"similarity Bm={Bm} Bn={Bn}: {t:8.1f} us  ({2.0 * Bm * Bn * re / t / 1e6:.0f} TF, {(Bm + Bn) * re * 2 / t / 1e6:.2f} TB/s algorithmic)", flush=True)
