@@ -18,8 +18,8 @@ import numpy as np
 import torch
 
 from . import lib as L
+from . import layers
 from . import ops
-from .engine import block_dilations, subject_segments
 
 FWD_FLAGS = L.CONV_PAIR_TILES            # the forward k = 3 convs of the encoder: two tiles per workgroup share a weight slab
 BWD_FLAGS = L.CONV_WAVE_PRIO             # the data-gradient convs of the encoder's backward
@@ -46,16 +46,13 @@ def _new(B: int, T: int, Cp: int, dtype, dev) -> torch.Tensor:
 
 def _segments(B: int, dy, x):
     """Sample segments of the weight-gradient launch of (dy, x): consecutive samples, a multiple of 8 segments (one per XCD round)."""
-    # (64-column tiles for kernel size 1 as well, not the kernel's 128-column tile there: kept for bit-stability)
-    nseg = ops.uniform_segment_count(B, ops.wgrad_ntiles(dy.shape[1], x.shape[1], 64))
-    return ops.UPLOADER.upload("blocks.seg", ops.uniform_segment_edges(B, nseg), dy.device), nseg
+    nseg = layers.uniform_nseg(B, dy.shape[1], x.shape[1])
+    return ops.UPLOADER.upload("blocks.seg", layers.uniform_segment_edges(B, nseg), dy.device), nseg
 
 
 def _wgrad(dy, x, B, T, KS, dil, Cout, Cin, glu_half=0, glu_half_p=0) -> torch.Tensor:
     """Parameter-layout weight gradient (Cout, Cin, KS) fp32 of a conv with output gradient dy and input x (RL buffers)."""
-    seg, nseg = _segments(B, dy, x)
-    slabs = ops.wgrad_gemm(dy, x, B=B, T=T, KS=KS, dil=dil, seg_start=seg, nseg=nseg, alg_dims=(Cin, Cout), flat_rows=True)
-    return ops.reduce_unpack_wgrad(slabs, Cout, Cin, KS, glu_half=glu_half, glu_half_p=glu_half_p)
+    return layers.conv_wgrad(dy, x, B, T, KS, dil, Cout, Cin, *_segments(B, dy, x), glu_half=glu_half, glu_half_p=glu_half_p)
 
 
 def _plans(module, dev, build):
@@ -100,11 +97,8 @@ def sa_backward(sa, c: SACtx, dY: torch.Tensor, want_x: bool, want_z: bool):
     dX = ops.input_grad(dY, c.Wp, None, c.B, Cc, c.T, c.x_dtype) if want_x else None
     dz = None
     if want_z:
-        seg, nseg = _segments(c.B, dY, c.Xt)
-        dWd = ops.reduce_slabs(ops.wgrad_gemm(dY, c.Xt, B=c.B, T=c.T, KS=1, dil=0, seg_start=seg, nseg=nseg))
-        cosT, sinT = sa.transposed_tables()
-        _, tab_b = sa.gemm_tables()
-        dz = ops.sa_weights_backward(dWd, c.W, c.mask, cosT, sinT, sa.z.shape[1], bwd_table=tab_b)
+        dz = layers.sa_z_grad(dY, c.Xt, c.B, c.T, *_segments(c.B, dY, c.Xt), c.W, c.mask, *sa.transposed_tables(), sa.z.shape[1],
+                              sa.gemm_tables()[1])
     return dX, dz
 
 
@@ -131,11 +125,7 @@ def _sb_plans(sb):
     D1p = L.pad_channels(sb.D1)
 
     def build(f, b):
-        f.add_weight("sb_w", sb.conv.weight, D1p, D1p)
-        f.add_vector("sb_b", sb.conv.bias, D1p)
-        f.add_weight("subj_w", sb.subject_layer.weight, D1p, D1p)
-        b.add_weight("sb_w", sb.conv.weight, D1p, D1p, mode=1)
-        b.add_weight("subj_w", sb.subject_layer.weight, D1p, D1p, mode=1)
+        layers.add_subject_block_packs(f, b, sb.conv.weight, sb.conv.bias, sb.subject_layer.weight, D1p)
         return f, b
     return _plans(sb, sb.conv.weight.device, build)
 
@@ -160,11 +150,9 @@ def subject_block_forward(sb, X: torch.Tensor, sidx: np.ndarray, mask, need_grad
         return y, None
     c = SBCtx(SACtx(B, T, Xt, W, Wp, mask, X.dtype), h_sa, h_c, widx)
     if want_subj_grad:
-        # samples sorted by subject, each subject's run cut into r slices so that the launch keeps ~ops.WGRAD_TARGET_WGS workgroups
-        # (64-column tiles; the engine's three-conv SubjectBlock counts 128 where D1p allows: kept apart for bit-stability)
-        r = ops.subject_slices(B, max(1, int(np.unique(sidx).size)), ops.wgrad_ntiles(D1p, D1p, 64))
-        perm, seg = subject_segments(sidx, S, r)
-        c.subj = (ops.UPLOADER.upload("blocks.subj_perm", perm, dev), ops.UPLOADER.upload("blocks.subj_seg", seg, dev), r)
+        plan = layers.subject_plan(sidx, S, *layers.subject_tiles_blocks(D1p))
+        c.subj = (ops.UPLOADER.upload("blocks.subj_perm", plan.perm, dev), ops.UPLOADER.upload("blocks.subj_seg", plan.seg_start, dev),
+                  plan.r)
     return y, c
 
 
@@ -176,11 +164,7 @@ def subject_block_backward(sb, c: SBCtx, dY: torch.Tensor, want: Dict[str, bool]
     D1p = L.pad_channels(D1)
     g: Dict[str, torch.Tensor] = {}
     if want["subj_w"]:
-        perm, seg, r = c.subj
-        slabs = ops.wgrad_gemm(dY, c.h_c, B=B, T=T, KS=1, dil=0, perm=perm, seg_start=seg, nseg=r * S, flat_rows=True)
-        if r > 1:
-            slabs = ops.reduce_slabs(slabs.view(r, -1)).view(S, 1, D1p, D1p)
-        g["subj_w"] = ops.unpack_conv_wgrad(slabs, S, D1, D1, 1, D1p, D1p)
+        g["subj_w"] = layers.subject_wgrad(dY, c.h_c, B, T, *c.subj, S, D1)
     if not (want["sb_w"] or want["sb_b"] or want["z"] or want["X"]):
         return g
     pkT = _sb_plans(sb)[1].run(_sb_sources(sb))
@@ -223,19 +207,9 @@ class CBCtx:
 
 
 def _cb_plans(cb):
-    D2 = cb.D2
-    D2p, cin_p = L.pad_channels(D2), L.pad_channels(cb.in_channels)
-    glu = dict(glu_half=D2, glu_half_p=D2p)
-
     def build(f, b):
-        for j, conv in ((0, cb.conv0), (1, cb.conv1)):
-            ci_p = cin_p if j == 0 else D2p
-            f.add_weight(f"c{j}w", conv.weight, D2p, ci_p)
-            f.add_vector(f"c{j}b", conv.bias, D2p)
-            b.add_weight(f"c{j}w", conv.weight, D2p, ci_p, mode=1)
-        f.add_weight("c2w", cb.conv2.weight, 2 * D2p, D2p, **glu)
-        f.add_vector("c2b", cb.conv2.bias, 2 * D2p, **glu)
-        b.add_weight("c2w", cb.conv2.weight, 2 * D2p, D2p, mode=1, **glu)
+        layers.add_conv_block_packs(f, b, "", [(c.weight, c.bias) for c in (cb.conv0, cb.conv1, cb.conv2)], cb.D2,
+                                    L.pad_channels(cb.in_channels))
         return f, b
     return _plans(cb, cb.conv0.weight.device, build)
 
@@ -251,7 +225,7 @@ def conv_block_forward(cb, X: torch.Tensor, need_grad: bool):
     B, Cc, T = X.shape
     dt, dev, D2 = cb.compute_dtype, X.device, cb.D2
     D2p = L.pad_channels(D2)
-    dil = block_dilations(cb.k)
+    dil = layers.block_dilations(cb.k)
     x, x_rows = rows_in(X, Cc, dt)
     pk = _cb_plans(cb)[0].run(_cb_sources(cb))
     hs, as_, bns = [], [], []
@@ -292,7 +266,7 @@ def conv_block_backward(cb, c: CBCtx, dY: torch.Tensor, want: Dict[str, bool]) -
     _check_versions(c)
     B, T, dt, dev, D2 = c.B, c.T, cb.compute_dtype, dY.device, cb.D2
     D2p, cin, cin_p = L.pad_channels(D2), cb.in_channels, L.pad_channels(cb.in_channels)
-    dil = block_dilations(cb.k)
+    dil = layers.block_dilations(cb.k)
     scratch = ops.reduce_scratch(2 * D2p, dev)
     g: Dict[str, torch.Tensor] = {}
     dc2 = _new(B, T, 2 * D2p, dt, dev)

@@ -17,13 +17,9 @@ import numpy as np
 import torch
 
 from . import lib as L
+from . import layers
 from . import ops
 from .clip import ClipBlockStats, ClipCtx, clip_backward, clip_backward_y, clip_block_finish, clip_block_stats, clip_forward  # noqa: F401
-
-
-def block_dilations(k: int):
-    """models.py:133,141,149"""
-    return 2 ** ((2 * k) % 5), 2 ** ((2 * k + 1) % 5), 2
 
 
 @dataclass
@@ -175,19 +171,14 @@ class _Backward:
         if not self.pg:
             return None
         B, T, eng = self.B, self.T, self.eng
-        # (64-column tiles for kernel size 1 too, not the kernel's 128-column tile there: kept for bit-stability)
-        perm, seg, nseg = eng._uniform_segments(B, ops.wgrad_ntiles(dy.shape[1], x.shape[1], 64), self.dev)
+        nseg = layers.uniform_nseg(B, dy.shape[1], x.shape[1])
+        _, seg = eng._uniform_segments(B, nseg, self.dev)
         if self.side is not None and not eng.reuse_workspace:
             # without the persistent workspace, dy is a buffer of this backward that is freed as soon as the loop moves on,
             # and the next main-stream allocation may take its memory before the side stream has read it
             dy.record_stream(self.side)
             x.record_stream(self.side)
-
-        def chain():
-            slabs = ops.wgrad_gemm(dy, x, B=B, T=T, KS=KS, dil=dil, perm=perm, seg_start=seg, nseg=nseg,
-                                   alg_dims=(Cin, Cout), flat_rows=True)
-            return ops.reduce_unpack_wgrad(slabs, Cout, Cin, KS, **glu)
-        return self.on_side(chain)
+        return self.on_side(lambda: layers.conv_wgrad(dy, x, B, T, KS, dil, Cout, Cin, seg, nseg, **glu))
 
     def dgrad(self, dy, key, out, KS, dil, res=None, widx=None, bn=None):
         """Data-gradient conv of the layer whose weight is P[key].  bn = (h, coef): `out` is the gradient entering
@@ -302,13 +293,12 @@ class EncoderEngine:
         self._ws_shapes.clear()
         self._seg_cache.clear()
 
-    def _uniform_segments(self, B: int, ntiles: int, device):
-        nseg = ops.uniform_segment_count(B, ntiles)
+    def _uniform_segments(self, B: int, nseg: int, device):
+        """(perm, seg_start) on `device` of `nseg` runs of consecutive samples (perm None: no permutation table), made once."""
         key = (B, nseg, str(device))
         if key not in self._seg_cache:
-            self._seg_cache[key] = (None, torch.from_numpy(ops.uniform_segment_edges(B, nseg)).to(device))
-        perm, seg = self._seg_cache[key]
-        return perm, seg, nseg
+            self._seg_cache[key] = (None, torch.from_numpy(layers.uniform_segment_edges(B, nseg)).to(device))
+        return self._seg_cache[key]
 
     @property
     def composed(self) -> bool:
@@ -341,24 +331,12 @@ class EncoderEngine:
             return self._fwd_plan, self._bwd_plan
         d = self.d
         f, b = ops.PackPlan(self.dtype, dev), ops.PackPlan(self.dtype, dev)
-        glu = dict(glu_half=d.D2, glu_half_p=d.D2p)
-        glu_fwd = dict(glu, glu_tile=80) if self.glu_fused else glu      # SDA_EPI_GLU's 80 value + 80 gate channels per tile
+        glu_tile = 80 if self.glu_fused else 0      # SDA_EPI_GLU's 80 value + 80 gate channels per tile
         if not self.composed:                # (the composed SubjectBlock builds its per-subject operand itself)
-            f.add_weight("sb_w", P["sb_w"], d.D1p, d.D1p)
-            f.add_vector("sb_b", P["sb_b"], d.D1p)
-            f.add_weight("subj_w", P["subj_w"], d.D1p, d.D1p)
-            b.add_weight("sb_w", P["sb_w"], d.D1p, d.D1p, mode=1)
-            b.add_weight("subj_w", P["subj_w"], d.D1p, d.D1p, mode=1)
+            layers.add_subject_block_packs(f, b, P["sb_w"], P["sb_b"], P["subj_w"], d.D1p)
         for k in range(5):
-            cin_p = d.D1p if k == 0 else d.D2p
-            for j in (0, 1):
-                ci_p = cin_p if j == 0 else d.D2p
-                f.add_weight(f"b{k}.c{j}w", P[f"b{k}.c{j}w"], d.D2p, ci_p)
-                f.add_vector(f"b{k}.c{j}b", P[f"b{k}.c{j}b"], d.D2p)
-                b.add_weight(f"b{k}.c{j}w", P[f"b{k}.c{j}w"], d.D2p, ci_p, mode=1)
-            f.add_weight(f"b{k}.c2w", P[f"b{k}.c2w"], 2 * d.D2p, d.D2p, **glu_fwd)
-            f.add_vector(f"b{k}.c2b", P[f"b{k}.c2b"], 2 * d.D2p, **glu_fwd)
-            b.add_weight(f"b{k}.c2w", P[f"b{k}.c2w"], 2 * d.D2p, d.D2p, mode=1, **glu)
+            layers.add_conv_block_packs(f, b, f"b{k}.", [(P[f"b{k}.c{j}w"], P[f"b{k}.c{j}b"]) for j in range(3)], d.D2,
+                                        d.D1p if k == 0 else d.D2p, glu_tile)
         f.add_weight("f1w", P["f1w"], d.F1p, d.D2p)
         f.add_vector("f1b", P["f1b"], d.F1p)
         f.add_weight("f2w", P["f2w"], d.Fp, d.F1p)
@@ -410,32 +388,16 @@ class EncoderEngine:
         per-subject weight gradient."""
         d, ctx = self.d, f.ctx
         B = ctx.B
-        # subject indices: CPU int tensor in the reference (train.py:189); validate like ModuleList indexing
-        sidx = torch.as_tensor(subject_idxs).detach().to("cpu").to(torch.int64).numpy()
-        if sidx.shape != (B,):
-            raise ValueError("subject_idxs must have shape (B,)")
-        if (sidx < 0).any() or (sidx >= d.S).any():
-            raise IndexError("subject index out of range")                # ModuleList semantics, models.py:115
+        sidx = layers.subject_indices(subject_idxs, B, d.S)
         up = ops.UPLOADER.upload                # pinned staging: no implicit host<->stream synchronisation
         ctx.widx = up(("widx", "train" if f.need_grad else "eval"), sidx.astype(np.int32), f.dev)
         if not (f.need_grad and ctx.param_grads):
             return
-        # per-subject weight gradient: samples sorted by subject, one K-segment per (slice j, subject s) in
-        # j-major order.  With many subjects one slice each is enough (the S segments already fill the GPU);
-        # with few (S = 1 in configs 1/4) every subject's samples are cut into r slices so that the launch still
-        # has ~WGRAD_TARGET_WGS workgroups, and the r slabs of a subject are summed afterwards in fixed order.
-        if self.composed:       # the per-subject gradient is the k = 3 one of (block 0's dh0, X): D2p x 64-channel tiles
-            ntiles = ops.wgrad_ntiles(d.D2p, d.Cp, 64)
-        else:
-            # (the kernel's 128-column tile of kernel size 1 where D1p allows; blocks.py counts 64 here: kept for bit-stability)
-            ntiles = ops.wgrad_ntiles(d.D1p, d.D1p, 128 if d.D1p % 128 == 0 else 64)
-        # (sized by the subjects PRESENT in the batch: a batch drawn from a few recordings — 8 of 27 subjects — otherwise
-        # runs the launch on a third of its workgroups: +0.3 ms per step, measured with the resident feed in round 5)
-        r = ops.subject_slices(B, max(1, int(np.unique(sidx).size)), ntiles)
-        perm, seg = subject_segments(sidx, d.S, r)
-        ctx.subj_perm = up("subj_perm", perm, f.dev)
-        ctx.subj_seg = up("subj_seg", seg, f.dev)
-        ctx.subj_slices = r
+        tiles = layers.subject_tiles_composed(d.D2p, d.Cp) if self.composed else layers.subject_tiles_three_conv(d.D1p)
+        plan = layers.subject_plan(sidx, d.S, *tiles)
+        ctx.subj_perm = up("subj_perm", plan.perm, f.dev)
+        ctx.subj_seg = up("subj_seg", plan.seg_start, f.dev)
+        ctx.subj_slices = plan.r
 
     def _fwd_pack(self, f: _Forward, X):
         """Operand packing (fp32 master weights -> compute dtype, K-contiguous, zero padded): ONE launch per plan, and X's layout
@@ -514,7 +476,7 @@ class EncoderEngine:
         """ConvBlock k (models.py:152-166) on input x.  Returns its output."""
         d, ctx, P, dev = self.d, f.ctx, f.P, f.dev
         B, T, pk, bufs, k3_flags, count = ctx.B, ctx.T, ctx.packed, ctx.bufs, f.k3_flags, f.count
-        dil = block_dilations(k)
+        dil = layers.block_dilations(k)
         for j in (0, 1):
             alg = (d.D1 if (k == 0 and j == 0) else d.D2, d.D2)
             pre = f"b{k}.c{j}"
@@ -679,7 +641,7 @@ class EncoderEngine:
         d, ctx, P, grads, pg = self.d, b.ctx, b.P, b.grads, b.pg
         B, T, bufs, scratch, world = b.B, b.T, ctx.bufs, b.scratch, b.world
         cin, cin_p = (d.D1, d.D1p) if k == 0 else (d.D2, d.D2p)
-        dil = block_dilations(k)
+        dil = layers.block_dilations(k)
         glu = dict(glu_half=d.D2, glu_half_p=d.D2p)       # (c2's bias gradient: a kernel when D2 is not a multiple of 64)
         dc2 = b.tmp(f"dc2.{k}", 2 * d.D2p)      # per-layer buffers: a side-stream wgrad may still read them
         if not pg:
@@ -755,7 +717,7 @@ class EncoderEngine:
         #   dL/dW_tot[s] = sum_tap W0[tap]^T M[s][tap],   M[s][tap] = sum_{b in s, t} dh0[b, t] (x) X[b, t + (tap - 1) dil]
         # = the per-subject kernel-3 weight gradient of (dh0, X) followed by one batched (D1 x 3 D2) . (3 D2 x C+1) product:
         # neither conv0's data gradient (a 320 -> 320 kernel-3 conv) nor a weight gradient over dx0 is computed.
-        M = ops.wgrad_gemm(dh0, ctx.bufs["Xt"], B=B, T=T, KS=3, dil=block_dilations(0)[0], perm=ctx.subj_perm,
+        M = ops.wgrad_gemm(dh0, ctx.bufs["Xt"], B=B, T=T, KS=3, dil=layers.block_dilations(0)[0], perm=ctx.subj_perm,
                            seg_start=ctx.subj_seg, nseg=r * d.S, flat_rows=True)     # (r*S, 3, D2p, Cp); column C: the folded bias
         if r > 1:
             M = ops.reduce_slabs(M.view(r, -1))
@@ -780,16 +742,9 @@ class EncoderEngine:
         """Backward of the SubjectBlock run as its three convs, from dhs (rows, D1p), block 0's input gradient."""
         d, ctx, P, grads, pg = self.d, b.ctx, b.P, b.grads, b.pg
         B, T, bufs = b.B, b.T, ctx.bufs
-
-        def subj_wgrad():
-            r = ctx.subj_slices
-            slabs = ops.wgrad_gemm(dhs, bufs["h_c"], B=B, T=T, KS=1, dil=0, perm=ctx.subj_perm, seg_start=ctx.subj_seg,
-                                   nseg=r * d.S, flat_rows=True)   # (r*S, 1, D1p, D1p), slice-major
-            if r > 1:
-                slabs = ops.reduce_slabs(slabs.view(r, -1)).view(d.S, 1, d.D1p, d.D1p)
-            return ops.unpack_conv_wgrad(slabs, d.S, d.D1, d.D1, 1, d.D1p, d.D1p)
         if pg:
-            grads["subj_w"] = b.on_side(subj_wgrad)
+            grads["subj_w"] = b.on_side(lambda: layers.subject_wgrad(dhs, bufs["h_c"], B, T, ctx.subj_perm, ctx.subj_seg,
+                                                                     ctx.subj_slices, d.S, d.D1))
         dh_c, _ = b.dgrad(dhs, "subj_w", b.tmp("dh_c", d.D1p), 1, 0, widx=ctx.widx)
         if pg:
             grads["sb_w"] = b.wgrad(dh_c, bufs["h_sa"], 1, 0, d.D1, d.D1)
@@ -800,31 +755,8 @@ class EncoderEngine:
             grads["X"] = ops.input_grad(dh_sa, ctx.W_x, None, B, d.C, T, ctx.x_dtype)
         if not pg:
             return
-        # (64-column tiles for this kernel-size-1 launch, not the kernel's 128-column tile: kept for bit-stability)
-        perm, seg, nseg = self._uniform_segments(B, ops.wgrad_ntiles(d.D1p, d.Cp, 64), b.dev)
-        dWd = ops.reduce_slabs(ops.wgrad_gemm(dh_sa, bufs["Xt"], B=B, T=T, KS=1, dil=0, perm=perm, seg_start=seg, nseg=nseg))
-        grads["z"] = ops.sa_weights_backward(dWd, ctx.W_sa, ctx.mask, P["cosT"], P["sinT"], P["z"].shape[1],
-                                             bwd_table=P.get("sa_tab_b"))
-
-
-def subject_segments(sidx: np.ndarray, S: int, r: int):
-    """K-segments of the per-subject weight gradient: samples sorted by subject (stable), each subject's run cut
-    into `r` nearly equal slices, segments listed slice-major (segment j*S + s = slice j of subject s) so that the
-    r slabs of one subject are `r` equally strided blocks for the ordered slab sum.
-    Returns (perm int32 [B], seg_start int32 [r*S + 1])."""
-    order = np.argsort(sidx, kind="stable").astype(np.int32)
-    bounds = np.searchsorted(sidx[order], np.arange(S + 1)).astype(np.int64)
-    lo, hi = bounds[:-1], bounds[1:]
-    cuts = [lo + ((hi - lo) * j) // r for j in range(r + 1)]              # r + 1 arrays of S cut points
-    seg = np.empty(r * S + 1, dtype=np.int32)
-    parts, pos = [], 0
-    for j in range(r):
-        for s in range(S):
-            a_, b_ = int(cuts[j][s]), int(cuts[j + 1][s])
-            seg[j * S + s] = pos
-            parts.append(order[a_:b_])
-            pos += b_ - a_
-    seg[r * S] = pos
-    perm = np.concatenate(parts).astype(np.int32) if parts else order
-    return perm, seg
+        nseg = layers.uniform_nseg(B, d.D1p, d.Cp)
+        _, seg = self._uniform_segments(B, nseg, b.dev)
+        grads["z"] = layers.sa_z_grad(dh_sa, bufs["Xt"], B, T, seg, nseg, ctx.W_sa, ctx.mask, P["cosT"], P["sinT"], P["z"].shape[1],
+                                      P.get("sa_tab_b"))
 

@@ -20,7 +20,8 @@ import torch.nn as nn
 
 from . import lib as L
 from . import ops
-from .engine import EncoderDims, EncoderEngine, block_dilations
+from .engine import EncoderDims, EncoderEngine
+from .layers import block_dilations, subject_indices
 from .layout import ch_locations_2d
 from . import loss as _loss
 from . import blocks as _blocks
@@ -63,16 +64,6 @@ def _check_input(X, who: str, channels: int):
         raise L.SdaError(f"{who} needs X on the MI355X device (there is no CPU path)")
     if X.dtype not in ops.COMPUTE_DTYPES:
         raise L.SdaError(f"{who}: X of dtype {X.dtype}; the module takes float32, bfloat16 or float16")
-
-
-def _subject_indices(subject_idxs, B: int, S: int) -> np.ndarray:
-    """subject_idxs validated as the encoder validates them (a CPU int tensor in the reference, train.py:189)."""
-    sidx = torch.as_tensor(subject_idxs).detach().to("cpu").to(torch.int64).numpy()
-    if sidx.shape != (B,):
-        raise ValueError("subject_idxs must have shape (B,)")
-    if (sidx < 0).any() or (sidx >= S).any():
-        raise IndexError("subject index out of range")                # ModuleList semantics, models.py:115
-    return sidx
 
 
 class _SpatialAttentionFn(torch.autograd.Function):
@@ -275,7 +266,7 @@ class SubjectBlock(nn.Module):
     def forward(self, X: torch.Tensor, subject_idxs) -> torch.Tensor:
         sa = self.spatial_attention
         _check_input(X, "SubjectBlock", sa.loc.shape[0])
-        sidx = _subject_indices(subject_idxs, X.shape[0], self.num_subjects)
+        sidx = subject_indices(subject_idxs, X.shape[0], self.num_subjects)
         mask = sa.dropout_mask(X.device)                     # the one draw of this call, through its SpatialAttention
         params = [sa.z, self.conv.weight, self.conv.bias, self.subject_layer.weight]
         grad_mode = torch.is_grad_enabled()

@@ -814,45 +814,14 @@ def colsum(x, B, T, scratch):
     return out
 
 
-# ---- launch planning of the weight gradients.  These numbers decide slab counts and therefore summation order (result bits):
-# the encoder's step (engine.py), the stand-alone blocks (blocks.py) and the tools all take them from here.
-WGRAD_TARGET_WGS = 256      # workgroups per weight-gradient launch, split over sample segments: one per CU, a sharp optimum
-                            # (160 +0.37 ms, 512 +0.2)
-
-
 def wgrad_tile_m(Cout_p: int) -> int:
     """Row tile sda_wgrad_gemm picks for Cout_p output channels."""
     return L.load().sda_wgrad_tile_m(Cout_p)
 
 
-def wgrad_ntiles(Cout_p: int, Cin_p: int, tile_n: int = 64) -> int:
-    """Output tiles of one segment AS THE CALLER'S PLANNING COUNTS THEM: row tiles x (Cin_p / tile_n).  The kernel's own column
-    tile is 64 for kernel size 3 and 128 for kernel size 1 (Cin_p % 128 == 0); most call sites count 64 for both."""
-    return (Cout_p // wgrad_tile_m(Cout_p)) * (Cin_p // tile_n)
-
-
 def splitk_tile_co(Np: int) -> int:
     """Tile AS splitk_plan COUNTS IT, kept for bit-stability (it decides ksplit): at Np = 640 the kernel, conv_tile_co(Np, 1), takes 128."""
     return 160 if Np % 160 == 0 else (128 if Np % 128 == 0 else 64)
-
-
-def uniform_segment_count(B: int, ntiles: int) -> int:
-    """Sample segments of a weight-gradient launch with `ntiles` tiles per segment."""
-    # segments are dealt round-robin to the 8 XCDs (wgrad_gemm's block order), so use a multiple of 8
-    nseg = 8 * max(1, round(WGRAD_TARGET_WGS / (8 * max(1, ntiles))))
-    return int(min(B, nseg)) if B >= 8 else int(max(1, min(B, nseg)))
-
-
-def uniform_segment_edges(B: int, nseg: int) -> np.ndarray:
-    """int32 [nseg + 1] edges of `nseg` nearly equal runs of consecutive samples (no permutation: the kernel then needs no index
-    load in its chunk loop)."""
-    return np.floor(np.linspace(0, B, nseg + 1)).astype(np.int32)
-
-
-def subject_slices(B: int, present: int, ntiles: int) -> int:
-    """Slices r each subject's samples are cut into for the per-subject weight gradient (`present` subjects in the batch, `ntiles`
-    tiles per segment): with many subjects one slice each fills the GPU; with few, r slices keep ~WGRAD_TARGET_WGS workgroups."""
-    return int(max(1, min(max(1, B // present), round(WGRAD_TARGET_WGS / max(1, ntiles * present)))))
 
 
 def bias_grad(cs, C, glu_half=0, glu_half_p=0):

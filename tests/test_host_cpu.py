@@ -98,7 +98,7 @@ def test_layout_normalisation():
 
 @pytest.fixture(scope="module")
 def lib():
-    """The built library: the row tile ops.wgrad_ntiles counts with is asked of it."""
+    """The built library: the row tile layers.wgrad_ntiles counts with is asked of it."""
     from speech_decoding_amd import lib as L
     if not os.path.exists(L.LIB_PATH):
         import __graft_entry__ as g
@@ -107,31 +107,73 @@ def lib():
 
 
 def test_uniform_and_subject_segments(lib):
-    from speech_decoding_amd import ops
-    from speech_decoding_amd.engine import EncoderDims, EncoderEngine, block_dilations
-    assert [block_dilations(k) for k in range(5)] == [(1, 2, 2), (4, 8, 2), (16, 1, 2), (2, 4, 2), (8, 16, 2)]
+    from speech_decoding_amd import layers
+    from speech_decoding_amd.engine import EncoderDims, EncoderEngine
+    assert [layers.block_dilations(k) for k in range(5)] == [(1, 2, 2), (4, 8, 2), (16, 1, 2), (2, 4, 2), (8, 16, 2)]
     eng = EncoderEngine(EncoderDims(208, 27, 270, 320, 1024, 32))
     for B, ntiles in [(256, 10), (7, 1), (256, 80), (3, 1000)]:
-        perm, seg, nseg = eng._uniform_segments(B, ntiles, "cpu")
+        nseg = layers.uniform_segment_count(B, ntiles)
+        perm, seg = eng._uniform_segments(B, nseg, "cpu")
         seg = seg.numpy()
         assert seg[0] == 0 and seg[-1] == B and len(seg) == nseg + 1 and (np.diff(seg) >= 0).all()
         assert perm is None                                   # consecutive samples: no permutation table
-        assert (nseg, seg.tolist()) == (ops.uniform_segment_count(B, ntiles), ops.uniform_segment_edges(B, nseg).tolist())
+        assert (nseg, seg.tolist()) == (layers.uniform_segment_count(B, ntiles), layers.uniform_segment_edges(B, nseg).tolist())
     d = eng.d
     assert (d.Cp, d.D1p, d.D2p, d.F1p, d.Fp) == (256, 320, 320, 640, 1024)
     # Slices per subject of the per-subject weight gradient, (B, subjects present) -> r, as each call site planned them before
-    # the arithmetic moved to ops.py (they decide slab counts, so result bits): the engine's composed SubjectBlock counts
+    # the arithmetic moved to one place (they decide slab counts, so result bits): the engine's composed SubjectBlock counts
     # D2p x Cp tiles of the k = 3 gradient, its three-conv form and blocks.py D1p x D1p tiles of the 1 x 1 one
+    slices = lambda B, present, tiles: layers.subject_slices(B, present, layers.wgrad_ntiles(*tiles))
     for C, cases in [(60, {(64, 1): (64, 26), (512, 1): (128, 26)}),                                  # BASELINE configs 1, 4
                      (208, {(256, 27): (1, 1), (256, 7): (5, 4), (256, 1): (32, 26)}),                # config 2
                      (306, {(512, 100): (1, 1), (512, 25): (1, 1), (512, 1): (26, 26)})]:             # config 5
         Cp = -(-C // 64) * 64
         for (B, present), (r_composed, r_three) in cases.items():
-            assert ops.subject_slices(B, present, ops.wgrad_ntiles(d.D2p, Cp, 64)) == r_composed
-            assert ops.subject_slices(B, present, ops.wgrad_ntiles(d.D1p, d.D1p, 128 if d.D1p % 128 == 0 else 64)) == r_three    # engine
-            assert ops.subject_slices(B, present, ops.wgrad_ntiles(d.D1p, d.D1p, 64)) == r_three                                 # blocks
-    # where D1p is a multiple of 128 the two three-conv call sites count different column tiles, on purpose (bit-stability)
-    assert ops.subject_slices(64, 1, ops.wgrad_ntiles(256, 256, 128)) == 64 and ops.subject_slices(64, 1, ops.wgrad_ntiles(256, 256, 64)) == 32
+            assert slices(B, present, layers.subject_tiles_composed(d.D2p, Cp)) == r_composed
+            assert slices(B, present, layers.subject_tiles_three_conv(d.D1p)) == r_three         # engine
+            assert slices(B, present, layers.subject_tiles_blocks(d.D1p)) == r_three             # blocks
+    # where D1p is a multiple of 128 the two three-conv call sites count different column tiles, on purpose
+    assert slices(64, 1, layers.subject_tiles_three_conv(256)) == 64 and slices(64, 1, layers.subject_tiles_blocks(256)) == 32
+
+
+def test_engine_and_standalone_modules_plan_the_same_operand_packs(lib):
+    """The encoder's pack-plan entries of ConvBlock k and of the SubjectBlock's two convs are the stand-alone modules' own, key
+    for key (without the engine's `b{k}.` prefix) and field for field, except glu_tile: only the engine runs F.glu in conv2's
+    epilogue.  Built on CPU tensors: no device, no launch."""
+    from types import SimpleNamespace as NS
+    from speech_decoding_amd import blocks
+    from speech_decoding_amd.engine import EncoderDims, EncoderEngine
+    d = EncoderDims(208, 27, 270, 320, 1024, 32)
+    shapes = {"sb_w": (d.D1, d.D1, 1), "sb_b": (d.D1,), "subj_w": (d.S, d.D1, d.D1, 1), "f1w": (d.F1, d.D2, 1), "f1b": (d.F1,),
+              "f2w": (d.F, d.F1, 1), "f2b": (d.F,)}
+    for k in range(5):
+        shapes.update({f"b{k}.c0w": (d.D2, d.D1 if k == 0 else d.D2, 3), f"b{k}.c1w": (d.D2, d.D2, 3), f"b{k}.c2w": (2 * d.D2, d.D2, 3),
+                       f"b{k}.c0b": (d.D2,), f"b{k}.c1b": (d.D2,), f"b{k}.c2b": (2 * d.D2,)})
+    P = {n: torch.empty(s) for n, s in shapes.items()}
+    eng = EncoderEngine(d)
+    eng.compose_subject_block = False                     # (the composed SubjectBlock packs no sb_w / subj_w operand)
+    assert eng.glu_fused
+
+    def entries(plan, prefix="", keys=None):
+        found = {key[len(prefix):]: (dict(f), dst.shape, dst.dtype) for key, _, dst, f in plan.items
+                 if key.startswith(prefix) and (keys is None or key in keys)}
+        return [(key, {n: v for n, v in f.items() if n != "glu_tile"}, shape, dt) for key, (f, shape, dt) in found.items()], \
+               {key: f["glu_tile"] for key, (f, _, _) in found.items()}
+
+    conv = lambda w, b: NS(weight=w, bias=b)
+    for k in (0, 1):
+        cb = NS(k=k, D2=d.D2, in_channels=d.D1 if k == 0 else d.D2, compute_dtype=eng.dtype,
+                conv0=conv(P[f"b{k}.c0w"], P[f"b{k}.c0b"]), conv1=conv(P[f"b{k}.c1w"], P[f"b{k}.c1b"]),
+                conv2=conv(P[f"b{k}.c2w"], P[f"b{k}.c2b"]))
+        for mine, alone in zip(eng._plans(P, "cpu"), blocks._cb_plans(cb)):
+            (got, got_tile), (want, want_tile) = entries(mine, f"b{k}."), entries(alone)
+            assert got == want and len(want) == (6 if mine is eng._fwd_plan else 3)
+            assert set(want_tile.values()) == {0}
+            assert got_tile == {key: 80 if mine is eng._fwd_plan and key.startswith("c2") else 0 for key in want_tile}
+    sb = NS(D1=d.D1, compute_dtype=eng.dtype, conv=conv(P["sb_w"], P["sb_b"]), subject_layer=NS(weight=P["subj_w"]))
+    for mine, alone in zip(eng._plans(P, "cpu"), blocks._sb_plans(sb)):
+        got, want = entries(mine, keys=("sb_w", "sb_b", "subj_w")), entries(alone)
+        assert got == want and len(want[0]) == (3 if mine is eng._fwd_plan else 2)
 
 
 def test_bn_gelu_backward_refuses_dg_without_statistics_before_any_launch(lib):
@@ -149,7 +191,7 @@ def test_bn_gelu_backward_refuses_dg_without_statistics_before_any_launch(lib):
 def test_subject_segments_partition_the_batch_slice_major(S, r, B):
     """Per-subject weight-gradient segments: every sample appears once, segment j*S + s holds only subject s,
     the r slices of a subject cover it in order and differ in size by at most one."""
-    from speech_decoding_amd.engine import subject_segments
+    from speech_decoding_amd.layers import subject_segments
     rng = np.random.default_rng(S * 100 + r)
     sidx = rng.integers(0, S, size=B).astype(np.int64)
     if S > 2:

@@ -3,7 +3,7 @@ the two 1x1 ones (conv_final1 / conv_final2) and the loss's dZ product.  SDA_WGR
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from speech_decoding_amd import ops, clip, lib as L
+from speech_decoding_amd import ops, clip, layers, lib as L
 
 def timeit(fn, n=20, warm=3):
     for _ in range(warm): fn()
@@ -22,10 +22,11 @@ for (cin, cout, KS, dil, wgs) in [(320, 320, 3, 4, 256), (320, 320, 3, 4, 512), 
                                   (640, 1024, 1, 0, 256), (640, 1024, 1, 0, 512), (320, 640, 1, 0, 256), (256, 320, 3, 1, 256)]:
     x = ops.new_rows(B, T, cin, dt, dev); x.normal_()
     dy = ops.new_rows(B, T, cout, dt, dev); dy.normal_()
-    ntiles = ops.wgrad_ntiles(cout, cin, 64 if KS == 3 else (128 if cin % 128 == 0 else 64))    # the kernel's own column tile
-    ops.WGRAD_TARGET_WGS = wgs                   # (this sweep varies the target the step keeps at 256)
-    nseg = ops.uniform_segment_count(B, ntiles)
-    seg = torch.from_numpy(ops.uniform_segment_edges(B, nseg)).to(dev)
+    tile_n = 64 if KS == 3 else (128 if cin % 128 == 0 else 64)     # the kernel's own column tile
+    ntiles = layers.wgrad_ntiles(cout, cin, tile_n)
+    layers.WGRAD_TARGET_WGS = wgs                # (this sweep varies the target the step keeps at 256)
+    nseg = layers.uniform_nseg(B, cout, cin, tile_n)
+    seg = torch.from_numpy(layers.uniform_segment_edges(B, nseg)).to(dev)
     fl = 2.0 * B * T * KS * cin * cout
     us = timeit(lambda: ops.wgrad_gemm(dy, x, B=B, T=T, KS=KS, dil=dil, perm=None, seg_start=seg, nseg=nseg, flat_rows=True))
     print(f"wgrad {cin:4d}->{cout:4d} k{KS} tiles {ntiles:3d} nseg {nseg:3d} ({ntiles * nseg:4d} wgs) {us:8.1f} us  {fl / us / 1e6:7.1f} TF", flush=True)

@@ -10,7 +10,7 @@ wall time per (one launch of each) against the sum and the maximum of the two al
 import sys, os, math
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
-from speech_decoding_amd import ops, lib as L
+from speech_decoding_amd import ops, layers, lib as L
 
 dev, dt = "cuda:0", torch.bfloat16
 B, T, C = 256, 360, 320
@@ -34,14 +34,14 @@ coef = torch.cat([gamma, beta, mean, rstd]).contiguous()
 scratch = ops.reduce_scratch(2 * C, dev)
 
 
-def seg_for(ntiles):
-    nseg = ops.uniform_segment_count(B, ntiles)
-    return torch.from_numpy(ops.uniform_segment_edges(B, nseg)).to(dev), nseg
+def seg_for(cout):
+    nseg = layers.uniform_nseg(B, cout, C)
+    return torch.from_numpy(layers.uniform_segment_edges(B, nseg)).to(dev), nseg
 
 
 def mk_w(cout):
     d = dy if cout == C else dy2
-    seg, nseg = seg_for(ops.wgrad_ntiles(cout, C, 64))
+    seg, nseg = seg_for(cout)
     return lambda: ops.wgrad_gemm(d, x, B=B, T=T, KS=3, dil=4, perm=None, seg_start=seg, nseg=nseg, flat_rows=True)
 
 
