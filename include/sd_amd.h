@@ -371,7 +371,7 @@ int sda_sa_softmax_pack(const float* a, int a_pitch, const float* mask, float* W
 int sda_sa_softmax_backward(const float* dWd, int dwd_pitch, const float* W, const float* mask, float* da,
                             int da_pitch, int D1, int C, void* stream);
 /* dWd fp32 [D1p][Cp] (from sda_wgrad_gemm) -> dz complex64 interleaved [D1][K2].
- * cosT/sinT are the transposed tables [C][K2] (constant buffers, transposed once by the host). */
+ * cosT/sinT are the transposed tables [C][K2] (constant buffers, transposed once by the host).  C <= 512 and C <= Cp. */
 int sda_sa_weights_backward(const float* dWd, const float* W, const float* mask, const float* cosT,
                             const float* sinT, float* dz, int D1, int K2, int C, int Cp, void* stream);
 
@@ -389,7 +389,8 @@ int sda_clip_logits_stats(const float* S, long s_pitch, const float* ysq, const 
  * [Bm + 1][g_pitch], the extra row and the columns >= Bn are written as zeros —, cscale[j] = inv_norm * exp(temp) /
  * (ymax |Z_j|) (the factor taken out of G: sda_wgrad_args.acc_scale of the dZ product), rscale[j] = inv_norm * sum_i D_ij
  * logits_ij / |Z_j|^2, so that dZ_j = cscale_j * sum_i G_ij Y_i - rscale_j Z_j; scalars[0] = this block's share of the loss,
- * scalars[1] = its share of dloss/dtemp.  inv_norm = 1/(2*B_global) for reduction="mean", 1/2 for "sum".  colpart: 2*Bn floats. */
+ * scalars[1] = its share of dloss/dtemp.  inv_norm = 1/(2*B_global) for reduction="mean", 1/2 for "sum".  colpart: 2*Bn floats.
+ * The block's positives are rows of it: 0 <= col0 and col0 + Bn <= Bm, or the call is refused. */
 int sda_clip_grad(const float* logits, const float* row_lse, const float* col_lse, const float* ysq,
                   const float* zsq, const float* temp, float inv_norm, int col0, void* G, long g_pitch,
                   float* rscale, float* cscale, float* colpart, float* scalars, int Bm, int Bn, int dtype, void* stream);

@@ -347,6 +347,7 @@ extern "C" int sda_sa_scratch_floats(int D1, int K2, int C) { return ((K2 + SA_M
 extern "C" int sda_sa_weights_forward(const float* z, const float* cos_t, const float* sin_t, const float* mask, float* W,
                                       void* Wp, float* scratch, int D1, int K2, int C, int D1p, int Cp, int dtype, void* stream) {
   if (!z || !cos_t || !sin_t || !W || !Wp || !scratch || C > 512 || C > Cp || D1 > D1p) { set_error("sa_weights_forward: bad arguments (C <= 512)"); return -1; }
+  if (dtype != SDA_F32 && dtype != SDA_BF16 && dtype != SDA_F16) { set_error("sa_weights_forward: unknown dtype"); return -1; }   // before the first launch
   hipStream_t st = (hipStream_t)stream;
   const int nchunk = (K2 + SA_MC - 1) / SA_MC;
   hipLaunchKernelGGL(sa_fwd_partial_kernel, dim3((D1 + SA_R - 1) / SA_R, nchunk), dim3(256), 0, st, z, cos_t, sin_t, scratch, D1, K2, C);
@@ -387,7 +388,9 @@ extern "C" int sda_sa_softmax_backward(const float* dWd, int dwd_pitch, const fl
 
 extern "C" int sda_sa_weights_backward(const float* dWd, const float* W, const float* mask, const float* cosT,
                                        const float* sinT, float* dz, int D1, int K2, int C, int Cp, void* stream) {
-  if (!dWd || !W || !cosT || !sinT || !dz || C > 512) { set_error("sa_weights_backward: bad arguments"); return -1; }
+  if (!dWd || !W || !cosT || !sinT || !dz || D1 < 1 || K2 < 1 || C < 1 || C > 512 || C > Cp) {
+    set_error("sa_weights_backward: bad arguments (C <= 512, C <= Cp)"); return -1;
+  }
   hipLaunchKernelGGL(sa_weights_bwd_kernel, dim3((D1 + SA_R - 1) / SA_R, (K2 + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      dWd, W, mask, cosT, sinT, dz, D1, K2, C, Cp);
   return check_launch("sa_weights_backward");
@@ -423,8 +426,8 @@ extern "C" int sda_clip_merge_rows(const float* all, int world, int Bg, float* l
 extern "C" int sda_clip_logits_stats(const float* S, long s_pitch, const float* ysq, const float* zsq, const float* temp,
                                      float* logits, float* row_max, float* row_sum, float* col_lse, float* diag,
                                      float* row_lse, int Bm, int Bn, int col0, void* stream) {
-  if (!S || !ysq || !zsq || !temp || !logits || !row_max || !row_sum || !col_lse || !diag || Bm < 1 || Bn < 1) {
-    set_error("clip_logits_stats: bad arguments"); return -1;
+  if (!S || !ysq || !zsq || !temp || !logits || !row_max || !row_sum || !col_lse || !diag || Bm < 1 || Bn < 1 || s_pitch < Bn) {
+    set_error("clip_logits_stats: bad arguments (Bm, Bn >= 1, s_pitch >= Bn)"); return -1;
   }
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(clip_rows_kernel, dim3(Bm), dim3(256), 0, st, S, s_pitch, ysq, zsq, temp, logits, row_max, row_sum, diag, row_lse, Bm, Bn, col0);
@@ -439,6 +442,8 @@ extern "C" int sda_clip_grad(const float* logits, const float* row_lse, const fl
   if (!logits || !row_lse || !col_lse || !ysq || !zsq || !temp || !G || !rscale || !cscale || !colpart || !scalars || g_pitch < Bn) {
     set_error("clip_grad: null argument or g_pitch < Bn"); return -1;
   }
+  // the kernel reads logits[(col0 + j) * Bn + j] and row_lse[col0 + j] for every local column j: the block's positives are rows of it
+  if (Bm < 1 || Bn < 1 || col0 < 0 || (long)col0 + Bn > Bm) { set_error("clip_grad: need Bm, Bn >= 1 and 0 <= col0, col0 + Bn <= Bm"); return -1; }
   hipStream_t st = (hipStream_t)stream;
   if (dtype == SDA_F32)
     hipLaunchKernelGGL(clip_grad_kernel<float>, dim3((unsigned)g_pitch), dim3(256), 0, st, logits, row_lse, col_lse, ysq, zsq, temp, inv_norm, col0, (float*)G, g_pitch, rscale, cscale, colpart, Bm, Bn);
@@ -488,6 +493,7 @@ extern "C" int sda_clip_grad_y_finish(const float* part, int nparts, int Bg, con
 
 extern "C" int sda_clip_ranks(const float* logits, const float* diag, int32_t* cnt, int Bm, int Bn, int col0, void* stream) {
   if (!logits || !diag || !cnt) { set_error("clip_ranks: null argument"); return -1; }
+  if (Bm < 1 || Bn < 1) { set_error("clip_ranks: need Bm, Bn >= 1"); return -1; }
   hipLaunchKernelGGL(clip_ranks_kernel, dim3(Bm), dim3(256), 0, (hipStream_t)stream, logits, diag, cnt, Bm, Bn, col0);
   return check_launch("clip_ranks");
 }
