@@ -544,13 +544,35 @@ int sda_gather_baseline_windows(const float* const* win_ptr, const long* win_cst
                                 int baseline_len, void* stream);
 
 /* ---- Frozen wav2vec 2.0 speech embedder (utils/wav2vec_util.py:14-32 calls the third-party HF Wav2Vec2Model; this is that
- * model's published forward for the layer-norm / stable-layer-norm variant xlsr-53 uses).  Every Linear, strided Conv1d and
+ * model's published forward: the layer-norm / stable-layer-norm variant xlsr-53 uses and the group-norm / post-LN variant
+ * of wav2vec2-base and -large; the host schedule in speech_decoding_amd/wav2vec2.py chooses).  Every Linear, strided Conv1d and
  * the grouped positional conv run on sda_conv_gemm (kernel size 1 on overlapping-row views); these are the other stages.
  * Activations are row-layout buffers of ONE chunk: row SDA_ROW_PAD + t = frame t. ---- */
 /* Feature-encoder layer 0: y = GELU(LayerNorm_C(Conv1d(1 -> C, K, stride)(wave) + bias)); wave fp32 [n_samples] on the
  * device, w fp32 [C][K], T = (n_samples - K) / stride + 1 frames */
 int sda_w2v_conv0(const float* wave, long n_samples, const float* w, const float* bias, const float* gamma,
                   const float* beta, void* y, int T, int C, int Cp, int K, int stride, float eps, int dtype, void* stream);
+/* Feature-encoder layer 0 of the group-norm checkpoints (feat_extract_norm = "group": wav2vec2-base, -large, -960h):
+ *     x[t][c] = Conv1d(1 -> C, K, stride)(wave) (+ bias when not NULL), fp32, never stored
+ *     y[SDA_ROW_PAD + t][c] = GELU(gamma[c] * (x[t][c] - mean_c) * rsqrt(var_c + eps) + beta[c]),  pad channels zero
+ * mean_c and the biased variance var_c run over ALL T frames of the call.  Two calls on one stream:
+ * sda_w2v_conv0_stats leaves stats = scratch[0 .. 3C): shift[C] = x[0][c], the mean of x - shift [C] (so mean_c = shift +
+ * that: two numbers, because one fp32 number cannot hold a mean of 1e4 to 1e-7 of a spread of 5), then rsqrt(var + eps)[C];
+ * sda_w2v_conv0_groupnorm reads them and computes the conv again (the same arithmetic: the same bits).  The statistics come
+ * from the unrounded fp32 conv outputs less the shift: per workgroup (a slice of max(SDA_W2V_GN_SLICE_MIN, ceil(T / SDA_W2V_GN_MAX_WG)) consecutive frames) and wave
+ * (every fourth frame of the slice) a Welford mean / sum of centred squares, merged in wave order, then in workgroup order,
+ * by Chan's formula.  No atomics, one summation order: the same input gives the same bits, eagerly or from a graph.
+ * scratch: sda_w2v_conv0_stats_floats(T, C) floats of device memory (contents irrelevant before); nothing is allocated and
+ * the host never waits.  wave fp32 [n_samples] on the device, w fp32 [C][K], T = (n_samples - K) / stride + 1 frames,
+ * C <= 1024, max(K, 8) * 64 * ceil(C / 64) * 4 bytes <= 64 KiB; offsets are 64-bit (T up to INT_MAX). */
+#define SDA_W2V_GN_SLICE_MIN 256
+#define SDA_W2V_GN_MAX_WG 1024
+long sda_w2v_conv0_stats_floats(int T, int C);
+int sda_w2v_conv0_stats(const float* wave, long n_samples, const float* w, const float* bias, float* scratch,
+                        long scratch_floats, int T, int C, int K, int stride, float eps, void* stream);
+int sda_w2v_conv0_groupnorm(const float* wave, long n_samples, const float* w, const float* bias, const float* gamma,
+                            const float* beta, const float* stats, void* y, int T, int C, int Cp, int K, int stride, int dtype,
+                            void* stream);
 /* y = LayerNorm over the C valid channels of each of T rows (biased variance, eps inside the root), affine, then GELU
  * when `gelu`; pad channels of y are written as zero.  Cp * sizeof(element) <= 4096 */
 int sda_layernorm_rows(const void* x, void* y, const float* gamma, const float* beta, int T, int C, int Cp, float eps,

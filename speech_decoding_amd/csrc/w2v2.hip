@@ -2,6 +2,8 @@
 // are not GEMMs.  Every Linear / strided Conv1d / grouped positional conv of the model runs on conv_gemm (kernel size 1
 // on overlapping-row views, see speech_decoding_amd/wav2vec2.py); this file holds
 //   * w2v_conv0_kernel      first feature-encoder layer: Conv1d(1 -> C, k, stride) + LayerNorm(C) + GELU, waveform in
+//   * conv0_stats / conv0_stats_finish / conv0_groupnorm  the same layer of the group-norm checkpoints: each channel
+//                           normalised over all frames of the call (statistics pass, finish, normalising pass)
 //   * layernorm_rows_kernel LayerNorm over the channels of each row (+ optional GELU)
 //   * group_split / group_merge_add  row layout <-> per-group row layout around the grouped positional conv
 //   * attention_kernel      softmax(Q K^T / sqrt(d)) V per head on the matrix cores, flash-style over 64-key blocks
@@ -58,6 +60,166 @@ __global__ __launch_bounds__(256) void w2v_conv0_kernel(const float* __restrict_
       const int c = lane + 64 * i;
       if (c < C) Elem<E>::st(yr + c, gelu_f<E>(fmaf((v[i] - mean) * rstd, g[i], be[i])));
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Group-norm feature encoder, layer 0 (HF Wav2Vec2GroupNormConvLayer: GroupNorm(C groups of one channel) = each channel
+// normalised over ALL T frames of the call), in three launches that never store the fp32 conv output:
+//   conv0_stats_kernel     workgroup g walks frames [g * slice, (g + 1) * slice), wave w the frames g * slice + w + 4 i in
+//                          order, lane = channels lane + 64 i; per channel a running (mean, M2) by Welford's update on
+//                          z = x - shift, x the unrounded fp32 conv output and shift = x at frame 0 of the call (every
+//                          wave computes it again); the four waves are merged in wave order (Chan) -> part[g][2][C]
+//   conv0_stats_finish     one thread per channel merges the workgroups' partials in workgroup order (Chan) ->
+//                          stats[0][c] = shift, stats[1][c] = mean of z, stats[2][c] = rsqrt(M2 / T + eps)
+//   conv0_groupnorm_kernel w2v_conv0_kernel's shape: computes the conv again (the same fmaf chain: the same bits),
+//                          y = GELU(gamma ((x - shift) - mean_z) rstd + beta), pad channels written as zero
+// Why the shift: speech with a DC offset gives channel means of 1e4 against a spread of 5; ONE fp32 number for the mean is
+// then off by up to half an ulp of 1e4 = 5e-4, 1e-4 of the spread, however it was summed.  x - shift is exact for values
+// that close, and the mean of z is a number of the spread's own size.
+// Counts are never stored: a slice's and a wave's frame counts follow from (T, slice).  No atomics; every sum has one order.
+// Weights sit in LDS as [K][64 NI] (lane-consecutive: no bank conflict), zero for channels >= C.
+// ------------------------------------------------------------------------------------------------
+constexpr int GN_SLICE_MIN = SDA_W2V_GN_SLICE_MIN;     // frames per workgroup, at least
+constexpr int GN_MAX_WG = SDA_W2V_GN_MAX_WG;           // workgroups of the statistics pass, at most
+
+__host__ __device__ inline int gn_slice(int T) {
+  const long s = ((long)T + GN_MAX_WG - 1) / GN_MAX_WG;
+  return (int)(s < GN_SLICE_MIN ? GN_SLICE_MIN : s);
+}
+
+template <int NI>
+__device__ inline void conv0_load_weights(float* wl, const float* __restrict__ w, int C, int K) {
+  constexpr int CL = 64 * NI;
+  for (int i = threadIdx.x; i < K * CL; i += 256) {
+    const int j = i / CL, c = i - j * CL;
+    wl[i] = c < C ? w[c * K + j] : 0.f;
+  }
+  __syncthreads();
+}
+
+// v[i] = bias + sum_j w[lane + 64 i][j] * xs[j], taps in order: the one arithmetic both passes share
+template <int NI>
+__device__ inline void conv0_frame(const float* wl, const float* __restrict__ xs, int K, int lane, const float (&b0)[NI],
+                                   float (&v)[NI]) {
+#pragma unroll
+  for (int i = 0; i < NI; ++i) v[i] = b0[i];
+  for (int j = 0; j < K; ++j) {
+    const float xv = xs[j];
+    const float* wr = wl + j * (64 * NI) + lane;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) v[i] = fmaf(wr[64 * i], xv, v[i]);
+  }
+}
+
+// (na, ma, qa) <- (na, ma, qa) merged with (nb, mb, qb): count, mean, sum of centred squares (Chan et al.)
+__device__ inline void chan_merge(float& na, float& ma, float& qa, float nb, float mb, float qb) {
+  if (nb == 0.f) return;
+  const float n = na + nb, d = mb - ma, r = nb / n;
+  ma = fmaf(d, r, ma);
+  qa = (qa + qb) + (d * d) * (na * r);
+  na = n;
+}
+
+template <int NI>
+__global__ __launch_bounds__(256) void conv0_stats_kernel(const float* __restrict__ wave, const float* __restrict__ w,
+                                                          const float* __restrict__ bias, float* __restrict__ shift,
+                                                          float* __restrict__ part, int T, int C, int K, int stride, int slice) {
+  constexpr int CL = 64 * NI;
+  extern __shared__ float wl[];                      // [K][CL]; once the frames are done, [4 waves][2][CL]
+  float* red = wl;
+  conv0_load_weights<NI>(wl, w, C, K);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  float b0[NI], sh[NI], mean[NI], m2[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int c = lane + 64 * i;
+    b0[i] = (c < C && bias) ? bias[c] : 0.f;
+    mean[i] = 0.f; m2[i] = 0.f;
+  }
+  conv0_frame<NI>(wl, wave, K, lane, b0, sh);
+  if (blockIdx.x == 0 && wid == 0) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+      if (lane + 64 * i < C) shift[lane + 64 * i] = sh[i];
+  }
+  const long t0 = (long)blockIdx.x * slice;
+  const long t1 = t0 + slice < (long)T ? t0 + slice : (long)T;
+  int n = 0;
+  for (long t = t0 + wid; t < t1; t += 4) {
+    float v[NI];
+    conv0_frame<NI>(wl, wave + t * stride, K, lane, b0, v);
+    const float rn = 1.0f / (float)(++n);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const float z = v[i] - sh[i];
+      const float d = z - mean[i];
+      mean[i] = fmaf(d, rn, mean[i]);
+      m2[i] = fmaf(d, z - mean[i], m2[i]);
+    }
+  }
+  __syncthreads();                                   // every wave is done with the weights
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    red[(wid * 2 + 0) * CL + lane + 64 * i] = mean[i];
+    red[(wid * 2 + 1) * CL + lane + 64 * i] = m2[i];
+  }
+  __syncthreads();
+  const int len = (int)(t1 - t0);
+  float* pg = part + (size_t)blockIdx.x * 2 * C;
+  for (int c = threadIdx.x; c < C; c += 256) {
+    float na = 0.f, ma = 0.f, qa = 0.f;
+    for (int wv = 0; wv < 4; ++wv) {
+      const int nw = len > wv ? (len - wv + 3) / 4 : 0;
+      chan_merge(na, ma, qa, (float)nw, red[(wv * 2 + 0) * CL + c], red[(wv * 2 + 1) * CL + c]);
+    }
+    pg[c] = ma;
+    pg[C + c] = qa;
+  }
+}
+
+__global__ __launch_bounds__(256) void conv0_stats_finish_kernel(const float* __restrict__ part, float* __restrict__ stats, int T,
+                                                                 int C, int slice, int n_wg, float eps) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  float na = 0.f, ma = 0.f, qa = 0.f;
+  for (int g = 0; g < n_wg; ++g) {
+    const long left = (long)T - (long)g * slice;
+    const float nb = (float)(left < slice ? left : (long)slice);
+    chan_merge(na, ma, qa, nb, part[(size_t)g * 2 * C + c], part[(size_t)g * 2 * C + C + c]);
+  }
+  stats[C + c] = ma;
+  stats[2 * C + c] = rsqrtf(qa / (float)T + eps);
+}
+
+template <typename E, int NI>
+__global__ __launch_bounds__(256) void conv0_groupnorm_kernel(const float* __restrict__ wave, const float* __restrict__ w,
+                                                              const float* __restrict__ bias, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, const float* __restrict__ stats,
+                                                              E* __restrict__ y, int T, int C, int Cp, int K, int stride) {
+  constexpr int CL = 64 * NI;
+  extern __shared__ float wl[];                      // [K][CL]
+  conv0_load_weights<NI>(wl, w, C, K);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  float b0[NI], g[NI], be[NI], sh[NI], mean[NI], rstd[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int c = lane + 64 * i;
+    const bool ok = c < C;
+    b0[i] = (ok && bias) ? bias[c] : 0.f;
+    g[i] = ok ? gamma[c] : 0.f; be[i] = ok ? beta[c] : 0.f;
+    sh[i] = ok ? stats[c] : 0.f; mean[i] = ok ? stats[C + c] : 0.f; rstd[i] = ok ? stats[2 * C + c] : 0.f;
+  }
+  for (long t = (long)blockIdx.x * 4 + wid; t < (long)T; t += (long)gridDim.x * 4) {
+    float v[NI];
+    conv0_frame<NI>(wl, wave + t * stride, K, lane, b0, v);
+    E* yr = y + (size_t)(PAD + t) * Cp;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const int c = lane + 64 * i;
+      if (c < Cp) Elem<E>::st(yr + c, c < C ? gelu_f<E>(fmaf(((v[i] - sh[i]) - mean[i]) * rstd[i], g[i], be[i])) : 0.f);
+    }
+    for (int c = CL + lane; c < Cp; c += 64) Elem<E>::st(yr + c, 0.f);
   }
 }
 
@@ -360,6 +522,63 @@ extern "C" int sda_w2v_conv0(const float* wave, long n_samples, const float* w, 
   if (ni <= 2) W2V_C0(2); else if (ni <= 8) W2V_C0(8); else W2V_C0(16);
 #undef W2V_C0
   return check_launch("w2v_conv0");
+}
+
+// shared argument rules of the two group-norm passes; LDS: max(K, 8) rows of 64 NI floats
+static bool gn_args_ok(const float* wave, long n_samples, const float* w, int T, int C, int K, int stride, int* ni, size_t* lds) {
+  if (!wave || !w || T < 1 || C < 1 || C > 1024 || K < 1 || stride < 1 || (long)(T - 1) * stride + K > n_samples) return false;
+  const int n = (C + 63) / 64;
+  *ni = n <= 1 ? 1 : (n <= 8 ? 8 : 16);
+  *lds = (size_t)(K > 8 ? K : 8) * 64 * *ni * sizeof(float);
+  return *lds <= 64 * 1024;
+}
+
+extern "C" long sda_w2v_conv0_stats_floats(int T, int C) {
+  if (T < 1 || C < 1) return -1;
+  const int slice = gn_slice(T);
+  const long n_wg = ((long)T + slice - 1) / slice;
+  return (3 + 2 * n_wg) * (long)C;
+}
+
+extern "C" int sda_w2v_conv0_stats(const float* wave, long n_samples, const float* w, const float* bias, float* scratch,
+                                   long scratch_floats, int T, int C, int K, int stride, float eps, void* stream) {
+  int ni = 0;
+  size_t lds = 0;
+  if (!gn_args_ok(wave, n_samples, w, T, C, K, stride, &ni, &lds) || !scratch || scratch_floats < sda_w2v_conv0_stats_floats(T, C)) {
+    set_error("w2v_conv0_stats: bad arguments (C <= 1024, max(K, 8) * 64 * ceil(C / 64) floats of LDS <= 64 KiB, scratch of "
+              "sda_w2v_conv0_stats_floats(T, C) floats)");
+    return -1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int slice = gn_slice(T);
+  const int n_wg = (int)(((long)T + slice - 1) / slice);
+  float* part = scratch + 3 * (size_t)C;
+#define W2V_GS(NI) hipLaunchKernelGGL((conv0_stats_kernel<NI>), dim3(n_wg), dim3(256), lds, st, wave, w, bias, scratch, part, T, C, K, \
+                                      stride, slice)
+  if (ni == 1) W2V_GS(1); else if (ni == 8) W2V_GS(8); else W2V_GS(16);
+#undef W2V_GS
+  if (check_launch("w2v_conv0_stats")) return -1;
+  hipLaunchKernelGGL(conv0_stats_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, st, part, scratch, T, C, slice, n_wg, eps);
+  return check_launch("w2v_conv0_stats(finish)");
+}
+
+extern "C" int sda_w2v_conv0_groupnorm(const float* wave, long n_samples, const float* w, const float* bias, const float* gamma,
+                                       const float* beta, const float* stats, void* y, int T, int C, int Cp, int K, int stride,
+                                       int dtype, void* stream) {
+  int ni = 0;
+  size_t lds = 0;
+  if (!gn_args_ok(wave, n_samples, w, T, C, K, stride, &ni, &lds) || !gamma || !beta || !stats || !y || C > Cp || Cp % 64 ||
+      Cp > 1024) {
+    set_error("w2v_conv0_groupnorm: bad arguments (C <= Cp <= 1024, Cp a multiple of 64, max(K, 8) * 64 * ceil(C / 64) floats "
+              "of LDS <= 64 KiB)");
+    return -1;
+  }
+  hipStream_t st = (hipStream_t)stream;
+#define W2V_GN(NI) SDA_DISPATCH(dtype, hipLaunchKernelGGL((conv0_groupnorm_kernel<E, NI>), dim3(grid_for(T, 4)), dim3(256), lds, st, \
+                                                          wave, w, bias, gamma, beta, stats, (E*)y, T, C, Cp, K, stride))
+  if (ni == 1) W2V_GN(1); else if (ni == 8) W2V_GN(8); else W2V_GN(16);
+#undef W2V_GN
+  return check_launch("w2v_conv0_groupnorm");
 }
 
 extern "C" int sda_layernorm_rows(const void* x, void* y, const float* gamma, const float* beta, int T, int C, int Cp,

@@ -108,6 +108,9 @@ SIGNATURES = {
     "sda_reduce_scratch_rows": (i32, [i32, i32]),
     "sda_glu_backward_colsum": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "sda_w2v_conv0": (i32, [vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]),
+    "sda_w2v_conv0_stats_floats": (i64, [i32, i32]),
+    "sda_w2v_conv0_stats": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32, vp]),
+    "sda_w2v_conv0_groupnorm": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "sda_layernorm_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp]),
     "sda_w2v_group_split": (i32, [vp, vp, i32, i32, i32, i32, i32, i64, i32, i32, vp]),
     "sda_w2v_group_merge_add": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i64, vp, i32, i32, vp]),

@@ -1110,6 +1110,53 @@ def w2v_conv0(wave, w, bias, gamma, beta, y, T, C, K, stride, eps=1e-5):
     return y
 
 
+INT_MAX = 2 ** 31 - 1
+
+
+def _need_conv0_frames(who: str, wave, T: int, K: int, stride: int):
+    """The frame count and the waveform of a layer-0 launch, or SdaError: T travels as a C int."""
+    if not 1 <= T <= INT_MAX - L.ROW_PAD:
+        raise L.SdaError(f"{who}: {T} frames; 1 <= frames <= {INT_MAX - L.ROW_PAD} (a C int holds the row index)")
+    _need_values(wave, torch.float32, (T - 1) * stride + K, "{}: wave is {} contiguous fp32 samples on the device", who,
+                 (T - 1) * stride + K)
+
+
+def w2v_conv0_stats_floats(T: int, C: int) -> int:
+    """Floats of scratch `w2v_conv0_stats` needs for T frames of C channels: shift[C], mean[C], rstd[C], then the workgroups' partials."""
+    if not 1 <= T <= INT_MAX - L.ROW_PAD or C < 1:
+        raise L.SdaError(f"w2v_conv0_stats_floats: {T} frames of {C} channels; 1 <= frames <= {INT_MAX - L.ROW_PAD}, channels >= 1")
+    return int(L.load().sda_w2v_conv0_stats_floats(T, C))
+
+
+def w2v_conv0_stats(wave, w, bias, scratch, T, C, K, stride, eps=1e-5):
+    """Per-channel statistics of x = Conv1d(1 -> C, K, stride)(wave) over all T frames, left in scratch[:3C]: shift = x at
+    frame 0, the mean of x - shift, rsqrt(biased variance + eps) (`sda_w2v_conv0_stats`); returns that (3, C) view.  scratch: fp32, at least
+    w2v_conv0_stats_floats(T, C) values, the caller's (one per stream in flight)."""
+    _need_conv0_frames("w2v_conv0_stats", wave, T, K, stride)
+    _need_values(w, torch.float32, C * K, "w2v_conv0_stats: w is fp32 [{}][{}] on the device", C, K)
+    _need_values(bias, torch.float32, C, "w2v_conv0_stats: bias is {} fp32 values on the device", C)
+    _need_values(scratch, torch.float32, w2v_conv0_stats_floats(T, C), "w2v_conv0_stats: scratch holds w2v_conv0_stats_floats({}, {}) fp32 "
+                 "values on the device", T, C)
+    L.check(L.load().sda_w2v_conv0_stats(_p(wave), wave.numel(), _p(w), _p(bias), _p(scratch), scratch.numel(), T, C, K, stride, eps,
+                                         _st()), "w2v_conv0_stats")
+    return scratch[:3 * C].view(3, C)
+
+
+def w2v_conv0_groupnorm(wave, w, bias, gamma, beta, stats, y, T, C, K, stride):
+    """y[ROW_PAD + t] = GELU(gamma ((conv(wave)[t] - shift) - mean) rstd + beta) with stats = the (3, C) of w2v_conv0_stats;
+    pad channels of those rows are written as zero (`sda_w2v_conv0_groupnorm`)."""
+    _need_conv0_frames("w2v_conv0_groupnorm", wave, T, K, stride)
+    _need_values(w, torch.float32, C * K, "w2v_conv0_groupnorm: w is fp32 [{}][{}] on the device", C, K)
+    for name, t in (("bias", bias), ("gamma", gamma), ("beta", beta)):
+        _need_values(t, torch.float32, C, "w2v_conv0_groupnorm: {} is {} fp32 values on the device", name, C)
+    _need_values(stats, torch.float32, 3 * C, "w2v_conv0_groupnorm: stats is fp32 [3][{}] on the device", C)
+    if not y.is_cuda or y.dim() != 2 or not y.is_contiguous() or y.shape[0] < L.ROW_PAD + T or C > y.shape[1]:
+        raise L.SdaError(f"w2v_conv0_groupnorm: y is a row-layout device buffer of at least {L.ROW_PAD + T} rows and {C} channels")
+    L.check(L.load().sda_w2v_conv0_groupnorm(_p(wave), wave.numel(), _p(w), _p(bias), _p(gamma), _p(beta), _p(stats), _p(y), T, C,
+                                             y.shape[1], K, stride, dt_code(y.dtype), _st()), "w2v_conv0_groupnorm")
+    return y
+
+
 def layernorm_rows(x, y, gamma, beta, T, C, eps=1e-5, gelu=False):
     L.check(L.load().sda_layernorm_rows(_p(x), _p(y), _p(gamma), _p(beta), T, C, x.shape[1], eps, int(gelu), dt_code(x.dtype), _st()),
             "layernorm_rows")

@@ -237,13 +237,7 @@ def speech_embeddings(embedder, wave: torch.Tensor, sample_rate: int, preprocs, 
     if preprocs["last4layers"]:
         emb = embedder.embed(wave16)                                 # (H, frames)
     else:
-        # the embedder keeps copies of its stages on request; the last feature-encoder layer is `feature_extractor`'s output
-        taps, embedder.taps = embedder.taps, {}
-        try:
-            embedder.hidden_states(wave16[0])
-            emb = embedder.taps[f"feat{len(embedder.cfg.conv_kernel) - 1}"].t()      # (C, frames)
-        finally:
-            embedder.taps = taps
+        emb = embedder.conv_features(wave16)                         # (C, frames): `feature_extractor`'s output, no transformer
     rate_after = audio_resample_rate * emb.shape[-1] / wave16.shape[-1]
     return resample_fft(emb, up=preprocs["brain_resample_rate"] / rate_after)
 
