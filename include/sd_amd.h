@@ -41,7 +41,8 @@ extern "C" {
                                   sda_stft_fft_f32 — the STFT as a power-of-two FFT;
                                   sda_conv_tile_co / sda_wgrad_tile_m — the output-channel tile rules, asked instead of mirrored;
                                   sda_sim_gemm_windows / sda_sim_gemm_windows_span / sda_window_sumsq — decoding against windows of
-                                  continuous speech tracks) */
+                                  continuous speech tracks;
+                                  sda_gather_windows — training batches gathered from such tracks) */
 #define SDA_ROW_PAD 16
 #define SDA_CH_ALIGN 64
 
@@ -263,6 +264,19 @@ int sda_fill_zero(void* p, long nbytes, void* stream);
  * embedding table kept in row layout (a sample = (T + SDA_ROW_PAD) * Cp elements, pad rows included) the gathered batch IS the
  * packed row-layout operand of the loss — no index_select + sda_pack_rows pair per step */
 int sda_gather_samples(const void* table, const long* idx, void* dst, int B, long sample_bytes, void* stream);
+/* The same batch gathered from WINDOWS of a table of plain rows (retrieval.WindowBank.table: table_rows rows of row_bytes bytes,
+ * row_bytes = pad64(F) * element size, a multiple of 128; the kernel moves bytes, so one serves bf16, fp16 and fp32):
+ *     dst sample b = SDA_ROW_PAD zero rows, then table rows starts[idx[b]] ... starts[idx[b]] + T - 1, bit for bit
+ * starts: M device int32 table rows; idx: B device int64 candidates in [0, M), any order, duplicates allowed; dst: a row-layout
+ * buffer of sda_rows_alloc(B, T) rows of row_bytes bytes.  ONE launch writes every byte of dst — the pad rows, the windows with
+ * the table's (zero) channel padding and the slack behind the last sample — so dst may arrive uninitialised, no sda_zero_pad_rows
+ * launch goes with it, and the result IS the packed row-layout operand of the loss: a track is stored once however many
+ * overlapping windows are cut from it (gwilliams2022.py materialises every window of the speech side).  Nothing outside the
+ * table is read: an idx[b] outside [0, M) or a start outside [0, table_rows - T] gives a sample of zeros and touches nothing
+ * else.  Fixed order, no atomics.  Refused before any launch: null pointers; B, T or M < 1; B > 65535; table_rows < T; row_bytes
+ * not a multiple of 128; table or dst not 16-byte aligned. */
+int sda_gather_windows(const void* table, long table_rows, const int32_t* starts, int M, const long* idx, void* dst, int B, int T,
+                       long row_bytes, void* stream);
 /* out[i] = a[i] * b[0], i < n (device scalars: e.g. d loss / d temp times the incoming gradient) */
 int sda_scalar_mul(const float* a, const float* b, float* out, int n, void* stream);
 

@@ -117,6 +117,37 @@ __global__ __launch_bounds__(256) void gather_samples_kernel(const uint4* __rest
   }
   for (; i < vecs; i += step) out[i] = src[i];
 }
+// dst sample b = the T rows from row starts[idx[b]] on of a table of plain rows (row_vec 16-byte vectors each), behind PAD zero
+// rows: a window of a resident track gathered straight into the row layout.  ONE launch writes every vector of dst — pad rows,
+// windows and the slack behind the last sample (slack_vecs, shared out over the whole grid) — so dst may arrive uninitialised.
+// A candidate outside [0, M) or a start outside [0, table_rows - T] gives a sample of zeros: nothing outside the table is read.
+// blockIdx.y = b; a window is T * row_vec contiguous vectors of the table, copied like gather_samples_kernel copies a sample.
+__global__ __launch_bounds__(256) void gather_windows_kernel(const uint4* __restrict__ table, long table_rows,
+                                                             const int* __restrict__ starts, int M, const long* __restrict__ idx,
+                                                             uint4* __restrict__ dst, int T, int row_vec, long slack_vecs) {
+  const long pad_vecs = (long)PAD * row_vec, vecs = (long)T * row_vec;
+  const long m = idx[blockIdx.y];
+  const long s = (m >= 0 && m < M) ? (long)starts[m] : -1;
+  const bool inside = s >= 0 && s <= table_rows - T;
+  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+  uint4* __restrict__ out = dst + (size_t)blockIdx.y * (pad_vecs + vecs);
+  const long first = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
+  for (long i = first; i < pad_vecs; i += step) out[i] = zero;
+  out += pad_vecs;
+  long i = first;
+  if (inside) {
+    const uint4* __restrict__ src = table + (size_t)s * row_vec;
+    for (; i + 3 * step < vecs; i += 4 * step) {            // four loads in flight per lane
+      const uint4 a = src[i], b = src[i + step], c = src[i + 2 * step], d = src[i + 3 * step];
+      out[i] = a; out[i + step] = b; out[i + 2 * step] = c; out[i + 3 * step] = d;
+    }
+    for (; i < vecs; i += step) out[i] = src[i];
+  } else {
+    for (; i < vecs; i += step) out[i] = zero;
+  }
+  uint4* __restrict__ slack = dst + (size_t)gridDim.y * (pad_vecs + vecs);
+  for (long j = (long)blockIdx.y * step + first; j < slack_vecs; j += (long)gridDim.y * step) slack[j] = zero;
+}
 __global__ void scalar_mul_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = a[i] * b[0];
@@ -157,6 +188,30 @@ extern "C" int sda_gather_samples(const void* table, const long* idx, void* dst,
   hipLaunchKernelGGL(gather_samples_kernel, dim3((unsigned)bx, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
                      (const uint4*)table, idx, (uint4*)dst, vecs);
   return check_launch("gather_samples");
+}
+
+extern "C" int sda_gather_windows(const void* table, long table_rows, const int32_t* starts, int M, const long* idx, void* dst,
+                                  int B, int T, long row_bytes, void* stream) {
+  if (!table || !starts || !idx || !dst) { set_error("gather_windows: null pointer (table, starts, idx and dst are required)"); return -1; }
+  if (B < 1 || T < 1 || M < 1) { set_error("gather_windows: B=%d, T=%d, M=%d must all be at least 1", B, T, M); return -1; }
+  if (B > 65535) { set_error("gather_windows: B=%d above 65535 samples per launch", B); return -1; }
+  if (table_rows < T) { set_error("gather_windows: a table of %ld rows holds no window of T=%d rows", table_rows, T); return -1; }
+  if (row_bytes < 128 || row_bytes % 128 || row_bytes > (1L << 30)) {
+    set_error("gather_windows: row_bytes=%ld is not a multiple of 128 up to 2^30 (a row is pad64(F) elements)", row_bytes); return -1;
+  }
+  if ((reinterpret_cast<uintptr_t>(table) & 15) || (reinterpret_cast<uintptr_t>(dst) & 15)) {
+    set_error("gather_windows: table and dst must be 16-byte aligned"); return -1;
+  }
+  const int row_vec = (int)(row_bytes / 16);
+  const long vecs = (long)T * row_vec;
+  long bx = (vecs + 256 * 8 - 1) / (256 * 8);             // at least eight vectors of a window per lane
+  const long want = (8L * launch_cus() + B - 1) / B;      // ~8 workgroups per CU over the whole batch
+  if (bx > want) bx = want;
+  if (bx < 1) bx = 1;
+  hipLaunchKernelGGL(gather_windows_kernel, dim3((unsigned)bx, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                     (const uint4*)table, table_rows, (const int*)starts, M, idx, (uint4*)dst, T, row_vec,
+                     (rows_alloc(B, T) - (long)B * rows_tp(T)) * row_vec);
+  return check_launch("gather_windows");
 }
 
 extern "C" int sda_scalar_mul(const float* a, const float* b, float* out, int n, void* stream) {

@@ -10,7 +10,10 @@ What it mirrors (SeanNobel/speech-decoding):
   * dataclass/gwilliams2022.py:129-142 (`__getitem__`: a speech segment i -> a random recording of that task, the MEG
     window at the segment's onset, the subject index) and :640-661 (`Gwilliams2022Collator`: baseline correction, robust
     scaling, clamp) — here `ResidentSegmentFeed`: the recordings stay in HBM, a batch is (recording, onset) pairs turned
-    into X (B, C, T) by ONE kernel (collate.ResidentSegments), Y rows are gathered from the resident embedding table;
+    into X (B, C, T) by ONE kernel (collate.ResidentSegments), Y rows are gathered from the resident embedding table — or, with
+    a retrieval.WindowBank as Y, from the embedding TRACKS themselves: gwilliams2022.py embeds each audio file once and cuts a
+    window per word onset; it materialises every window of the speech side (`self.Y[i]`), here sda_gather_windows writes a
+    batch's windows straight into the loss's row layout and each track is stored once (`synthetic_track_dataset`);
   * dataclass/brennan2018.py:72-152 (shift, trim, RobustScaler + clamp over the WHOLE recording per subject and channel or
     per channel with the subjects pooled, split into chunks, baseline correction per chunk; `__getitem__`: chunk i of a
     random subject) — here `ResidentSubjectFeed`: the (S, C, L) array is scaled once on the device by exact order statistics
@@ -56,12 +59,47 @@ class ShardedRandomSampler:
         return self.updates
 
 
-class _ResidentEmbeddings:
-    """The speech side shared by the resident feeds: Y (N, F, T) embeddings on the device, optionally kept as a row-layout
-    table in the compute dtype (pack_embeddings), one gather per batch."""
+def check_track_dtype(who: str, dtype):
+    """SdaError unless `dtype` is one a track-backed feed can hold (train.py data=tracks asks before it builds anything)."""
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise _tracks_are_16bit(who, dtype)
 
-    Y: torch.Tensor
+
+def _tracks_are_16bit(who: str, dtype) -> Exception:
+    from .lib import SdaError
+    return SdaError(f"{who}: dtype {dtype}; speech tracks are 16-bit (a WindowBank holds bfloat16 or float16 and nothing "
+                    "materialises its windows instead): fp32 training uses materialised Y (N, F, T) segments")
+
+
+class _ResidentEmbeddings:
+    """The speech side shared by the resident feeds, one gather per batch.  Y is (N, F, T) embeddings on the device, optionally
+    kept as a row-layout table in the compute dtype (pack_embeddings), or a retrieval.WindowBank whose candidate i is segment i:
+    the segments are then windows of resident tracks, each track stored once, and a batch is gathered from the bank's table
+    (ops.gather_windows) — nothing materialises the windows."""
+
+    Y: torch.Tensor           # or a retrieval.WindowBank
     _Yt = None                # row-layout table in the compute dtype (pack_embeddings)
+
+    def _bank(self):
+        """The WindowBank behind Y, or None when Y holds materialised segments."""
+        from .retrieval import WindowBank
+        return self.Y if isinstance(self.Y, WindowBank) else None
+
+    def _check_segments(self, ii: np.ndarray):
+        """Bank-backed feeds: every segment index is a candidate of the bank (checked on the host, before any launch)."""
+        n = len(self.Y)
+        if len(ii) and (int(ii.min()) < 0 or int(ii.max()) >= n):
+            raise IndexError(f"segment index outside the bank's [0, {n})")
+
+    def speech_bank(self, indices=None):
+        """The WindowBank the feed's segments are windows of; with `indices` (segment indices, e.g. a test split) the bank of
+        those candidates, in that order, sharing the same resident table (WindowBank.select) — what retrieve / retrieve_classes
+        decode against."""
+        bank = self._bank()
+        if bank is None:
+            from .lib import SdaError
+            raise SdaError("speech_bank: this feed holds materialised Y (N, F, T) segments, not a WindowBank")
+        return bank if indices is None else bank.select(indices)
 
     def pack_embeddings(self, dtype: torch.dtype, chunk: int = 128):
         """Keep the speech embeddings resident as a row-layout table in `dtype` (the encoder's compute dtype): batch() then
@@ -70,6 +108,16 @@ class _ResidentEmbeddings:
         embedding is rounded to `dtype` once here instead of once per step in the loss's pack — the same numbers."""
         from . import lib as L
         from . import ops
+        bank = self._bank()
+        if bank is not None:
+            # windows of resident tracks are already the loss's operand in the bank's dtype: no copy is made, and none CAN be
+            # made in another dtype without materialising every window
+            if dtype == bank.dtype:
+                return self
+            if dtype == torch.float32:
+                raise _tracks_are_16bit("pack_embeddings", dtype)
+            raise L.SdaError(f"pack_embeddings: dtype {dtype}, but the feed's WindowBank holds {bank.dtype} tracks; build the bank "
+                             "in the encoder's compute dtype")
         N, F, T = self.Y.shape
         Tp, Fp = L.rows_tp(T), L.pad_channels(F)
         table = torch.zeros((N * Tp + L.rows_alloc(1, T) - Tp, Fp), dtype=dtype, device=self.Y.device)
@@ -81,6 +129,17 @@ class _ResidentEmbeddings:
 
     def _gather_Y(self, ii: np.ndarray) -> torch.Tensor:
         """Y of the segments `ii` (host int64 indices; duplicates allowed)."""
+        bank = self._bank()
+        if bank is not None:
+            # segments are windows of resident tracks: ONE kernel writes the whole row-layout batch (pad rows and slack included)
+            # from the bank's table, and the view below is the loss's packed operand like the pack_embeddings form's
+            from . import ops
+            ii = np.asarray(ii, dtype=np.int64)
+            self._check_segments(ii)
+            B = len(ii)
+            with torch.cuda.device(bank.table.device):
+                rows = ops.gather_windows(bank.table, bank.starts, ops.upload_small(ii, bank.table.device), B, bank.T)
+            return ops.rows_view(rows, B, bank.F, bank.T)
         if self._Yt is not None:
             # embeddings resident in ROW LAYOUT in the compute dtype (pack_embeddings): the gathered batch IS the loss's packed
             # operand — CLIPLoss recognises the view and neither copies nor re-packs it
@@ -99,10 +158,12 @@ class ResidentSegmentFeed(_ResidentEmbeddings):
     """recordings: list of (C, L_r) device tensors, one per (subject, session) recording, each with the subject index
     `rec_subject[r]` and the task `rec_task[r]` it recorded; onsets[r][j] = first MEG sample of the j-th speech segment of
     that task; seg_task[i], seg_in_task[i] = (task, position) of global speech segment i (gwilliams2022.py: `segment_to_task`);
-    Y (N, F, T) speech embeddings, resident.  batch(idx) -> (X, Y, subject_idxs) with X collated on the device."""
+    Y (N, F, T) speech embeddings, resident — or a retrieval.WindowBank of N candidates, candidate i being segment i as a window
+    of its task's embedding track (the reference embeds each audio file once and cuts a window per word onset; it materialises
+    them, self.Y[i], here the tracks stay whole).  batch(idx) -> (X, Y, subject_idxs) with X collated on the device."""
 
     def __init__(self, recordings: Sequence[torch.Tensor], rec_subject: Sequence[int], rec_task: Sequence[int],
-                 onsets: Sequence[np.ndarray], seg_task: np.ndarray, seg_in_task: np.ndarray, Y: torch.Tensor, *,
+                 onsets: Sequence[np.ndarray], seg_task: np.ndarray, seg_in_task: np.ndarray, Y, *,
                  seq_len_samp: int, baseline_len_samp: int, clamp_lim: float, clamp: bool = True, seed: int = 0):
         self.rs = ResidentSegments(list(recordings), seq_len_samp, baseline_len_samp, clamp_lim, clamp)
         self.rec_subject = np.asarray(rec_subject, dtype=np.int32)
@@ -111,6 +172,8 @@ class ResidentSegmentFeed(_ResidentEmbeddings):
         self.seg_task, self.seg_in_task = np.asarray(seg_task), np.asarray(seg_in_task)
         self.Y = Y
         self._Yt = None           # row-layout table in the compute dtype (pack_embeddings)
+        if self._bank() is not None and len(Y) != len(self.seg_task):
+            raise ValueError(f"the WindowBank holds {len(Y)} candidates for {len(self.seg_task)} segments (candidate i is segment i)")
         self.by_task = {int(t): np.nonzero(self.rec_task == t)[0] for t in np.unique(self.rec_task)}
         # (gwilliams2022.py:133 draws the recording from NumPy's GLOBAL generator inside DataLoader workers; the global
         # generator stays reserved for SpatialDropout's centre here — every rank must draw that one in lockstep)
@@ -123,7 +186,7 @@ class ResidentSegmentFeed(_ResidentEmbeddings):
         self._onset_table = np.stack(self.onsets) if len(lens) == 1 else None
 
     def __len__(self) -> int:
-        return int(self.Y.shape[0])
+        return len(self.Y) if self._bank() is not None else int(self.Y.shape[0])
 
     def draw_recordings(self, idx) -> np.ndarray:
         """gwilliams2022.py:133: one random recording of each segment's task, drawn item by item from the feed's generator
@@ -142,6 +205,8 @@ class ResidentSegmentFeed(_ResidentEmbeddings):
         draws are made for the GLOBAL batch on every rank alike and sliced, see batches())."""
         idx = torch.as_tensor(idx, dtype=torch.int64)
         ii = idx.numpy()
+        if self._bank() is not None:
+            self._check_segments(ii)
         rec = self.draw_recordings(ii) if rec is None else np.asarray(rec, dtype=np.int64)
         on = self._onset_of(rec, self.seg_in_task[ii])
         X = self.rs.batch(rec, on)
@@ -208,6 +273,58 @@ def synthetic_resident_dataset(args, device, *, n_segments: int, n_tasks: int = 
         w = (w - w[:, :nb].mean(dim=1, keepdim=True)) / (2.0 * 1.35)
         Y[i] = P @ w + 0.5 * torch.randn(F, T, generator=g)
     feed = ResidentSegmentFeed(recordings, rec_subject, rec_task, onsets, seg_task, seg_in_task, Y.to(device), seq_len_samp=T,
+                               baseline_len_samp=nb, clamp_lim=float(args.preprocs["clamp_lim"]), clamp=bool(args.preprocs["clamp"]),
+                               seed=seed + 17)
+    n_train = int(n_segments * float(args.split_ratio))
+    perm = np.random.RandomState(seed).permutation(n_segments)
+    return feed, perm[:n_train], perm[n_train:]
+
+
+def synthetic_track_dataset(args, device, *, n_segments: int, dtype, n_tasks: int = 4, seed: int = 1234, recs_per_task: int = 2,
+                            hop: int = None) -> Tuple[ResidentSegmentFeed, np.ndarray, np.ndarray]:
+    """synthetic_resident_dataset with the speech side the way the reference first holds it (gwilliams2022.py embeds each audio
+    file once): the same recordings, onsets, tasks and split, and ONE (F, L) embedding track per task — a fixed linear read-out of
+    the task's FIRST recording plus noise, so retrieval is learnable — added to a WindowBank of `dtype` (bfloat16 or float16) with
+    the task's segment onsets as window starts, tasks and onsets in time order, so that candidate i is segment i.  Segments are
+    `hop` samples apart (default T // 2; a word every third of a second is T // 9): neighbouring windows overlap and the track is
+    stored once.  Returns (feed, train indices, test indices); the feed's Y is the bank."""
+    check_track_dtype("synthetic_track_dataset", dtype)
+    from .retrieval import WindowBank
+    C = int(args.get("num_channels", 208 if args.dataset == "Gwilliams2022" else 60))
+    rate = args.preprocs["brain_resample_rate"]
+    T = int(args.preprocs["seq_len_sec"] * rate)
+    nb = int(args.preprocs["baseline_len_sec"] * rate)
+    F = 1024 if args.preprocs["last4layers"] else int(args.F)
+    S = int(args.num_subjects)
+    g = torch.Generator().manual_seed(seed)
+    per_task = (n_segments + n_tasks - 1) // n_tasks
+    hop = max(1, T // 2) if hop is None else int(hop)
+    if hop < 1:
+        raise ValueError(f"synthetic_track_dataset: hop={hop} must be at least one sample")
+    Lr = per_task * hop + T + 64
+    recordings, rec_subject, rec_task, onsets, firsts = [], [], [], [], []
+    for t in range(n_tasks):
+        base = torch.randn(C, Lr, generator=g)
+        for k in range(recs_per_task):
+            drift = torch.linspace(0, float(k + 1), Lr)[None, :] * torch.randn(C, 1, generator=g)     # what the collate removes
+            rec = (base + 0.3 * torch.randn(C, Lr, generator=g)) * (2.0 + k) + drift
+            if k == 0:
+                firsts.append(rec)
+            recordings.append(rec.to(device))
+            rec_subject.append((recs_per_task * t + k) % S)
+            rec_task.append(t)
+            onsets.append(np.arange(per_task, dtype=np.int64) * hop + 7 * k)
+    seg_task = np.repeat(np.arange(n_tasks), per_task)[:n_segments]
+    seg_in_task = np.concatenate([np.arange(per_task)] * n_tasks)[:n_segments]
+    P = torch.randn(F, C, generator=g) / np.sqrt(C)
+    bank = WindowBank(F, T, dtype=dtype, device=device)
+    for t in range(n_tasks):
+        n_t = int((seg_task == t).sum())
+        if n_t == 0:
+            continue
+        track = P @ (firsts[t] / (2.0 * 1.35)) + 0.5 * torch.randn(F, Lr, generator=g)
+        bank.add_track(track.to(device), onsets[recs_per_task * t][:n_t])          # speech onsets = the first recording's
+    feed = ResidentSegmentFeed(recordings, rec_subject, rec_task, onsets, seg_task, seg_in_task, bank, seq_len_samp=T,
                                baseline_len_samp=nb, clamp_lim=float(args.preprocs["clamp_lim"]), clamp=bool(args.preprocs["clamp"]),
                                seed=seed + 17)
     n_train = int(n_segments * float(args.split_ratio))

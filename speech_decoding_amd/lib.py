@@ -150,6 +150,7 @@ SIGNATURES = {
     "sda_scalar_mul": (i32, [vp, vp, vp, i32, vp]),
     "sda_fill_zero": (i32, [vp, i64, vp]),
     "sda_gather_samples": (i32, [vp, vp, vp, i32, i64, vp]),
+    "sda_gather_windows": (i32, [vp, i64, vp, i32, vp, vp, i32, i32, i64, vp]),
     "sda_clip_merge_rows": (i32, [vp, i32, i32, vp, vp, vp]),
     "sda_copy3d": (i32, [vp, i64, i64, i64, vp, i64, i64, i64, i32, i32, i32, vp]),
     "sda_mse_forward": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),

@@ -174,6 +174,27 @@ def gather_samples(table: torch.Tensor, idx: torch.Tensor, B: int, T: int) -> to
     return out
 
 
+def gather_windows(table: torch.Tensor, starts: torch.Tensor, idx: torch.Tensor, B: int, T: int) -> torch.Tensor:
+    """table: (L, Cp) plain rows (retrieval.WindowBank.table, Cp a multiple of 64, channel padding zero); starts: M int32 table
+    rows on the device; idx: B int64 candidates on the device (any order, duplicates allowed).  Returns a fresh row-layout buffer
+    (rows_alloc(B, T), Cp) whose sample b is the T table rows from starts[idx[b]] on.  ONE launch writes all of it, pad rows and
+    slack included; a candidate outside [0, M) or a window that leaves the table comes back as zeros."""
+    _need_cuda(table, starts, idx)
+    if idx.dtype != torch.int64 or idx.numel() != B or not idx.is_contiguous():
+        raise L.SdaError("gather_windows: idx must hold B int64 indices")
+    if starts.dtype != torch.int32 or starts.dim() != 1 or not starts.is_contiguous() or starts.numel() < 1:
+        raise L.SdaError("gather_windows: starts must be a contiguous one-dimensional int32 tensor of at least one table row")
+    if table.dim() != 2 or not table.is_contiguous() or table.dtype not in COMPUTE_DTYPES:
+        raise L.SdaError("gather_windows: table must be a contiguous (L, Cp) tensor of float32, bfloat16 or float16 rows")
+    if table.device != starts.device or table.device != idx.device:
+        raise L.SdaError(f"gather_windows: table on {table.device}, starts on {starts.device}, idx on {idx.device}")
+    Cp = table.shape[1]
+    out = torch.empty((L.rows_alloc(B, T), Cp), dtype=table.dtype, device=table.device)      # the kernel writes all of it
+    L.check(L.load().sda_gather_windows(_p(table), table.shape[0], _p(starts), starts.numel(), _p(idx), _p(out), B, T,
+                                        Cp * table.element_size(), _st()), "gather_windows")
+    return out
+
+
 def clip_merge_rows(allp: torch.Tensor):
     """allp: the all-gathered (world, 3, Bg) fp32 table of per-rank (row max, row sum exp, positive's logit) -> (lse, diag)."""
     world, k, Bg = allp.shape

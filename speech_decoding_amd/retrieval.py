@@ -15,6 +15,8 @@ against its own bank and no collective is issued.  No gradients: both entry poin
 A `WindowBank` holds candidates that are windows of continuous speech tracks (the reference cuts its segments at word onsets out
 of one embedding track per audio file): each track is stored once as plain rows, a candidate is a row start, and the same pass
 scores them with the windowed form of the similarity GEMM (sda_sim_gemm_windows) — 16-bit storage only, nothing is materialised.
+The same bank is the speech side of the training feed (data.ResidentSegmentFeed with the bank as Y: ops.gather_windows), and
+`WindowBank.select` hands a subset of its candidates — the test split — to the same decoding without copying the table.
 
 Word-level decoding sits on the same blocked score matrix, filled by the same pass (`_ScorePass`: checks, pack, norms, scratch
 and block loop, written once): a `ClassIndex` says which class (word) every candidate is an instance of, and `retrieve_classes`
@@ -166,9 +168,34 @@ class WindowBank:
         self._starts = None             # (_capacity,) int32
         self._sq = None                 # (_capacity,) fp32
         self.starts_host = np.empty(0, dtype=np.int32)
+        self._table_of = None           # the bank whose table this one shares (select); None: the table is its own
 
     def __len__(self) -> int:
         return self._size
+
+    def select(self, indices) -> "WindowBank":
+        """A new bank whose candidates are the candidates `indices` of this one (host or device integers, one-dimensional, any
+        order, duplicates allowed), in that order — the test candidates of a train / test split of the same resident tracks.  The
+        table and the per-row sums are SHARED, nothing is copied; starts, starts_host and norms_sq are the result's own, taken
+        from this bank's values.  The result does not own the table: its add_track raises.  Tracks added to this bank afterwards
+        are not seen by the result."""
+        arr = indices.detach().cpu().numpy() if torch.is_tensor(indices) else np.asarray(indices)
+        if arr.ndim != 1 or arr.dtype.kind not in "iu":
+            raise ValueError("WindowBank.select: indices must be a one-dimensional array of integer candidates")
+        if arr.size and (int(arr.min()) < 0 or int(arr.max()) >= self._size):
+            raise IndexError(f"WindowBank.select: a candidate outside [0, {self._size})")
+        arr = arr.astype(np.int64)
+        sub = WindowBank(self.F, self.T, dtype=self.dtype, device=self.device)
+        sub._table_of = self if self._table_of is None else self._table_of
+        sub._store, sub._row_sq, sub._L, sub._row_capacity = self._store, self._row_sq, self._L, self._row_capacity
+        sub.starts_host = self.starts_host[arr]
+        sub._size = sub._capacity = int(arr.shape[0])
+        if sub._size:
+            sub._starts = torch.from_numpy(sub.starts_host).to(self._starts.device)
+            sub._sq = self._sq.index_select(0, torch.from_numpy(arr).to(self._sq.device))
+        else:
+            sub._starts, sub._sq = self._starts[:0], self._sq[:0]
+        return sub
 
     @property
     def table(self) -> torch.Tensor:
@@ -224,6 +251,9 @@ class WindowBank:
         `starts` (host integers in [0, L - T], any order, duplicates allowed); returns the bank indices the windows received.
         Add tracks, and the windows of a track, in time order where you can: a chunk of neighbouring candidates then reads
         neighbouring table rows, which is what the caches can keep and what the 4 GB span of one GEMM launch is counted over."""
+        if self._table_of is not None:
+            raise L.SdaError("WindowBank.add_track: this bank was made by select() and shares another bank's table, which it does "
+                             "not own; add the track to the bank the selection was made from and select again")
         if not torch.is_tensor(E) or E.dim() != 2 or E.shape[0] != self.F or E.shape[1] < self.T:
             got = tuple(E.shape) if torch.is_tensor(E) else type(E).__name__
             raise ValueError(f"WindowBank.add_track: expected an ({self.F}, L) track with L >= {self.T}, got {got}")

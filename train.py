@@ -16,6 +16,8 @@ What is kept from the reference loop (train.py:148-259):
   * the per-epoch print line and the optional W&B scalar names; `model_last.pt` = encoder.state_dict().
 `data=continuous` (with dataset=Brennan2018) runs that dataset's own input path on the GPU: whole-recording robust scaling
 (preprocs.subject_wise), clamp, segment gather with baseline correction (speech_decoding_amd.data.ResidentSubjectFeed).
+`data=tracks` (with dataset=Gwilliams2022, compute_dtype=bf16 or fp16) is `data=resident` with the speech embeddings kept as one
+resident track per task: a batch's Y is the windows at the segments' onsets, gathered into the loss's operand by one kernel.
 What is not: the M/EEG + wav2vec2 dataset classes (they need the raw recordings and un-downloadable weights; their
 signal conditioning — band-pass, audio and FFT resampling — is built as speech_decoding_amd.signal_prep, but this
 script does not read raw files).  `--data synthetic` (default) builds a seeded stand-in with the same tensor
@@ -81,6 +83,13 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
     data_kind = str(args.get("data", "pool"))
     if train_batches is None and data_kind == "continuous" and args.dataset != "Brennan2018":
         raise ValueError("data=continuous is Brennan2018's input path (one stimulus, every subject): use dataset=Brennan2018")
+    if train_batches is None and data_kind == "tracks" and args.dataset != "Gwilliams2022":
+        raise ValueError("data=tracks is Gwilliams2022's input path (segments are windows of per-task speech tracks): use "
+                         "dataset=Gwilliams2022")
+    if train_batches is None and data_kind == "tracks":        # fp32: the feed's own refusal, before anything is built
+        from speech_decoding_amd.data import check_track_dtype
+        from speech_decoding_amd.models import resolve_dtype
+        check_track_dtype("data=tracks", resolve_dtype(args))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -107,12 +116,20 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
     # baseline correction + robust scaling + clamp (gwilliams2022.py:129-142,640-661) as one kernel per batch;
     # data=continuous (dataset=Brennan2018): that dataset's own input path — the (subjects, channels, time) recording of one
     # stimulus resident in HBM, robust scaling + clamp over the WHOLE recording once (preprocs.subject_wise: per subject, or all
-    # subjects pooled), a batch = chunk i of a random subject with its baseline removed (brennan2018.py:72-152)
+    # subjects pooled), a batch = chunk i of a random subject with its baseline removed (brennan2018.py:72-152);
+    # data=tracks (dataset=Gwilliams2022): data=resident with the speech side held the way the reference first computes it — one
+    # embedding track per task, resident once in the encoder's 16-bit compute dtype (retrieval.WindowBank), a segment = the window
+    # at its onset; a batch's Y is gathered from the tracks into the loss's packed operand by one kernel (sda_gather_windows), no
+    # window is materialised.  Same sampler, epoch seeds and evaluation shards as data=resident; compute_dtype=fp32 is refused
     feeds_local_shards = False
-    if train_batches is None and data_kind == "resident":
-        from speech_decoding_amd.data import ShardedRandomSampler, synthetic_resident_dataset
+    if train_batches is None and data_kind in ("resident", "tracks"):
+        from speech_decoding_amd.data import ShardedRandomSampler, synthetic_resident_dataset, synthetic_track_dataset
         n_seg = int(args.get("synthetic_segments", 4 * int(args.batch_size)))
-        feed, train_idx, test_idx = synthetic_resident_dataset(args, device, n_segments=n_seg, seed=1234)
+        if data_kind == "tracks":
+            from speech_decoding_amd.models import resolve_dtype
+            feed, train_idx, test_idx = synthetic_track_dataset(args, device, n_segments=n_seg, dtype=resolve_dtype(args), seed=1234)
+        else:
+            feed, train_idx, test_idx = synthetic_resident_dataset(args, device, n_segments=n_seg, seed=1234)
         updates = int(args.get("updates_per_epoch", max(1, len(train_idx) // int(args.batch_size))))
         epoch_no = [0]
         pack_resident_embeddings = feed          # (packed once the encoder's compute dtype is known, below)
