@@ -19,16 +19,25 @@ What it mirrors (SeanNobel/speech-decoding):
     random subject) — here `ResidentSubjectFeed`: the (S, C, L) array is scaled once on the device by exact order statistics
     (collate.robust_stats / scale_clamp_rows) and stays resident; a batch is (subject, chunk) pairs turned into X by one
     kernel (collate.gather_baseline_windows).
+
+Written once: `segment_dims` (the sizes every stand-in and train.py read out of `args`), `_ResidentEmbeddings` (the speech side and
+`batches()`, for both feeds: a feed says what it draws for a batch and under which keyword `batch()` takes it), and
+`_synthetic_gwilliams` (the Gwilliams2022 stand-in: `synthetic_resident_dataset` and `synthetic_track_dataset` differ only in the
+speech side they attach).
 """
 from __future__ import annotations
 
-from typing import Iterator, List, Sequence, Tuple
+from typing import Iterator, NamedTuple, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import collate as _collate
+from . import lib as _lib
+from . import ops
 from .collate import ResidentSegments
+from .lib import SdaError
+from .retrieval import WindowBank
 
 
 class ShardedRandomSampler:
@@ -66,23 +75,57 @@ def check_track_dtype(who: str, dtype):
 
 
 def _tracks_are_16bit(who: str, dtype) -> Exception:
-    from .lib import SdaError
     return SdaError(f"{who}: dtype {dtype}; speech tracks are 16-bit (a WindowBank holds bfloat16 or float16 and nothing "
                     "materialises its windows instead): fp32 training uses materialised Y (N, F, T) segments")
 
 
+class SegmentDims(NamedTuple):
+    C: int        # M/EEG channels
+    T: int        # samples per segment
+    nb: int       # of them baseline
+    F: int        # speech embedding channels
+    S: int        # subjects
+
+
+def segment_dims(args) -> SegmentDims:
+    """(C, T, nb, F, S) as the stand-in datasets and train.py read them out of `args`."""
+    rate = args.preprocs["brain_resample_rate"]
+    return SegmentDims(C=int(args.get("num_channels", 208 if args.dataset == "Gwilliams2022" else 60)),
+                       T=int(args.preprocs["seq_len_sec"] * rate), nb=int(args.preprocs["baseline_len_sec"] * rate),
+                       F=1024 if args.preprocs["last4layers"] else int(args.F), S=int(args.num_subjects))
+
+
 class _ResidentEmbeddings:
-    """The speech side shared by the resident feeds, one gather per batch.  Y is (N, F, T) embeddings on the device, optionally
+    """What the resident feeds share.  The speech side, one gather per batch: Y is (N, F, T) embeddings on the device, optionally
     kept as a row-layout table in the compute dtype (pack_embeddings), or a retrieval.WindowBank whose candidate i is segment i:
     the segments are then windows of resident tracks, each track stored once, and a batch is gathered from the bank's table
-    (ops.gather_windows) — nothing materialises the windows."""
+    (ops.gather_windows) — nothing materialises the windows.  And batches(): a feed names the keyword under which its batch()
+    takes what it draws from `rng` per item (`drawn_as`) and draws it for any set of segments (`draw_for`)."""
 
     Y: torch.Tensor           # or a retrieval.WindowBank
-    _Yt = None                # row-layout table in the compute dtype (pack_embeddings)
+    _Yt = None                # row-layout table in the compute dtype (set by pack_embeddings only)
+    drawn_as: str             # "rec" / "subjects"; draw_for(ii) makes one such draw from the feed's generator per segment of ii
+
+    def batches(self, sampler, index_map=None) -> Iterator[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+        """One (X, Y, subject_idxs) per batch of `sampler`.  With a ShardedRandomSampler of more than one rank the draw (the
+        recording of a segment, the subject of a chunk) is made for EVERY item of the global batch on every rank from the same
+        generator state and the rank keeps its slice — the union over the ranks is exactly the batch a single process would have
+        drawn, and no two ranks share a draw.  `index_map`: optional array mapping sampler indices to segment indices (a train
+        split)."""
+        if hasattr(sampler, "global_batches") and getattr(sampler, "world", 1) > 1:
+            per = sampler.batch_size // sampler.world
+            lo = sampler.rank * per
+            for gidx in sampler.global_batches():
+                g = gidx.numpy() if index_map is None else np.asarray(index_map)[gidx.numpy()]
+                drawn = self.draw_for(g)
+                yield self.batch(g[lo: lo + per], **{self.drawn_as: drawn[lo: lo + per]})
+            return
+        for idx in sampler:
+            i = idx.numpy() if isinstance(idx, torch.Tensor) else np.asarray(idx)
+            yield self.batch(i if index_map is None else np.asarray(index_map)[i])
 
     def _bank(self):
         """The WindowBank behind Y, or None when Y holds materialised segments."""
-        from .retrieval import WindowBank
         return self.Y if isinstance(self.Y, WindowBank) else None
 
     def _check_segments(self, ii: np.ndarray):
@@ -97,7 +140,6 @@ class _ResidentEmbeddings:
         decode against."""
         bank = self._bank()
         if bank is None:
-            from .lib import SdaError
             raise SdaError("speech_bank: this feed holds materialised Y (N, F, T) segments, not a WindowBank")
         return bank if indices is None else bank.select(indices)
 
@@ -106,8 +148,6 @@ class _ResidentEmbeddings:
         hands out Y as a zero-copy (B, F, T) view of ONE gather kernel's output, which CLIPLoss consumes as its packed operand —
         per step 0.4 GB of HBM traffic instead of the 1.3 GB of index_select + sda_pack_rows (batch 256, bf16).  Values: each
         embedding is rounded to `dtype` once here instead of once per step in the loss's pack — the same numbers."""
-        from . import lib as L
-        from . import ops
         bank = self._bank()
         if bank is not None:
             # windows of resident tracks are already the loss's operand in the bank's dtype: no copy is made, and none CAN be
@@ -116,11 +156,11 @@ class _ResidentEmbeddings:
                 return self
             if dtype == torch.float32:
                 raise _tracks_are_16bit("pack_embeddings", dtype)
-            raise L.SdaError(f"pack_embeddings: dtype {dtype}, but the feed's WindowBank holds {bank.dtype} tracks; build the bank "
+            raise SdaError(f"pack_embeddings: dtype {dtype}, but the feed's WindowBank holds {bank.dtype} tracks; build the bank "
                              "in the encoder's compute dtype")
         N, F, T = self.Y.shape
-        Tp, Fp = L.rows_tp(T), L.pad_channels(F)
-        table = torch.zeros((N * Tp + L.rows_alloc(1, T) - Tp, Fp), dtype=dtype, device=self.Y.device)
+        Tp, Fp = _lib.rows_tp(T), _lib.pad_channels(F)
+        table = torch.zeros((N * Tp + _lib.rows_alloc(1, T) - Tp, Fp), dtype=dtype, device=self.Y.device)
         for k in range(0, N, chunk):
             n = min(chunk, N - k)
             ops.pack_rows(self.Y[k: k + n], table[k * Tp:])
@@ -128,14 +168,12 @@ class _ResidentEmbeddings:
         return self
 
     def _gather_Y(self, ii: np.ndarray) -> torch.Tensor:
-        """Y of the segments `ii` (host int64 indices; duplicates allowed)."""
+        """Y of the segments `ii` (host int64 indices; duplicates allowed; a bank-backed feed's batch() has checked them)."""
         bank = self._bank()
         if bank is not None:
             # segments are windows of resident tracks: ONE kernel writes the whole row-layout batch (pad rows and slack included)
             # from the bank's table, and the view below is the loss's packed operand like the pack_embeddings form's
-            from . import ops
             ii = np.asarray(ii, dtype=np.int64)
-            self._check_segments(ii)
             B = len(ii)
             with torch.cuda.device(bank.table.device):
                 rows = ops.gather_windows(bank.table, bank.starts, ops.upload_small(ii, bank.table.device), B, bank.T)
@@ -143,12 +181,10 @@ class _ResidentEmbeddings:
         if self._Yt is not None:
             # embeddings resident in ROW LAYOUT in the compute dtype (pack_embeddings): the gathered batch IS the loss's packed
             # operand — CLIPLoss recognises the view and neither copies nor re-packs it
-            from . import ops
             B, (F, T) = len(ii), self.Y.shape[1:]
             with torch.cuda.device(self._Yt.device):
                 return ops.rows_view(ops.gather_samples(self._Yt, ops.upload_small(ii, self._Yt.device), B, T), B, F, T)
         if self.Y.is_cuda:
-            from . import ops
             with torch.cuda.device(self.Y.device):
                 return self.Y.index_select(0, ops.upload_small(ii, self.Y.device))    # (index table in kernel arguments: no host wait)
         return self.Y.index_select(0, torch.as_tensor(ii, dtype=torch.int64))
@@ -171,7 +207,6 @@ class ResidentSegmentFeed(_ResidentEmbeddings):
         self.onsets = [np.asarray(o, dtype=np.int64) for o in onsets]
         self.seg_task, self.seg_in_task = np.asarray(seg_task), np.asarray(seg_in_task)
         self.Y = Y
-        self._Yt = None           # row-layout table in the compute dtype (pack_embeddings)
         if self._bank() is not None and len(Y) != len(self.seg_task):
             raise ValueError(f"the WindowBank holds {len(Y)} candidates for {len(self.seg_task)} segments (candidate i is segment i)")
         self.by_task = {int(t): np.nonzero(self.rec_task == t)[0] for t in np.unique(self.rec_task)}
@@ -200,6 +235,11 @@ class ResidentSegmentFeed(_ResidentEmbeddings):
             return self._rec_table[np.searchsorted(self._task_keys, tasks), u].astype(np.int64)
         return np.array([self.rng.choice(self.by_task[int(t)]) for t in tasks], dtype=np.int64)
 
+    drawn_as = "rec"
+
+    def draw_for(self, ii: np.ndarray) -> np.ndarray:
+        return self.draw_recordings(ii)
+
     def batch(self, idx, rec=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """idx: this rank's global segment indices; rec: their recordings when the caller drew them (data parallelism: the
         draws are made for the GLOBAL batch on every rank alike and sliced, see batches())."""
@@ -218,89 +258,18 @@ class ResidentSegmentFeed(_ResidentEmbeddings):
             return self._onset_table[rec, j]
         return np.array([self.onsets[r][k] for r, k in zip(rec, j)], dtype=np.int64)
 
-    def batches(self, sampler, index_map=None) -> Iterator[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
-        """One (X, Y, subject_idxs) per batch of `sampler`.  With a ShardedRandomSampler the recording of EVERY segment of the
-        global batch is drawn on every rank from the same generator state and the rank keeps its slice — the union over the
-        ranks is exactly the batch a single process would have drawn, and no two ranks share a draw.  `index_map`: optional
-        array mapping sampler indices to segment indices (a train split)."""
-        if hasattr(sampler, "global_batches") and getattr(sampler, "world", 1) > 1:
-            per = sampler.batch_size // sampler.world
-            lo = sampler.rank * per
-            for gidx in sampler.global_batches():
-                g = gidx.numpy() if index_map is None else np.asarray(index_map)[gidx.numpy()]
-                rec = self.draw_recordings(g)
-                yield self.batch(g[lo: lo + per], rec=rec[lo: lo + per])
-            return
-        for idx in sampler:
-            i = idx.numpy() if isinstance(idx, torch.Tensor) else np.asarray(idx)
-            yield self.batch(i if index_map is None else np.asarray(index_map)[i])
 
-
-def synthetic_resident_dataset(args, device, *, n_segments: int, n_tasks: int = 4, seed: int = 1234,
-                               recs_per_task: int = 2) -> Tuple[ResidentSegmentFeed, np.ndarray, np.ndarray]:
-    """Seeded stand-in with the STRUCTURE of Gwilliams2022 (27 subjects x up to 2 sessions x 4 tasks of ~100 k samples are
-    not needed to exercise the path): `n_tasks` tasks, `recs_per_task` recordings per task from different subjects (the real
-    dataset has every subject hear every task: pass ceil(S / n_tasks) to see all S subjects in a batch), segments laid out
-    back to back with an overlap; the speech embedding of a segment is a fixed linear read-out of the raw window of the
-    task's FIRST recording plus noise, so retrieval is learnable.  Returns (feed, train indices, test indices)."""
-    C = int(args.get("num_channels", 208 if args.dataset == "Gwilliams2022" else 60))
-    rate = args.preprocs["brain_resample_rate"]
-    T = int(args.preprocs["seq_len_sec"] * rate)
-    nb = int(args.preprocs["baseline_len_sec"] * rate)
-    F = 1024 if args.preprocs["last4layers"] else int(args.F)
-    S = int(args.num_subjects)
+def _synthetic_gwilliams(args, device, speech_side, *, n_segments: int, n_tasks: int, seed: int, recs_per_task: int,
+                         hop: int = None) -> Tuple[ResidentSegmentFeed, np.ndarray, np.ndarray]:
+    """The stand-in behind synthetic_resident_dataset and synthetic_track_dataset: recordings, subjects, tasks, onsets, segment
+    tables, the read-out P, the feed and the split.  `speech_side(P, firsts, speech_onsets, seg_task, seg_in_task, g)` returns the
+    feed's Y from the tasks' FIRST recordings (host copies) and their onsets — the speech onsets.  Every value comes from the one
+    generator `g`, in this order: per task `base`, then per recording the drift's (C, 1) and the noise's (C, Lr); P; then whatever
+    `speech_side` draws."""
+    C, T, nb, F, S = segment_dims(args)
     g = torch.Generator().manual_seed(seed)
     per_task = (n_segments + n_tasks - 1) // n_tasks
-    hop = max(1, T // 2)
-    Lr = per_task * hop + T + 64
-    recordings, rec_subject, rec_task, onsets = [], [], [], []
-    for t in range(n_tasks):
-        base = torch.randn(C, Lr, generator=g)
-        for k in range(recs_per_task):
-            drift = torch.linspace(0, float(k + 1), Lr)[None, :] * torch.randn(C, 1, generator=g)     # what the collate removes
-            recordings.append(((base + 0.3 * torch.randn(C, Lr, generator=g)) * (2.0 + k) + drift).to(device))
-            rec_subject.append((recs_per_task * t + k) % S)
-            rec_task.append(t)
-            onsets.append(np.arange(per_task, dtype=np.int64) * hop + 7 * k)
-    seg_task = np.repeat(np.arange(n_tasks), per_task)[:n_segments]
-    seg_in_task = np.concatenate([np.arange(per_task)] * n_tasks)[:n_segments]
-    P = torch.randn(F, C, generator=g) / np.sqrt(C)
-    Y = torch.empty((n_segments, F, T))
-    for i in range(n_segments):
-        r0 = recs_per_task * int(seg_task[i])
-        o = int(onsets[r0][seg_in_task[i]])
-        w = recordings[r0][:, o: o + T].cpu()
-        w = (w - w[:, :nb].mean(dim=1, keepdim=True)) / (2.0 * 1.35)
-        Y[i] = P @ w + 0.5 * torch.randn(F, T, generator=g)
-    feed = ResidentSegmentFeed(recordings, rec_subject, rec_task, onsets, seg_task, seg_in_task, Y.to(device), seq_len_samp=T,
-                               baseline_len_samp=nb, clamp_lim=float(args.preprocs["clamp_lim"]), clamp=bool(args.preprocs["clamp"]),
-                               seed=seed + 17)
-    n_train = int(n_segments * float(args.split_ratio))
-    perm = np.random.RandomState(seed).permutation(n_segments)
-    return feed, perm[:n_train], perm[n_train:]
-
-
-def synthetic_track_dataset(args, device, *, n_segments: int, dtype, n_tasks: int = 4, seed: int = 1234, recs_per_task: int = 2,
-                            hop: int = None) -> Tuple[ResidentSegmentFeed, np.ndarray, np.ndarray]:
-    """synthetic_resident_dataset with the speech side the way the reference first holds it (gwilliams2022.py embeds each audio
-    file once): the same recordings, onsets, tasks and split, and ONE (F, L) embedding track per task — a fixed linear read-out of
-    the task's FIRST recording plus noise, so retrieval is learnable — added to a WindowBank of `dtype` (bfloat16 or float16) with
-    the task's segment onsets as window starts, tasks and onsets in time order, so that candidate i is segment i.  Segments are
-    `hop` samples apart (default T // 2; a word every third of a second is T // 9): neighbouring windows overlap and the track is
-    stored once.  Returns (feed, train indices, test indices); the feed's Y is the bank."""
-    check_track_dtype("synthetic_track_dataset", dtype)
-    from .retrieval import WindowBank
-    C = int(args.get("num_channels", 208 if args.dataset == "Gwilliams2022" else 60))
-    rate = args.preprocs["brain_resample_rate"]
-    T = int(args.preprocs["seq_len_sec"] * rate)
-    nb = int(args.preprocs["baseline_len_sec"] * rate)
-    F = 1024 if args.preprocs["last4layers"] else int(args.F)
-    S = int(args.num_subjects)
-    g = torch.Generator().manual_seed(seed)
-    per_task = (n_segments + n_tasks - 1) // n_tasks
-    hop = max(1, T // 2) if hop is None else int(hop)
-    if hop < 1:
-        raise ValueError(f"synthetic_track_dataset: hop={hop} must be at least one sample")
+    hop = max(1, T // 2) if hop is None else hop
     Lr = per_task * hop + T + 64
     recordings, rec_subject, rec_task, onsets, firsts = [], [], [], [], []
     for t in range(n_tasks):
@@ -317,19 +286,59 @@ def synthetic_track_dataset(args, device, *, n_segments: int, dtype, n_tasks: in
     seg_task = np.repeat(np.arange(n_tasks), per_task)[:n_segments]
     seg_in_task = np.concatenate([np.arange(per_task)] * n_tasks)[:n_segments]
     P = torch.randn(F, C, generator=g) / np.sqrt(C)
-    bank = WindowBank(F, T, dtype=dtype, device=device)
-    for t in range(n_tasks):
-        n_t = int((seg_task == t).sum())
-        if n_t == 0:
-            continue
-        track = P @ (firsts[t] / (2.0 * 1.35)) + 0.5 * torch.randn(F, Lr, generator=g)
-        bank.add_track(track.to(device), onsets[recs_per_task * t][:n_t])          # speech onsets = the first recording's
-    feed = ResidentSegmentFeed(recordings, rec_subject, rec_task, onsets, seg_task, seg_in_task, bank, seq_len_samp=T,
+    Y = speech_side(P, firsts, onsets[::recs_per_task], seg_task, seg_in_task, g)
+    feed = ResidentSegmentFeed(recordings, rec_subject, rec_task, onsets, seg_task, seg_in_task, Y, seq_len_samp=T,
                                baseline_len_samp=nb, clamp_lim=float(args.preprocs["clamp_lim"]), clamp=bool(args.preprocs["clamp"]),
                                seed=seed + 17)
     n_train = int(n_segments * float(args.split_ratio))
     perm = np.random.RandomState(seed).permutation(n_segments)
     return feed, perm[:n_train], perm[n_train:]
+
+
+def synthetic_resident_dataset(args, device, *, n_segments: int, n_tasks: int = 4, seed: int = 1234,
+                               recs_per_task: int = 2) -> Tuple[ResidentSegmentFeed, np.ndarray, np.ndarray]:
+    """Seeded stand-in with the STRUCTURE of Gwilliams2022 (27 subjects x up to 2 sessions x 4 tasks of ~100 k samples are
+    not needed to exercise the path): `n_tasks` tasks, `recs_per_task` recordings per task from different subjects (the real
+    dataset has every subject hear every task: pass ceil(S / n_tasks) to see all S subjects in a batch), segments laid out
+    back to back with an overlap; the speech embedding of a segment is a fixed linear read-out of the raw window of the
+    task's FIRST recording plus noise, so retrieval is learnable.  Returns (feed, train indices, test indices)."""
+    _, T, nb, F, _ = segment_dims(args)
+
+    def segments(P, firsts, speech_onsets, seg_task, seg_in_task, g):
+        Y = torch.empty((n_segments, F, T))
+        for i, (t, j) in enumerate(zip(seg_task, seg_in_task)):
+            o = int(speech_onsets[t][j])
+            w = firsts[t][:, o: o + T].contiguous()
+            w = (w - w[:, :nb].mean(dim=1, keepdim=True)) / (2.0 * 1.35)
+            Y[i] = P @ w + 0.5 * torch.randn(F, T, generator=g)
+        return Y.to(device)
+    return _synthetic_gwilliams(args, device, segments, n_segments=n_segments, n_tasks=n_tasks, seed=seed, recs_per_task=recs_per_task)
+
+
+def synthetic_track_dataset(args, device, *, n_segments: int, dtype, n_tasks: int = 4, seed: int = 1234, recs_per_task: int = 2,
+                            hop: int = None) -> Tuple[ResidentSegmentFeed, np.ndarray, np.ndarray]:
+    """synthetic_resident_dataset with the speech side the way the reference first holds it (gwilliams2022.py embeds each audio
+    file once): the same recordings, onsets, tasks and split, and ONE (F, L) embedding track per task — a fixed linear read-out of
+    the task's FIRST recording plus noise, so retrieval is learnable — added to a WindowBank of `dtype` (bfloat16 or float16) with
+    the task's segment onsets as window starts, tasks and onsets in time order, so that candidate i is segment i.  Segments are
+    `hop` samples apart (default T // 2; a word every third of a second is T // 9): neighbouring windows overlap and the track is
+    stored once.  Returns (feed, train indices, test indices); the feed's Y is the bank."""
+    check_track_dtype("synthetic_track_dataset", dtype)
+    if hop is not None and int(hop) < 1:
+        raise ValueError(f"synthetic_track_dataset: hop={int(hop)} must be at least one sample")
+    _, T, _, F, _ = segment_dims(args)
+
+    def tracks(P, firsts, speech_onsets, seg_task, seg_in_task, g):
+        bank = WindowBank(F, T, dtype=dtype, device=device)
+        for t, first in enumerate(firsts):
+            n_t = int((seg_task == t).sum())
+            if n_t == 0:                                    # (a task without segments: no track, and no draw)
+                continue
+            track = P @ (first / (2.0 * 1.35)) + 0.5 * torch.randn(F, first.shape[1], generator=g)
+            bank.add_track(track.to(device), speech_onsets[t][:n_t])
+        return bank
+    return _synthetic_gwilliams(args, device, tracks, n_segments=n_segments, n_tasks=n_tasks, seed=seed, recs_per_task=recs_per_task,
+                                hop=None if hop is None else int(hop))
 
 
 def subject_feed_geometry(length: int, srate: float, seq_len_sec: float, baseline_len_sec: float, shift_ms: float = 150,
@@ -394,7 +403,6 @@ class ResidentSubjectFeed(_ResidentEmbeddings):
         F = int(Y.shape[0])
         # (Y[:, :-shift] then [:trim_len]: the first trim_len samples; Y's segments ARE materialised, one embedding per item)
         self.Y = Y[:, :trim].reshape(F, n, seg).permute(1, 0, 2).contiguous()
-        self._Yt = None
         self.rng = np.random.RandomState(seed)       # (the global generator stays reserved for SpatialDropout, see above)
 
     def __len__(self) -> int:
@@ -404,6 +412,11 @@ class ResidentSubjectFeed(_ResidentEmbeddings):
         """brennan2018.py:148 draws `np.random.choice(num_subjects)` item by item; one vectorised randint(0, S, size=n) from the
         feed's own generator is the same stream of values."""
         return self.rng.randint(0, self.S, size=int(n)).astype(np.int64)
+
+    drawn_as = "subjects"
+
+    def draw_for(self, ii: np.ndarray) -> np.ndarray:
+        return self.draw_subjects(len(ii))
 
     def batch(self, idx, subjects=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """idx: this rank's segment indices (duplicates allowed); subjects: their subjects when the caller drew them (data
@@ -415,21 +428,6 @@ class ResidentSubjectFeed(_ResidentEmbeddings):
         X = _collate.gather_baseline_windows(self.X, sub, ii * self.seg, self.seg, self.nb)
         return X, self._gather_Y(ii), torch.from_numpy(sub.astype(np.int32))
 
-    def batches(self, sampler, index_map=None) -> Iterator[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
-        """One (X, Y, subject_idxs) per batch of `sampler` (ResidentSegmentFeed.batches): with a ShardedRandomSampler of more
-        than one rank the subjects of the GLOBAL batch are drawn on every rank alike and the rank keeps its slice."""
-        if hasattr(sampler, "global_batches") and getattr(sampler, "world", 1) > 1:
-            per = sampler.batch_size // sampler.world
-            lo = sampler.rank * per
-            for gidx in sampler.global_batches():
-                g = gidx.numpy() if index_map is None else np.asarray(index_map)[gidx.numpy()]
-                sub = self.draw_subjects(len(g))
-                yield self.batch(g[lo: lo + per], subjects=sub[lo: lo + per])
-            return
-        for idx in sampler:
-            i = idx.numpy() if isinstance(idx, torch.Tensor) else np.asarray(idx)
-            yield self.batch(i if index_map is None else np.asarray(index_map)[i])
-
 
 def synthetic_subject_dataset(args, device, *, length: int, seed: int = 1234) -> Tuple[torch.Tensor, torch.Tensor]:
     """Seeded stand-in with the STRUCTURE of Brennan2018: S subjects hear one stimulus; a shared latent brain response
@@ -437,9 +435,7 @@ def synthetic_subject_dataset(args, device, *, length: int, seed: int = 1234) ->
     whole-recording scaling removes (and what makes subject_wise matter) — plus rare artefact spikes for the clamp.  The
     speech embedding at sample t is a fixed linear read-out of the latent response `shift_len` ms LATER plus noise, so
     retrieval is learnable after the feed's shift.  Returns (X (S, C, length), Y (F, length)) on `device`."""
-    C = int(args.get("num_channels", 208 if args.dataset == "Gwilliams2022" else 60))
-    F = 1024 if args.preprocs["last4layers"] else int(args.F)
-    S = int(args.num_subjects)
+    C, _, _, F, S = segment_dims(args)
     shift = int(args.preprocs["brain_resample_rate"] * (args.preprocs.get("shift_len", 150) / 1000))
     g = torch.Generator().manual_seed(seed)
     latent = torch.randn(C, length, generator=g)

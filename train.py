@@ -22,6 +22,9 @@ What is not: the M/EEG + wav2vec2 dataset classes (they need the raw recordings 
 signal conditioning — band-pass, audio and FFT resampling — is built as speech_decoding_amd.signal_prep, but this
 script does not read raw files).  `--data synthetic` (default) builds a seeded stand-in with the same tensor
 shapes; a real dataset object can be passed to `run()` as (train_batches, test_batch) callables.
+
+Layout: `build_data` makes the synthetic data of a `data=` kind (the feed, or None for the pool, and the two callables; sampler,
+epoch seed and test shard are written there once), `make_backward_and_step` the update, `run` the loop around them.
 """
 from __future__ import annotations
 
@@ -38,8 +41,10 @@ sys.path.insert(0, ROOT)
 
 from speech_decoding.models import BrainEncoder, Classifier       # noqa: E402  (train.py:22 import path)
 from speech_decoding.utils.loss import CLIPLoss, MSELoss           # noqa: E402  (train.py:24)
+from speech_decoding_amd import data as D                          # noqa: E402  (feeds are looked up in the module when run() is called)
 from speech_decoding_amd import load_config                        # noqa: E402
 from speech_decoding_amd.distributed import allreduce_gradients, broadcast_parameters, shard_range  # noqa: E402
+from speech_decoding_amd.models import resolve_dtype               # noqa: E402
 
 
 class SyntheticSegments:
@@ -48,19 +53,16 @@ class SyntheticSegments:
     learnable), subject indices uniform.  Split by `split_ratio` like the shallow split."""
 
     def __init__(self, args, n_segments: int, device, seed: int = 0):
-        C = int(args.get("num_channels", 208 if args.dataset == "Gwilliams2022" else 60))
-        T = int(args.preprocs["seq_len_sec"] * args.preprocs["brain_resample_rate"])
-        F = 1024 if args.preprocs["last4layers"] else int(args.F)
+        C, T, nb, F, S = D.segment_dims(args)
         g = torch.Generator().manual_seed(seed)
         X = torch.randn(n_segments, C, T, generator=g)
-        nb = int(args.preprocs["baseline_len_sec"] * args.preprocs["brain_resample_rate"])
         X = X - X[:, :, :nb].mean(dim=-1, keepdim=True)
         if args.preprocs["clamp"]:
             X = X.clamp(-float(args.preprocs["clamp_lim"]), float(args.preprocs["clamp_lim"]))
         P = torch.randn(F, C, generator=g) / np.sqrt(C)
         Y = torch.einsum("fc,nct->nft", P, X) + 0.5 * torch.randn(n_segments, F, T, generator=g)
         self.X, self.Y = X.to(device), Y.to(device)
-        self.subj = torch.randint(0, int(args.num_subjects), (n_segments,), generator=g, dtype=torch.int32)
+        self.subj = torch.randint(0, S, (n_segments,), generator=g, dtype=torch.int32)
         n_train = int(n_segments * float(args.split_ratio))
         self.train_idx = torch.arange(n_train)
         self.test_idx = torch.arange(n_train, n_segments)
@@ -78,133 +80,64 @@ class SyntheticSegments:
         return self.X[i], self.Y[i], self.subj[i]
 
 
-def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Callable] = None, log=print):
-    import torch.distributed as dist
-    data_kind = str(args.get("data", "pool"))
-    if train_batches is None and data_kind == "continuous" and args.dataset != "Brennan2018":
-        raise ValueError("data=continuous is Brennan2018's input path (one stimulus, every subject): use dataset=Brennan2018")
-    if train_batches is None and data_kind == "tracks" and args.dataset != "Gwilliams2022":
-        raise ValueError("data=tracks is Gwilliams2022's input path (segments are windows of per-task speech tracks): use "
-                         "dataset=Gwilliams2022")
-    if train_batches is None and data_kind == "tracks":        # fp32: the feed's own refusal, before anything is built
-        from speech_decoding_amd.data import check_track_dtype
-        from speech_decoding_amd.models import resolve_dtype
-        check_track_dtype("data=tracks", resolve_dtype(args))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    torch.cuda.set_device(local)
-    device = torch.device("cuda", local)
-    from speech_decoding_amd.streams import use_training_stream
-    caller_stream = torch.cuda.current_stream(device)
-    use_training_stream(device)          # the loop's chain on a high-priority stream; the engine's side streams stay normal
-    owns_group = world > 1 and not dist.is_initialized()
-    if owns_group:
-        from speech_decoding_amd.distributed import init_process_group as sda_init_pg
-        sda_init_pg(os.environ.get("SDA_DIST_BACKEND", "nccl"))
-    if args.get("reproducible", False):
-        np.random.seed(0)
-        torch.manual_seed(0)
-    elif world > 1:
-        # SpatialDropout's centre comes from NumPy's global generator (models.py:81) and must be the same on every rank
-        from speech_decoding_amd.distributed import seed_numpy_all_ranks
-        seed_numpy_all_ranks()
+def build_data(args, data_kind: str, device, rank: int, world: int):
+    """The synthetic data of a `data=` kind -> (feed, train_batches, test_batch).  `feed` is None for the pool; otherwise the
+    callables hand out THIS rank's shard of every batch, and feed.pack_embeddings is the caller's to call once the encoder's
+    compute dtype is known.
 
-    # data=pool (default): a resident pool of ready-made segments, every rank slicing its shard out of the global batch;
-    # data=resident: the reference's own input path on the GPU — recordings resident in HBM, RandomSampler(replacement=True)
-    # (get_dataloaders.py:48-87) cut into rank shards so that no rank materialises another rank's samples, window gather +
-    # baseline correction + robust scaling + clamp (gwilliams2022.py:129-142,640-661) as one kernel per batch;
-    # data=continuous (dataset=Brennan2018): that dataset's own input path — the (subjects, channels, time) recording of one
-    # stimulus resident in HBM, robust scaling + clamp over the WHOLE recording once (preprocs.subject_wise: per subject, or all
-    # subjects pooled), a batch = chunk i of a random subject with its baseline removed (brennan2018.py:72-152);
-    # data=tracks (dataset=Gwilliams2022): data=resident with the speech side held the way the reference first computes it — one
-    # embedding track per task, resident once in the encoder's 16-bit compute dtype (retrieval.WindowBank), a segment = the window
-    # at its onset; a batch's Y is gathered from the tracks into the loss's packed operand by one kernel (sda_gather_windows), no
-    # window is materialised.  Same sampler, epoch seeds and evaluation shards as data=resident; compute_dtype=fp32 is refused
-    feeds_local_shards = False
-    if train_batches is None and data_kind in ("resident", "tracks"):
-        from speech_decoding_amd.data import ShardedRandomSampler, synthetic_resident_dataset, synthetic_track_dataset
-        n_seg = int(args.get("synthetic_segments", 4 * int(args.batch_size)))
-        if data_kind == "tracks":
-            from speech_decoding_amd.models import resolve_dtype
-            feed, train_idx, test_idx = synthetic_track_dataset(args, device, n_segments=n_seg, dtype=resolve_dtype(args), seed=1234)
-        else:
-            feed, train_idx, test_idx = synthetic_resident_dataset(args, device, n_segments=n_seg, seed=1234)
-        updates = int(args.get("updates_per_epoch", max(1, len(train_idx) // int(args.batch_size))))
-        epoch_no = [0]
-        pack_resident_embeddings = feed          # (packed once the encoder's compute dtype is known, below)
-
-        def train_batches():
-            sampler = ShardedRandomSampler(len(train_idx), int(args.batch_size), updates, rank, world, seed=4321 + epoch_no[0])
-            epoch_no[0] += 1
-            # (under data parallelism the recordings of the whole global batch are drawn on every rank alike and sliced)
-            yield from feed.batches(sampler, index_map=train_idx)
-
-        def test_batch():
-            lo, hi = shard_range(len(test_idx), rank, world)
-            return feed.batch(test_idx[lo:hi])
-        feeds_local_shards = True
-    elif train_batches is None and data_kind == "continuous":
-        from speech_decoding_amd.data import ResidentSubjectFeed, ShardedRandomSampler, synthetic_subject_dataset
+    data=pool (default): a resident pool of ready-made segments, every rank slicing its shard out of the global batch;
+    data=resident: the reference's own input path on the GPU — recordings resident in HBM, RandomSampler(replacement=True)
+    (get_dataloaders.py:48-87) cut into rank shards so that no rank materialises another rank's samples, window gather +
+    baseline correction + robust scaling + clamp (gwilliams2022.py:129-142,640-661) as one kernel per batch;
+    data=continuous (dataset=Brennan2018): that dataset's own input path — the (subjects, channels, time) recording of one
+    stimulus resident in HBM, robust scaling + clamp over the WHOLE recording once (preprocs.subject_wise: per subject, or all
+    subjects pooled), a batch = chunk i of a random subject with its baseline removed (brennan2018.py:72-152);
+    data=tracks (dataset=Gwilliams2022): data=resident with the speech side held the way the reference first computes it — one
+    embedding track per task, resident once in the encoder's 16-bit compute dtype (retrieval.WindowBank), a segment = the window
+    at its onset; a batch's Y is gathered from the tracks into the loss's packed operand by one kernel (sda_gather_windows), no
+    window is materialised.  Same sampler, epoch seeds and evaluation shards as data=resident; compute_dtype=fp32 is refused."""
+    batch_size = int(args.batch_size)
+    n_seg = int(args.get("synthetic_segments", 4 * batch_size))
+    if data_kind == "tracks":
+        feed, train_idx, test_idx = D.synthetic_track_dataset(args, device, n_segments=n_seg, dtype=resolve_dtype(args), seed=1234)
+    elif data_kind == "resident":
+        feed, train_idx, test_idx = D.synthetic_resident_dataset(args, device, n_segments=n_seg, seed=1234)
+    elif data_kind == "continuous":
         pre = args.preprocs
         rate = pre["brain_resample_rate"]
-        seq = int(pre["seq_len_sec"] * rate)
-        n_seg = int(args.get("synthetic_segments", 4 * int(args.batch_size)))
+        seq = D.segment_dims(args).T
         shift_ms = pre.get("shift_len", 150) if pre.get("shift_brain", True) else 0
-        Xc, Yc = synthetic_subject_dataset(args, device, length=n_seg * seq + int(rate * (shift_ms / 1000)) + seq // 3, seed=1234)
-        feed = ResidentSubjectFeed(Xc, Yc, srate=rate, seq_len_sec=pre["seq_len_sec"], baseline_len_sec=pre["baseline_len_sec"],
-                                   clamp_lim=float(pre["clamp_lim"]), clamp=bool(pre["clamp"]),
-                                   subject_wise=bool(pre.get("subject_wise", True)), shift_ms=shift_ms, seed=1234 + 17)
+        Xc, Yc = D.synthetic_subject_dataset(args, device, length=n_seg * seq + int(rate * (shift_ms / 1000)) + seq // 3, seed=1234)
+        feed = D.ResidentSubjectFeed(Xc, Yc, srate=rate, seq_len_sec=pre["seq_len_sec"], baseline_len_sec=pre["baseline_len_sec"],
+                                     clamp_lim=float(pre["clamp_lim"]), clamp=bool(pre["clamp"]),
+                                     subject_wise=bool(pre.get("subject_wise", True)), shift_ms=shift_ms, seed=1234 + 17)
         del Xc, Yc
         n_train = int(len(feed) * float(args.split_ratio))
         perm = np.random.RandomState(1234).permutation(len(feed))
         train_idx, test_idx = perm[:n_train], perm[n_train:]
-        updates = int(args.get("updates_per_epoch", max(1, len(train_idx) // int(args.batch_size))))
-        epoch_no = [0]
-        pack_resident_embeddings = feed
+    else:
+        pool = SyntheticSegments(args, n_seg, device, seed=1234)
+        updates = int(args.get("updates_per_epoch", max(1, len(pool.train_idx) // batch_size)))
+        return None, lambda: pool.train_batches(batch_size, updates), pool.test_batch
+    updates = int(args.get("updates_per_epoch", max(1, len(train_idx) // batch_size)))
+    epoch_no = [0]
 
-        def train_batches():
-            sampler = ShardedRandomSampler(len(train_idx), int(args.batch_size), updates, rank, world, seed=4321 + epoch_no[0])
-            epoch_no[0] += 1
-            yield from feed.batches(sampler, index_map=train_idx)
+    def train_batches():
+        sampler = D.ShardedRandomSampler(len(train_idx), batch_size, updates, rank, world, seed=4321 + epoch_no[0])
+        epoch_no[0] += 1
+        # (under data parallelism the draws for the whole global batch are made on every rank alike and sliced)
+        yield from feed.batches(sampler, index_map=train_idx)
 
-        def test_batch():
-            lo, hi = shard_range(len(test_idx), rank, world)
-            return feed.batch(test_idx[lo:hi])
-        feeds_local_shards = True
-    elif train_batches is None:
-        n_seg = int(args.get("synthetic_segments", 4 * int(args.batch_size)))
-        data = SyntheticSegments(args, n_seg, device, seed=1234)
-        updates = int(args.get("updates_per_epoch", max(1, len(data.train_idx) // int(args.batch_size))))
-        train_batches = lambda: data.train_batches(int(args.batch_size), updates)      # noqa: E731
-        test_batch = data.test_batch
+    def test_batch():
+        lo, hi = shard_range(len(test_idx), rank, world)
+        return feed.batch(test_idx[lo:hi])
+    return feed, train_batches, test_batch
 
-    brain_encoder = BrainEncoder(args).to(device)
-    if feeds_local_shards and "pack_resident_embeddings" in locals():
-        pack_resident_embeddings.pack_embeddings(brain_encoder.compute_dtype)      # Y batches arrive as the loss's packed operand
-    classifier = Classifier(args)
-    loss_kind = str(args.get("loss", "clip")).lower()
-    if loss_kind not in ("clip", "mse"):
-        raise ValueError(f"loss={loss_kind}: expected clip or mse")
-    clip = loss_kind == "clip"
-    loss_func = (CLIPLoss(args) if clip else MSELoss()).to(device)
-    loss_func.train()
-    broadcast_parameters(brain_encoder)
-    # MSELoss has no parameters of its own: Adam steps the encoder alone
-    params = list(brain_encoder.parameters()) + (list(loss_func.parameters()) if clip else [])
-    optimizer = torch.optim.Adam(params, lr=float(args.lr))
-    wandb = None
-    if args.get("use_wandb", False) and rank == 0:
-        import wandb as _wandb
-        wandb = _wandb
-        wandb.init(project=args.wandb.project, entity=args.wandb.entity, config=dict(args), save_code=True)
-        wandb.run.name = args.wandb.run_name + "_" + str(args.split_mode)
 
-    from speech_decoding_amd.amp import LossScaler
-    seq_T = int(args.preprocs["seq_len_sec"] * args.preprocs["brain_resample_rate"])
-    scaler = LossScaler.for_dtype(brain_encoder.compute_dtype, float(args.get("fp16_loss_scale", 1024.0)),
-                                  global_batch=int(args.batch_size), T=seq_T)                      # no-op unless fp16
-
+def make_backward_and_step(brain_encoder, loss_func, params, optimizer, scaler, world: int, device):
+    """backward_and_step(loss) for the loop: backward of the scaled loss, the gradient all-reduce under data parallelism, fp16's
+    overflow guard, Adam."""
+    clip = isinstance(loss_func, CLIPLoss)
     fp16 = scaler.enabled            # (not `scale != 1`: a scale halved down to 1, or fp16_loss_scale=1, keeps the overflow guard)
     one = torch.ones((), dtype=torch.float32, device=device)       # d loss / d loss, resident (autograd would fill one per step)
 
@@ -225,6 +158,75 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
         scaler.update(ok)
         if ok:
             optimizer.step()
+    return backward_and_step
+
+
+def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Callable] = None, log=print):
+    import torch.distributed as dist
+    data_kind = str(args.get("data", "pool"))
+    if train_batches is None and data_kind == "continuous" and args.dataset != "Brennan2018":
+        raise ValueError("data=continuous is Brennan2018's input path (one stimulus, every subject): use dataset=Brennan2018")
+    if train_batches is None and data_kind == "tracks" and args.dataset != "Gwilliams2022":
+        raise ValueError("data=tracks is Gwilliams2022's input path (segments are windows of per-task speech tracks): use "
+                         "dataset=Gwilliams2022")
+    if train_batches is None and data_kind == "tracks":        # fp32: the feed's own refusal, before anything is built
+        D.check_track_dtype("data=tracks", resolve_dtype(args))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local)
+    device = torch.device("cuda", local)
+    from speech_decoding_amd.streams import use_training_stream
+    caller_stream = torch.cuda.current_stream(device)
+    use_training_stream(device)          # the loop's chain on a high-priority stream; the engine's side streams stay normal
+    owns_group = world > 1 and not dist.is_initialized()
+    if owns_group:
+        from speech_decoding_amd.distributed import init_process_group as sda_init_pg
+        sda_init_pg(os.environ.get("SDA_DIST_BACKEND", "nccl"))
+    if args.get("reproducible", False):
+        np.random.seed(0)
+        torch.manual_seed(0)
+    elif world > 1:
+        # SpatialDropout's centre comes from NumPy's global generator (models.py:81) and must be the same on every rank
+        from speech_decoding_amd.distributed import seed_numpy_all_ranks
+        seed_numpy_all_ranks()
+
+    feed = None          # a resident feed hands out this rank's shard; batches of the pool, or the caller's, are whole and sliced here
+    if train_batches is None:
+        feed, train_batches, test_batch = build_data(args, data_kind, device, rank, world)
+
+    def local_shard(batch):
+        X, Y, subject_idxs = batch
+        if world > 1 and feed is None:
+            lo, hi = shard_range(X.shape[0], rank, world)
+            X, Y, subject_idxs = X[lo:hi], Y[lo:hi], subject_idxs[lo:hi]
+        return X, Y, subject_idxs
+
+    brain_encoder = BrainEncoder(args).to(device)
+    if feed is not None:
+        feed.pack_embeddings(brain_encoder.compute_dtype)      # Y batches arrive as the loss's packed operand
+    classifier = Classifier(args)
+    loss_kind = str(args.get("loss", "clip")).lower()
+    if loss_kind not in ("clip", "mse"):
+        raise ValueError(f"loss={loss_kind}: expected clip or mse")
+    clip = loss_kind == "clip"
+    loss_func = (CLIPLoss(args) if clip else MSELoss()).to(device)
+    loss_func.train()
+    broadcast_parameters(brain_encoder)
+    # MSELoss has no parameters of its own: Adam steps the encoder alone
+    params = list(brain_encoder.parameters()) + (list(loss_func.parameters()) if clip else [])
+    optimizer = torch.optim.Adam(params, lr=float(args.lr))
+    wandb = None
+    if args.get("use_wandb", False) and rank == 0:
+        import wandb as _wandb
+        wandb = _wandb
+        wandb.init(project=args.wandb.project, entity=args.wandb.entity, config=dict(args), save_code=True)
+        wandb.run.name = args.wandb.run_name + "_" + str(args.split_mode)
+
+    from speech_decoding_amd.amp import LossScaler
+    scaler = LossScaler.for_dtype(brain_encoder.compute_dtype, float(args.get("fp16_loss_scale", 1024.0)),
+                                  global_batch=int(args.batch_size), T=D.segment_dims(args).T)     # no-op unless fp16
+    backward_and_step = make_backward_and_step(brain_encoder, loss_func, params, optimizer, scaler, world, device)
 
     history = []
     for epoch in range(int(args.epochs)):
@@ -237,13 +239,6 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
         tr_loss, tr_ranks = [], []
         brain_encoder.train()
         loss = None
-        def local_shard(batch):
-            X, Y, subject_idxs = batch
-            if world > 1 and not feeds_local_shards:
-                lo, hi = shard_range(X.shape[0], rank, world)
-                X, Y, subject_idxs = X[lo:hi], Y[lo:hi], subject_idxs[lo:hi]
-            return X, Y, subject_idxs
-
         # The speech side of the loss does not depend on the encoder: it is started ONE BATCH AHEAD, like a data loader —
         # batch n + 1's rows are packed (and, under data parallelism, all-gathered: 197 MB per rank at config 3) while batch
         # n's backward runs, five milliseconds of cover instead of the forward's two and a half.  CLIPLoss keeps two packed
@@ -279,10 +274,7 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
         brain_encoder.eval()
         te_loss, te_top1, te_top10 = [], [], []
         with torch.no_grad():
-            X, Y, subject_idxs = test_batch()
-            if world > 1 and not feeds_local_shards:
-                lo, hi = shard_range(X.shape[0], rank, world)
-                X, Y, subject_idxs = X[lo:hi], Y[lo:hi], subject_idxs[lo:hi]
+            X, Y, subject_idxs = local_shard(test_batch())
             Z = brain_encoder(X, subject_idxs)
             te_loss.append(loss_func(Y, Z).item())
             t1, t10 = classifier(Z, Y, test=True)
