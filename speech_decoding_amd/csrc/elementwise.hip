@@ -477,8 +477,9 @@ __global__ void bn_bwd_coef_kernel(const float* __restrict__ mean, const float* 
   coef[1 * Cp + c] = c < C ? beta[c] : 0.f;
   coef[2 * Cp + c] = mean[c];
   coef[3 * Cp + c] = rstd[c];
-  coef[4 * Cp + c] = dbeta[c] * inv_count;
-  coef[5 * Cp + c] = dgamma[c] * inv_count;
+  // eval mode hands in 1 / N = 0 (no batch-statistics terms): a select, since 0 * the sums would carry one sample's inf / NaN into all
+  coef[4 * Cp + c] = inv_count != 0.f ? dbeta[c] * inv_count : 0.f;
+  coef[5 * Cp + c] = inv_count != 0.f ? dgamma[c] * inv_count : 0.f;
 }
 
 // reduce_stats + bn_bwd_coef in one launch (single-process case: no all-reduce sits between them)
@@ -499,8 +500,8 @@ __global__ __launch_bounds__(256) void bn_bwd_stats_coef_kernel(const float* __r
   coef[1 * Cp + c] = c < C ? beta[c] : 0.f;
   coef[2 * Cp + c] = mean[c];
   coef[3 * Cp + c] = rstd[c];
-  coef[4 * Cp + c] = db * inv_count;
-  coef[5 * Cp + c] = dg * inv_count;
+  coef[4 * Cp + c] = inv_count != 0.f ? db * inv_count : 0.f;          // (a select: see bn_bwd_coef_kernel)
+  coef[5 * Cp + c] = inv_count != 0.f ? dg * inv_count : 0.f;
 }
 
 // DG: `dy` already holds dg = dy * GELU'(gamma * xhat + beta) (a conv epilogue with SDA_EPI_BN_STORE_DG wrote it): the affine

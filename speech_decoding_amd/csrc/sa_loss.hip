@@ -17,7 +17,7 @@ __device__ inline float block_max(float v, float* sh) {
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
-  return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+  return max_nan(max_nan(sh[0], sh[1]), max_nan(sh[2], sh[3]));
 }
 
 // SpatialAttention weights, forward.  a[o][c] = sum_m Re z[o][m] cos[m][c] + Im z[o][m] sin[m][c].
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void sa_fwd_final_kernel(const float* __restri
     a[k] = 0.f;
     if (c < C) {
       for (int j = 0; j < nchunk; ++j) a[k] += part[((size_t)j * D1 + o) * ppitch + c];
-      mx = fmaxf(mx, a[k]);
+      mx = max_nan(mx, a[k]);
     }
   }
   mx = block_max(mx, sh);
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void clip_rows_kernel(const float* __restrict_
   for (int j = tid; j < Bn; j += 256) {
     const float l = S[(size_t)i * s_pitch + j] * ri / sqrtf(zsq[j]);
     logits[(size_t)i * Bn + j] = l;
-    mx = fmaxf(mx, l);
+    mx = max_nan(mx, l);
     if (col0 + j == i) diag[i] = l;
   }
   mx = block_max(mx, sh);
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void clip_cols_kernel(const float* __restrict_
   __shared__ float sh[4];
   const int j = blockIdx.x, tid = threadIdx.x;
   float mx = -INFINITY;
-  for (int i = tid; i < Bm; i += 256) mx = fmaxf(mx, logits[(size_t)i * Bn + j]);
+  for (int i = tid; i < Bm; i += 256) mx = max_nan(mx, logits[(size_t)i * Bn + j]);
   mx = block_max(mx, sh);
   float sum = 0.f;
   for (int i = tid; i < Bm; i += 256) sum += expf(logits[(size_t)i * Bn + j] - mx);
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void clip_grad_kernel(const float* __restrict_
     return;
   }
   float ymax2 = 0.f;
-  for (int i = tid; i < Bm; i += 256) ymax2 = fmaxf(ymax2, ysq[i]);
+  for (int i = tid; i < Bm; i += 256) ymax2 = max_nan(ymax2, ysq[i]);
   ymax2 = block_max(ymax2, sh);
   const float ymax = sqrtf(ymax2);
   const float alpha = expf(temp[0]);
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(256) void clip_grad_y_kernel(const float* __restric
   const int c0 = blockIdx.x * 64, jt = blockIdx.y, j0 = jt * 64, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int nparts = (Bn + 63) / 64;
   float zmax2 = 0.f;
-  for (int k = tid; k < nz; k += 256) zmax2 = fmaxf(zmax2, zsq_all[k]);
+  for (int k = tid; k < nz; k += 256) zmax2 = max_nan(zmax2, zsq_all[k]);
   const float zmax = sqrtf(block_max(zmax2, sh));
   const int j = j0 + lane;
   const bool jv = j < Bn;
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(256) void clip_grad_y_kernel(const float* __restric
       if (i == col0 + j) d -= 2.f;
       dl = d * l;
     }
-    tile[cc][lane] = d * zf;
+    tile[cc][lane] = (iv && jv) ? d * zf : 0.f;       // (a select: 0 * zf would carry a non-finite zf into the pad columns)
     dl = wave_sum(dl);
     if (iv && jt < nparts && lane == 0) part[(size_t)jt * Bm + i] = dl;
   }
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256) void clip_grad_y_finish_kernel(const float* __
   __shared__ float sh[4];
   const int tid = threadIdx.x, r = blockIdx.x * 256 + tid;
   float zmax2 = 0.f;
-  for (int k = tid; k < nz; k += 256) zmax2 = fmaxf(zmax2, zsq_all[k]);
+  for (int k = tid; k < nz; k += 256) zmax2 = max_nan(zmax2, zsq_all[k]);
   const float zmax = sqrtf(block_max(zmax2, sh));
   if (r >= nrows) return;
   const int i = row0 + r;
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(256) void clip_merge_rows_kernel(const float* __res
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= Bg) return;
   float M = -INFINITY;
-  for (int r = 0; r < world; ++r) M = fmaxf(M, all[((size_t)r * 3 + 0) * Bg + i]);
+  for (int r = 0; r < world; ++r) M = max_nan(M, all[((size_t)r * 3 + 0) * Bg + i]);
   float S = 0.f, D = 0.f;
   for (int r = 0; r < world; ++r) {
     S += all[((size_t)r * 3 + 1) * Bg + i] * expf(all[((size_t)r * 3 + 0) * Bg + i] - M);

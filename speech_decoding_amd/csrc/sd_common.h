@@ -300,9 +300,12 @@ __device__ inline float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
+// fmaxf returns the other operand when one is NaN: a maximum that decides a stored value (a soft-max's shift, a range factor)
+// would then hide a NaN that fp16's overflow guard has to see.  This one hands it on.
+__device__ inline float max_nan(float a, float b) { return (a != a || b != b) ? a + b : fmaxf(a, b); }
 __device__ inline float wave_max(float v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  for (int o = 32; o > 0; o >>= 1) v = max_nan(v, __shfl_xor(v, o));
   return v;
 }
 

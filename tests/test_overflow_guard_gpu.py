@@ -1,0 +1,313 @@
+"""The fp16 overflow guard, run for real on an MI355X: train.make_backward_and_step with the project's Adam and
+LossScaler(scale, enabled=True) on the toy shape, under CLIPLoss and MSELoss, single process and two data-parallel ranks.
+
+An activation gradient that overflows fp16 must reach a parameter gradient as inf / NaN (tests/test_nonfinite_gpu.py holds every
+kernel on the way to that); then unscale_(check=True) returns False, the step is skipped and the scale halved.  A swallowed
+overflow would not crash: Adam would be fed a wrong, finite gradient.
+
+The overflow scale comes from the float64 oracle, never from the code under test: g = max |dL/dZ| at scale 1, and the scale is
+the smallest power of two s with s g >= 4 x 65504 — two binades past fp16's range, far more than the fp16 path's gradient error
+(GRAD_REL 8e-3 in tests/test_e2e_gpu.py), so the first stored activation gradient overflows whatever the rounding does.
+Backward is linear in the scale: no other number is needed.  The default scale (1024) at these shapes is the one
+tests/test_e2e_gpu.py asserts healthy: it is the "no false alarm" scale here."""
+import datetime
+import math
+import os
+import socket
+
+import pytest
+import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
+import torch.nn.functional as TF
+
+pytestmark = pytest.mark.gpu
+
+from oracle import brain_oracle as O      # noqa: E402
+
+DEV = "cuda:0"
+TOY = dict(C=20, S=3, D1=32, D2=48, F=64, K=4, T=70)
+B = 12                        # one process; two ranks take 6 each
+TEMP = 3.0
+CENTRE = 4
+FP16_MAX = 65504.0
+MARGIN = 4.0
+LOSSES = ["clip", "mse"]
+
+
+class Args(dict):
+    __getattr__ = dict.__getitem__
+
+
+def problem():
+    d = TOY
+    loc = O.synthetic_positions(d["C"], seed=1)
+    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=2, loc=loc)
+    X, Y, subj = O.synthetic_batch(B, d["C"], d["T"], d["F"], d["S"], seed=3)
+    return loc, P, X, Y, subj
+
+
+def double(P):
+    return {k: (v.to(torch.complex128) if v.is_complex() else v.double() if v.is_floating_point() else v) for k, v in P.items()}
+
+
+def pow2_at_least(x):
+    return 2.0 ** math.ceil(math.log2(x))
+
+
+def oracle_Z(loc, P, X, subj):
+    """the float64 oracle's embeddings of a training-mode forward"""
+    return O.brain_encoder_forward(double(P), X.double(), subj, training=True, loc=loc, drop_centre=CENTRE).detach()
+
+
+def oracle_dZ(kind, Y, Z):
+    """dL/dZ of the float64 oracle at loss scale 1: (B, F, T)"""
+    Z = Z.clone().requires_grad_(True)
+    if kind == "clip":
+        loss, _ = O.clip_loss(Y.double(), Z, torch.tensor([TEMP], dtype=torch.float64))
+    else:
+        loss = ((Y.double() - Z) ** 2).sum(dim=(1, 2)).mean()
+    (dZ,) = torch.autograd.grad(loss, [Z])
+    return dZ
+
+
+def overflow_scale(dZ):
+    return pow2_at_least(MARGIN * FP16_MAX / float(dZ.abs().max()))
+
+
+def build(kind, P, loc):
+    from speech_decoding.models import BrainEncoder
+    from speech_decoding.utils.loss import CLIPLoss, MSELoss
+    d = TOY
+    args = Args(num_subjects=d["S"], D1=d["D1"], D2=d["D2"], F=d["F"], K=d["K"], dataset="Gwilliams2022", d_drop=0.1, root_dir=".",
+                preprocs={"last4layers": False}, reduction="mean", init_temperature=TEMP, sensor_positions=loc.numpy(),
+                compute_dtype="fp16")
+    enc = BrainEncoder(args)
+    enc.load_state_dict(P)
+    enc = enc.to(DEV).train()
+    enc.set_drop_centre(CENTRE)
+    lossf = (CLIPLoss(args) if kind == "clip" else MSELoss()).to(DEV)
+    lossf.train()
+    return enc, lossf
+
+
+class Run:
+    """encoder + loss + Adam + scaler + train.py's step, as train.run() wires them"""
+
+    def __init__(self, kind, P, loc, world=1, scale=None):
+        import train
+        from speech_decoding_amd.amp import DEFAULT_FP16_SCALE, LossScaler
+        from speech_decoding_amd.optim import FusedAdam
+        self.enc, self.lossf = build(kind, P, loc)
+        self.params = list(self.enc.parameters()) + list(self.lossf.parameters())
+        self.opt = FusedAdam(self.params, lr=1e-3)
+        self.scaler = LossScaler(DEFAULT_FP16_SCALE if scale is None else scale, enabled=True)
+        self.oks = []                 # what every unscale_() of the step returned, in order
+        unscale = self.scaler.unscale_
+        self.scaler.unscale_ = lambda params, check=False: self.oks.append(unscale(params, check=check)) or self.oks[-1]
+        self.step = train.make_backward_and_step(self.enc, self.lossf, self.params, self.opt, self.scaler, world, torch.device(DEV))
+
+    def forward(self, X, Y, subj):
+        Z = self.enc(X.to(DEV), subj)
+        return self.lossf(Y.to(DEV), Z)
+
+    def train_step(self, X, Y, subj):
+        loss = self.forward(X, Y, subj)
+        self.step(loss)
+        return float(loss.detach())
+
+    def state(self):
+        """every parameter (the temperature included), every Adam moment and step count, as host copies"""
+        torch.cuda.synchronize()
+        real = lambda t: (torch.view_as_real(t) if t.is_complex() else t).detach().cpu().clone()
+        out = {}
+        for i, p in enumerate(self.params):
+            out[f"param {i}"] = real(p)
+            st = self.opt.state.get(p, {})
+            out[f"step {i}"] = torch.tensor(int(st.get("step", 0)))
+            for k in ("exp_avg", "exp_avg_sq"):
+                if k in st:
+                    out[f"{k} {i}"] = real(st[k])
+        return out
+
+    def bn_state(self):
+        torch.cuda.synchronize()
+        return {k: v.detach().cpu().clone() for k, v in self.enc.state_dict().items()
+                if k.endswith(("running_mean", "running_var", "num_batches_tracked"))}
+
+
+def same_bits(a, b):
+    assert a.keys() == b.keys(), sorted(set(a) ^ set(b))
+    bad = [k for k in a if a[k].dtype != b[k].dtype or a[k].shape != b[k].shape
+           or not torch.equal(a[k].reshape(-1).contiguous().view(torch.uint8), b[k].reshape(-1).contiguous().view(torch.uint8))]
+    return bad
+
+
+@pytest.mark.parametrize("kind", LOSSES)
+def test_backward_overflow_skips_the_step_and_leaves_no_trace(kind):
+    from speech_decoding_amd.amp import DEFAULT_FP16_SCALE
+    loc, P, X, Y, subj = problem()
+    dZ = oracle_dZ(kind, Y, oracle_Z(loc, P, X, subj))
+    s = overflow_scale(dZ)
+    print(f"{kind}: oracle max |dL/dZ| {float(dZ.abs().max()):.4e}, overflow scale 2^{int(math.log2(s))}")
+    assert s * float(dZ.abs().max()) >= MARGIN * FP16_MAX > 0.5 * s * float(dZ.abs().max()) and s > DEFAULT_FP16_SCALE
+    X2, Y2, subj2 = O.synthetic_batch(B, TOY["C"], TOY["T"], TOY["F"], TOY["S"], seed=5)
+    run, twin = Run(kind, P, loc), Run(kind, P, loc)
+    # a healthy step first: Adam's moments exist, and the two runs start from the same bits
+    for r in (run, twin):
+        r.train_step(X2, Y2, subj2)
+        assert r.oks == [True] and r.scaler.skipped_steps == 0 and r.scaler.scale_value == DEFAULT_FP16_SCALE, "a false alarm at the default scale"
+    before = run.state()
+    assert same_bits(before, twin.state()) == [] and all(int(v) == 1 for k, v in before.items() if k.startswith("step"))
+    # the overflowing step
+    run.scaler.scale_value = s
+    loss = run.train_step(X, Y, subj)
+    assert math.isfinite(loss), "the forward does not depend on the loss scale"
+    assert run.oks == [True, False], run.oks                    # unscale_(check=True) itself returned False
+    assert run.scaler.skipped_steps == 1 and run.scaler.scale_value == s / 2, (run.scaler.skipped_steps, run.scaler.scale_value)
+    assert same_bits(run.state(), before) == [], "a skipped step moved a parameter, a moment or a step count"
+    # the forward moved the running statistics as it does in any step; the overflowing backward did not touch them
+    float(twin.forward(X, Y, subj).detach())
+    assert same_bits(run.bn_state(), twin.bn_state()) == []
+    # back at the default scale the next step is taken and equals the twin's, which never saw the overflow
+    run.scaler.scale_value = DEFAULT_FP16_SCALE
+    X3, Y3, subj3 = O.synthetic_batch(B, TOY["C"], TOY["T"], TOY["F"], TOY["S"], seed=7)
+    for r in (run, twin):
+        r.train_step(X3, Y3, subj3)
+    assert run.oks == [True, False, True] and twin.oks == [True, True]
+    assert run.scaler.skipped_steps == 1 and twin.scaler.skipped_steps == 0
+    after = run.state()
+    assert all(int(v) == 2 for k, v in after.items() if k.startswith("step"))
+    assert same_bits(after, twin.state()) == [], "the skipped step left a trace in a parameter or a moment"
+    assert same_bits(after, before) != []
+    assert same_bits(run.bn_state(), twin.bn_state()) == []
+
+
+def pre_batchnorm_activation(loc, P, X, subj):
+    """the first ConvBlock's conv0 output: the last tensor in front of the first BatchNorm, which the encoder stores in fp16 for
+    that BatchNorm's statistics.  Everything up to it scales with the input; nothing behind the BatchNorm does."""
+    Q = double(P)
+    h = O.subject_block(Q, X.double(), subj, O.dropout_mask(loc, CENTRE, 0.1))
+    d0 = O.block_dilations(0)[0]
+    return TF.conv1d(h, Q["conv_blocks.conv0.conv0.weight"], Q["conv_blocks.conv0.conv0.bias"], padding=d0, dilation=d0)
+
+
+@pytest.mark.parametrize("kind", LOSSES)
+def test_forward_overflow_skips_the_step(kind):
+    """the input scaled until a stored fp16 activation passes 65504 by the margin of 4: the loss is non-finite, the step is skipped,
+    parameters and moments stay.  (The running statistics have moved, as under torch.cuda.amp; train.py says so, and nothing is
+    asserted on them.)"""
+    from speech_decoding_amd.amp import DEFAULT_FP16_SCALE
+    loc, P, X, Y, subj = problem()
+    a = float(pre_batchnorm_activation(loc, P, X, subj).abs().max())
+    f = pow2_at_least(MARGIN * FP16_MAX / a)
+    big = float(pre_batchnorm_activation(loc, P, X * f, subj).abs().max())
+    print(f"{kind}: oracle max |activation in front of the first BatchNorm| {a:.4e}, input factor 2^{int(math.log2(f))}, then {big:.4e}")
+    assert big >= 0.5 * MARGIN * FP16_MAX                       # (the bias does not scale: within a factor of two of f a)
+    run = Run(kind, P, loc)
+    X2, Y2, subj2 = O.synthetic_batch(B, TOY["C"], TOY["T"], TOY["F"], TOY["S"], seed=5)
+    run.train_step(X2, Y2, subj2)
+    before = run.state()
+    loss = run.train_step(X * f, Y, subj)
+    assert not math.isfinite(loss)
+    assert run.oks == [True, False], run.oks
+    assert run.scaler.skipped_steps == 1 and run.scaler.scale_value == DEFAULT_FP16_SCALE / 2
+    assert same_bits(run.state(), before) == []
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# data parallel: two gloo ranks on one device; only rank 0's shard carries the sample that overflows
+# ---------------------------------------------------------------------------------------------------------------
+def dp_problem(kind):
+    """(X, Y, subj, scale, per-sample max |dL/dZ| x scale).  MSE: sample 0's target is scaled until its own dL/dZ overflows at the
+    DEFAULT scale; every other sample's gradient is as healthy as ever.  CLIP (whose dZ couples the ranks through the global
+    negatives): rank 1's speech rows are its own brain embeddings, which leaves its dL/dZ an order of magnitude below rank
+    0's; the scale is the oracle's overflow scale of the whole batch, and rank 1's dL/dZ stays inside fp16 at it."""
+    from speech_decoding_amd.amp import DEFAULT_FP16_SCALE
+    loc, P, X, Y, subj = problem()
+    Z = oracle_Z(loc, P, X, subj)
+    Y = Y.clone()
+    if kind == "mse":
+        g0 = float(oracle_dZ(kind, Y, Z)[0].abs().max())
+        k = pow2_at_least(2 * MARGIN * FP16_MAX / (DEFAULT_FP16_SCALE * g0))      # dL/dZ[0] = 2 (Z[0] - k Y[0]) / B grows with k
+        Y[0] *= k
+        scale = DEFAULT_FP16_SCALE
+    else:
+        Y[B // 2:] = Z[B // 2:].float()
+        scale = overflow_scale(oracle_dZ(kind, Y, Z))
+    per_sample = scale * oracle_dZ(kind, Y, Z).abs().amax(dim=(1, 2))
+    return loc, P, X, Y, subj, scale, per_sample
+
+
+@pytest.mark.parametrize("kind", LOSSES)
+def test_dp_problem_overflows_on_rank_0_only(kind):
+    """the oracle's word on the data-parallel cases (no GPU work): scaled dL/dZ passes 4 x 65504 in rank 0's shard and stays
+    inside fp16, with the fp16 path's error to spare, in every sample of rank 1's"""
+    *_, Y, _, scale, per_sample = dp_problem(kind)
+    print(f"{kind}: scale 2^{int(math.log2(scale))}, scaled max |dL/dZ| per sample {[f'{float(v):.3e}' for v in per_sample]}")
+    assert float(per_sample[:B // 2].max()) >= MARGIN * FP16_MAX
+    assert float(per_sample[B // 2:].max()) * 1.1 < FP16_MAX
+    assert float(Y.abs().max()) < FP16_MAX
+
+
+DP_CASES = [(kind, overlap) for kind in LOSSES for overlap in (True, False)]       # overlap: the engine's own reduction inside backward
+
+
+def _worker(rank, world, port, ret):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+                      HSA_ENABLE_IPC_MODE_LEGACY="0")
+    torch.cuda.set_device(DEV)
+    # short collective timeout: if one rank fails, the other errors out instead of blocking the run
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=90))
+    try:
+        from speech_decoding_amd.distributed import shard_range
+        problems = {kind: dp_problem(kind) for kind in LOSSES}
+        lo, hi = shard_range(B, rank, world)
+        for kind, overlap in DP_CASES:
+            loc, P, X, Y, subj, scale, _ = problems[kind]
+            run = Run(kind, P, loc, world=world, scale=scale)
+            run.enc.engine.overlap_grad_allreduce = overlap
+            assert run.enc.grads_are_reduced == overlap
+            before = run.state()
+            loss = run.train_step(X[lo:hi], Y[lo:hi], subj[lo:hi])
+            after = run.state()
+            ret[(rank, kind, overlap)] = dict(ok=run.oks, scale=run.scaler.scale_value, skipped=run.scaler.skipped_steps, loss=loss, start_scale=scale,
+                                              moved=same_bits(after, before), params={k: v for k, v in after.items() if k.startswith("param")})
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.fixture(scope="module")
+def two_ranks():
+    """one pair of processes (the worker and spawn pattern of tests/test_dp_gpu.py) steps every case of DP_CASES once"""
+    world = 2
+    ctx = mp.get_context("spawn")
+    ret = ctx.Manager().dict()
+    with socket.socket() as sock:
+        sock.bind(("127.0.0.1", 0))
+        port = sock.getsockname()[1]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, ret)) for r in range(world)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(300)
+    for p in procs:
+        if p.is_alive():
+            p.terminate()
+            p.join(10)
+    assert [p.exitcode for p in procs] == [0] * world
+    return dict(ret)
+
+
+@pytest.mark.parametrize("kind,overlap", DP_CASES, ids=[f"{k}-{'engine-reduction' if o else 'allreduce_gradients'}" for k, o in DP_CASES])
+def test_two_ranks_skip_the_same_step(two_ranks, kind, overlap):
+    """train.py: "SUM of the still-scaled gradients: every rank then sees the same overflow, or none".  If one rank skipped and
+    the other stepped, the replicas would diverge and nothing would report it.  Both gradient paths: the engine's own reduction
+    inside backward (grads_are_reduced) and allreduce_gradients after it."""
+    out = [two_ranks[(r, kind, overlap)] for r in range(2)]
+    for r in range(2):
+        assert out[r]["ok"] == [False], (r, out[r]["ok"])
+        assert out[r]["skipped"] == 1 and out[r]["scale"] == out[r]["start_scale"] / 2, (r, out[r]["scale"])
+        assert out[r]["moved"] == [], (r, "a skipped step moved", out[r]["moved"])
+    assert out[0]["scale"] == out[1]["scale"]
+    assert same_bits(out[0]["params"], out[1]["params"]) == []
