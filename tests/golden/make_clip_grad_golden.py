@@ -22,17 +22,15 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 REF = os.environ.get("SD_REFERENCE", "/root/reference")
 sys.dont_write_bytecode = True
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, REF)
 
 from speech_decoding.utils.loss import CLIPLoss as RefCLIPLoss      # noqa: E402  (the reference)
+from speech_decoding_amd.config import Config                        # noqa: E402
 
 SHAPES = [(4, 72, 25), (2, 100, 9), (6, 64, 19)]
 TEMPS = [2.3, 0.7, 1.5]
 CASES = [("fast-mean", True, "mean"), ("fast-sum", True, "sum"), ("slow-mean", False, "mean"), ("slow-sum", False, "sum")]
-
-
-class Args(dict):
-    __getattr__ = dict.__getitem__
 
 
 def main():
@@ -43,7 +41,7 @@ def main():
         y = torch.randn(B, F, T, generator=g)
         out[f"s{i}/x"], out[f"s{i}/y"] = x.numpy(), y.numpy()
         for name, fast, reduction in CASES:
-            crit = RefCLIPLoss(Args(reduction=reduction, init_temperature=t0))
+            crit = RefCLIPLoss(Config(reduction=reduction, init_temperature=t0))
             xl, yl = x.clone().requires_grad_(True), y.clone().requires_grad_(True)
             loss = crit(xl, yl, fast=fast)
             loss.backward()

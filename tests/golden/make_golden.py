@@ -49,15 +49,11 @@ import speech_decoding.models as ref_models            # noqa: E402  (the refere
 from speech_decoding.utils.loss import CLIPLoss as RefCLIPLoss  # noqa: E402
 
 from oracle import brain_oracle as O                    # noqa: E402  (input generators only)
-
-
-class Args(dict):
-    """attribute + item access, like the Hydra DictConfig the reference receives."""
-    __getattr__ = dict.__getitem__
+from speech_decoding_amd.config import Config           # noqa: E402  (attribute + item access, like the Hydra DictConfig)
 
 
 def make_args(C, S, D1, D2, F, K, last4layers):
-    return Args(num_subjects=S, D1=D1, D2=D2, F=F, K=K, dataset="Gwilliams2022", d_drop=0.1,
+    return Config(num_subjects=S, D1=D1, D2=D2, F=F, K=K, dataset="Gwilliams2022", d_drop=0.1,
                 root_dir="/nonexistent", preprocs={"last4layers": last4layers}, reduction="mean",
                 init_temperature=5.1, num_channels=C)
 
@@ -170,7 +166,7 @@ def gen_classifier():
     g = torch.Generator().manual_seed(5)
     Y = torch.randn(B, F, T, generator=g)
     Z = 0.12 * Y + torch.randn(B, F, T, generator=g)      # partially aligned ⇒ non-trivial ranks
-    clf = ref_models.Classifier(Args())
+    clf = ref_models.Classifier(Config())
     top1, top10 = clf(Z, Y)
     np.savez_compressed(os.path.join(HERE, "classifier.npz"), Z=Z.numpy(), Y=Y.numpy(),
                         top1=np.float64(top1), top10=np.float64(top10))

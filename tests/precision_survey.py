@@ -12,7 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import brain_oracle as O          # noqa: E402   (test infrastructure)
 from tests.parity import operands_as_device_sees_them, rel_l2, round_to, temp_grad_terms_norm      # noqa: E402
-from tests.test_e2e_gpu import build, grads_by_state_key, make_args, null_grad   # noqa: E402
+from tests.builders import grads_by_state_key, null_bias_grad   # noqa: E402
+from tests.test_e2e_gpu import build, make_args                  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -53,7 +54,7 @@ def survey(name, C, S, T, B, dtype, D1=270, D2=320, F=1024, K=32, last4=True, se
         if ref is None or g is None:
             continue
         e = rel_l2(g, ref)
-        worst.append((e, k, null_grad(k)))
+        worst.append((e, k, null_bias_grad(k)))
     for e, k, ng in sorted(worst, reverse=True)[:14]:
         print(f"   {e:.3e}  {k}{'  (null-gradient bias)' if ng else ''}")
 

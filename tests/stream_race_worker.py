@@ -21,7 +21,7 @@ import torch.distributed as dist
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from oracle import brain_oracle as O                                   # noqa: E402  (seeded parameters / inputs only)
+from tests.builders import toy_problem                                 # noqa: E402  (seeded parameters / inputs only)
 from tests.test_dp_gpu import REAL_208, build                          # noqa: E402
 from speech_decoding_amd import loss as sda_loss                       # noqa: E402
 from speech_decoding_amd.distributed import active_group, allreduce_gradients   # noqa: E402
@@ -75,9 +75,7 @@ def main():
     dist.init_process_group("nccl", rank=0, world_size=1, timeout=datetime.timedelta(seconds=120), device_id=torch.device(DEV))
     assert active_group() is not None
     d = dict(REAL_208, B=16)
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=2, loc=loc)
-    X, Y, subj = O.synthetic_batch(d["B"], d["C"], d["T"], d["F"], d["S"], seed=3)
+    _, P, X, Y, subj = toy_problem(d, d["B"])
     bad = []
     for dp in (False, True):
         multi = run(dtype, d, P, X, Y, subj, True, dp)                 # FIRST: the run whose buffers are all first-use

@@ -7,9 +7,7 @@ train.py tests depend on the values."""
 import numpy as np
 import torch
 
-
-class Args(dict):
-    __getattr__ = dict.__getitem__
+from tests.builders import Config
 
 
 C, F, S, RATE = 6, 5, 3, 8                      # T = 8 samples, 2 of them baseline; default hop 4
@@ -17,7 +15,7 @@ SEED = 1234
 
 
 def args(dataset="Gwilliams2022"):
-    return Args(dataset=dataset, num_channels=C, F=F, num_subjects=S, split_ratio=0.7,
+    return Config(dataset=dataset, num_channels=C, F=F, num_subjects=S, split_ratio=0.7,
                 preprocs=dict(brain_resample_rate=RATE, seq_len_sec=1, baseline_len_sec=0.25, last4layers=False, clamp_lim=20.0,
                               clamp=True, shift_len=150))
 

@@ -9,12 +9,9 @@ import pytest
 import torch
 
 from tests import golden_io as G
+from tests.builders import clip_loss
 
 CASES = [("fast-mean", True, "mean"), ("fast-sum", True, "sum"), ("slow-mean", False, "mean"), ("slow-sum", False, "sum")]
-
-
-class Args(dict):
-    __getattr__ = dict.__getitem__
 
 
 def clip_formula(x, y, temp, fast, reduction):
@@ -79,9 +76,8 @@ def test_dx_of_the_formula_is_autograd_of_the_loss():
 
 
 def test_cpu_operands_with_x_requiring_grad_raise():
-    from speech_decoding.utils.loss import CLIPLoss
     from speech_decoding_amd.lib import SdaError
-    crit = CLIPLoss(Args(reduction="mean", init_temperature=1.0))
+    crit = clip_loss(1.0, "cpu")
     x = torch.randn(3, 16, 5, requires_grad=True)
     y = torch.randn(3, 16, 5, requires_grad=True)
     with pytest.raises(SdaError):

@@ -1,80 +1,48 @@
 """CLIPLoss's speech-side gradient under data parallelism on ONE MI355X: two ranks (gloo rendezvous, both on cuda:0, a fresh
 process each) hold the two halves of a batch; the concatenated dY rows and dZ rows equal one process on the global batch, and
 each rank's result is the same bits run to run."""
-import datetime
-import os
-import socket
-
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 pytestmark = pytest.mark.gpu
+
+from tests.builders import clip_loss      # noqa: E402
+from tests.ranks import run_ranks          # noqa: E402
 
 B_RANK, F, T = 6, 64, 70
 
 
-class Args(dict):
-    __getattr__ = dict.__getitem__
-
-
-def _worker(rank, world, port, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      HSA_ENABLE_IPC_MODE_LEGACY="0")
-    dev = "cuda:0"
-    torch.cuda.set_device(dev)
-    # short collective timeout: if one rank fails, the other errors out instead of blocking the run
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=90))
-    try:
-        from speech_decoding.utils.loss import CLIPLoss
-        from speech_decoding_amd.distributed import shard_range
-        Bg = B_RANK * world
-        g = torch.Generator().manual_seed(77)
-        Yf, Zf = torch.randn(Bg, F, T, generator=g), torch.randn(Bg, F, T, generator=g)
-        lo, hi = shard_range(Bg, rank, world)
-        res = {}
-        for name, dtype in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
-            runs = []
-            crit = CLIPLoss(Args(reduction="mean", init_temperature=2.0)).to(dev)
-            for _ in range(2):
-                x = Yf[lo:hi].to(dtype).to(dev).requires_grad_(True)
-                y = Zf[lo:hi].to(dtype).to(dev).requires_grad_(True)
-                loss = crit(x, y)
-                dx, dy, dt = torch.autograd.grad(loss, [x, y, crit.temp])
-                runs.append(dict(loss=float(loss), dx=dx.float().cpu(), dy=dy.float().cpu(), dt=dt.cpu()))
-            res[name] = runs
-            if rank == 0:      # single-process reference on the whole batch, collectives switched off
-                crit1 = CLIPLoss(Args(reduction="mean", init_temperature=2.0)).to(dev)
-                crit1.global_negatives = False
-                x1 = Yf.to(dtype).to(dev).requires_grad_(True)
-                y1 = Zf.to(dtype).to(dev).requires_grad_(True)
-                l1 = crit1(x1, y1)
-                dx1, dy1 = torch.autograd.grad(l1, [x1, y1])
-                res[name + "/ref"] = dict(loss=float(l1), dx=dx1.float().cpu(), dy=dy1.float().cpu())
-        ret[rank] = res
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world, dev):
+    from speech_decoding_amd.distributed import shard_range
+    Bg = B_RANK * world
+    g = torch.Generator().manual_seed(77)
+    Yf, Zf = torch.randn(Bg, F, T, generator=g), torch.randn(Bg, F, T, generator=g)
+    lo, hi = shard_range(Bg, rank, world)
+    res = {}
+    for name, dtype in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
+        runs = []
+        crit = clip_loss(2.0, dev)
+        for _ in range(2):
+            x = Yf[lo:hi].to(dtype).to(dev).requires_grad_(True)
+            y = Zf[lo:hi].to(dtype).to(dev).requires_grad_(True)
+            loss = crit(x, y)
+            dx, dy, dt = torch.autograd.grad(loss, [x, y, crit.temp])
+            runs.append(dict(loss=float(loss), dx=dx.float().cpu(), dy=dy.float().cpu(), dt=dt.cpu()))
+        res[name] = runs
+        if rank == 0:      # single-process reference on the whole batch, collectives switched off
+            crit1 = clip_loss(2.0, dev)
+            crit1.global_negatives = False
+            x1 = Yf.to(dtype).to(dev).requires_grad_(True)
+            y1 = Zf.to(dtype).to(dev).requires_grad_(True)
+            l1 = crit1(x1, y1)
+            dx1, dy1 = torch.autograd.grad(l1, [x1, y1])
+            res[name + "/ref"] = dict(loss=float(l1), dx=dx1.float().cpu(), dy=dy1.float().cpu())
+    return res
 
 
 def test_two_ranks_dy_matches_one_process_on_the_global_batch():
     world = 2
-    ctx = mp.get_context("spawn")
-    ret = ctx.Manager().dict()
-    with socket.socket() as sock:
-        sock.bind(("127.0.0.1", 0))
-        port = sock.getsockname()[1]
-    procs = [ctx.Process(target=_worker, args=(r, world, port, ret)) for r in range(world)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(300)
-    for p in procs:
-        if p.is_alive():
-            p.terminate()
-            p.join(10)
-    assert [p.exitcode for p in procs] == [0] * world
-    out = dict(ret)
+    out = run_ranks(_worker, world)
     for name, tol in (("fp32", 1e-5), ("bf16", 2e-2)):
         ref = out[0][name + "/ref"]
         for r in range(world):

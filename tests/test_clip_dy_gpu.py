@@ -9,6 +9,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import brain_oracle as O      # noqa: E402
+from tests import builders as TB          # noqa: E402
 from tests import golden_io as G           # noqa: E402
 from tests.parity import rel_l2            # noqa: E402
 
@@ -16,16 +17,11 @@ DEV = "cuda:0"
 DT = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
 GRAD_REL_L2 = {"fp32": 1e-5, "bf16": 6e-2, "fp16": 8e-3}      # every gradient 6e-2 / 8e-3 in the 16-bit modes
 CASES = [("fast-mean", True, "mean"), ("fast-sum", True, "sum"), ("slow-mean", False, "mean"), ("slow-sum", False, "sum")]
-TOY = dict(C=20, S=3, D1=32, D2=48, F=64, K=4, T=70, B=6)
-
-
-class Args(dict):
-    __getattr__ = dict.__getitem__
+TOY = dict(TB.TOY, B=6)
 
 
 def clip(reduction="mean", temp=2.0):
-    from speech_decoding.utils.loss import CLIPLoss
-    return CLIPLoss(Args(reduction=reduction, init_temperature=temp)).to(DEV)
+    return TB.clip_loss(temp, DEV, reduction)
 
 
 def ref_clip(x, y, temp, fast=True, reduction="mean"):
@@ -192,14 +188,7 @@ def test_rows_dx_buffer_contract_on_poisoned_memory(dtype):
 
 
 def build_encoder(P, d, seed_drop=4):
-    from speech_decoding.models import BrainEncoder
-    loc = O.synthetic_positions(d["C"], seed=1)
-    args = Args(num_subjects=d["S"], D1=d["D1"], D2=d["D2"], F=d["F"], K=d["K"], dataset="Gwilliams2022", d_drop=0.1,
-                root_dir=".", preprocs={"last4layers": False}, reduction="mean", init_temperature=2.0,
-                sensor_positions=loc.numpy(), compute_dtype="fp32")
-    enc = BrainEncoder(args)
-    enc.load_state_dict(P)
-    enc = enc.to(DEV).train()
+    enc = TB.build_encoder(P, d, DEV)
     enc.set_drop_centre(seed_drop)
     return enc
 
@@ -208,11 +197,8 @@ def test_two_brain_encoders_brain_to_brain():
     """Two trainable towers: the first argument is a second BrainEncoder's row-layout output; its dY goes back into that
     encoder zero-copy, and the encoder's parameter gradients equal a separate backward of the same dY."""
     d = TOY
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P1 = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=2, loc=loc)
-    P2 = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=12, loc=loc)
-    X1, _, subj = O.synthetic_batch(d["B"], d["C"], d["T"], d["F"], d["S"], seed=3)
-    X2, _, _ = O.synthetic_batch(d["B"], d["C"], d["T"], d["F"], d["S"], seed=13)
+    _, P1, X1, _, subj = TB.toy_problem(d, d["B"])
+    _, P2, X2, _, _ = TB.toy_problem(d, d["B"], param_seed=12, batch_seed=13)
     enc1, enc2 = build_encoder(P1, d), build_encoder(P2, d)
     crit = clip()
     Z = enc1(X1.to(DEV), subj)
@@ -308,9 +294,7 @@ def test_prefetch_equals_no_prefetch():
 # ------------------------------------------------------------------------------------------------------------------------------
 def test_joint_adam_steps_match_cpu_float64():
     d = TOY
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=2, loc=loc)
-    X, _, subj = O.synthetic_batch(d["B"], d["C"], d["T"], d["F"], d["S"], seed=3)
+    loc, P, X, _, subj = TB.toy_problem(d, d["B"])
     M = randn(d["B"], 20, d["T"], seed=61)                  # a Mel-spectrogram-like speech input
     torch.manual_seed(0)
     speech = torch.nn.Sequential(torch.nn.Conv1d(20, d["F"], 3, padding=1), torch.nn.GELU(), torch.nn.Conv1d(d["F"], d["F"], 1))

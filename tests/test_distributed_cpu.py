@@ -1,50 +1,21 @@
 """world_size-2 `gloo` tests (CPU) of the data-parallel host logic: gradient bucket all-reduce, parameter
 broadcast, the cross-rank softmax-statistic merge used for global-batch negatives, and the algebra that
 makes per-rank loss shares / gradients sum to the single-process result (checked with the oracle)."""
-import os
-
-import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from oracle import brain_oracle as O
-
-
-def _worker(rank, world, port, fn, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
-    # (the package's own entry point: the RCCL stream-priority option of backend "nccl" does not apply to gloo, the call must
-    # pass everything else through)
-    from speech_decoding_amd.distributed import init_process_group
-    init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        ret[rank] = fn(rank, world)
-    finally:
-        dist.destroy_process_group()
-
-
-def _free_port():
-    """A port the OS hands out (a pid-derived one can collide with another test process)."""
-    import socket
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        return sk.getsockname()[1]
+from tests.ranks import run_ranks
 
 
 def run2(fn):
-    ctx = mp.get_context("spawn")
-    ret = ctx.Manager().dict()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, fn, ret)) for r in range(2)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(120)
-        assert p.exitcode == 0
-    return dict(ret)
+    # (the package's own entry point: the RCCL stream-priority option of backend "nccl" does not apply to gloo, the call must
+    # pass everything else through)
+    from speech_decoding_amd.distributed import init_process_group
+    return run_ranks(fn, 2, init=init_process_group, device="cpu", timeout=120)
 
 
-def _grads(rank, world):
+def _grads(rank, world, dev):
     from speech_decoding_amd.distributed import allreduce_gradients, broadcast_parameters
     torch.manual_seed(rank)
     lin = torch.nn.Linear(5, 3)
@@ -70,7 +41,7 @@ def test_gradient_allreduce_and_broadcast():
         assert torch.all(out[r][4] == 1.0)                           # None grad on one rank counts as zero
 
 
-def _clip_shares(rank, world):
+def _clip_shares(rank, world, dev):
     """Global-negative CLIP loss from per-rank column blocks == single-process loss (oracle logits)."""
     from speech_decoding_amd.distributed import merge_row_softmax_stats, shard_range
     g = torch.Generator().manual_seed(0)
@@ -103,7 +74,7 @@ def test_global_negative_loss_shares_sum_to_full_loss():
         assert lse_ok and abs(tot - full) < 1e-5
 
 
-def _syncbn(rank, world):
+def _syncbn(rank, world, dev):
     """Summing per-rank (sum, sumsq) partials reproduces the global-batch BatchNorm of the oracle."""
     g = torch.Generator().manual_seed(1)
     x = torch.randn(8, 6, 10, generator=g)
@@ -123,7 +94,7 @@ def test_synchronised_batchnorm_statistics():
     assert out[0] and out[1]
 
 
-def _seed_and_sampler(rank, world):
+def _seed_and_sampler(rank, world, dev):
     """SpatialDropout's centre under data parallelism: NumPy's global generator in lockstep on all ranks
     (distributed.seed_numpy_all_ranks), and the sampler shards of data.ShardedRandomSampler."""
     import numpy as np

@@ -2,24 +2,17 @@
 of a batch with synchronised BatchNorm statistics, all-gathered speech embeddings (global negatives) and a
 SUM gradient all-reduce; loss, embeddings and gradients must equal the single-process run on the whole
 batch.  (The 8-GPU RCCL run is the driver's; this covers the algebra and the collective call sequence.)"""
-import os
-
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 pytestmark = pytest.mark.gpu
 
 from oracle import brain_oracle as O      # noqa: E402
+from tests import builders as TB          # noqa: E402
+from tests.ranks import run_ranks          # noqa: E402
 
-
-class Args(dict):
-    __getattr__ = dict.__getitem__
-
-
-TOY = dict(C=20, S=3, D1=32, D2=48, F=64, K=4, T=70, B=12)
+TOY = dict(TB.TOY, B=12)
 # BASELINE configs[2] / configs[3] per-rank shapes (Gwilliams 208 ch x 27 subjects, Brennan 60 ch x 1 subject) at the
 # real layer widths, 12 segments per rank (the Classifier needs 10 candidates): SyncBN + global negatives + per-group gradient all-reduce at full dims
 REAL_208 = dict(C=208, S=27, D1=270, D2=320, F=1024, K=32, T=360, B=12)
@@ -27,75 +20,44 @@ REAL_60 = dict(C=60, S=1, D1=270, D2=320, F=1024, K=32, T=360, B=12)
 
 
 def build(dtype, P, d, dev="cuda:0"):
-    from speech_decoding.models import BrainEncoder
-    from speech_decoding.utils.loss import CLIPLoss
     loc = O.synthetic_positions(d["C"], seed=1)
-    args = Args(num_subjects=d["S"], D1=d["D1"], D2=d["D2"], F=d["F"], K=d["K"], dataset="Gwilliams2022", d_drop=0.1,
-                root_dir=".", preprocs={"last4layers": False}, reduction="mean", init_temperature=3.0,
-                sensor_positions=loc.numpy(), compute_dtype=dtype)
-    enc = BrainEncoder(args)
-    enc.load_state_dict(P)
-    return enc.to(dev).train(), CLIPLoss(args).to(dev)
+    return TB.build_encoder(P, TB.encoder_args(d, loc, dtype), dev), TB.clip_loss(3.0, dev)
 
 
-def grads_of(enc, lossf):
-    out = {n: (torch.view_as_real(p.grad) if p.grad.is_complex() else p.grad).detach().cpu().clone()
-           for n, p in enc.named_parameters()}
-    out["temp"] = lossf.temp.grad.detach().cpu().clone()
-    return out
-
-
-def _worker(rank, world, port, ret, d, backend="gloo"):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      HSA_ENABLE_IPC_MODE_LEGACY="0")
-    import datetime
-    # gloo: every rank on cuda:0 (one-GPU box); nccl (= RCCL): one device per rank
-    DEV = f"cuda:{rank}" if backend == "nccl" else "cuda:0"
-    torch.cuda.set_device(DEV)
-    # short collective timeout: if one rank fails, the others error out instead of blocking the whole run
-    if backend == "nccl":
-        dist.init_process_group("nccl", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120),
-                                device_id=torch.device(DEV))
-    else:
-        dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=90))
-    try:
-        from speech_decoding_amd.distributed import allreduce_gradients, shard_range
-        loc = O.synthetic_positions(d["C"], seed=1)
-        P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=2, loc=loc)
-        Bg = d["B"] * world
-        X, Y, subj = O.synthetic_batch(Bg, d["C"], d["T"], d["F"], d["S"], seed=3)
-        lo, hi = shard_range(Bg, rank, world)
-        enc, lossf = build("fp32", P, d, DEV)
-        enc.set_drop_centre(4)
-        Yl = Y[lo:hi].to(DEV)
-        lossf.prefetch(Yl, torch.float32)                          # async all-gather of Y overlapping the encoder
-        Z = enc(X[lo:hi].to(DEV), subj[lo:hi])
-        loss = lossf(Yl, Z)
-        loss.backward()
-        assert enc.grads_are_reduced                                  # encoder grads: all-reduced inside backward
-        allreduce_gradients(list(lossf.parameters()))
-        from speech_decoding.models import Classifier
-        top = Classifier(None)(Z, Yl)                              # served from the loss's global ranks
-        top_again = Classifier(None)(Z, Yl.clone())                # uncached path: gathers and ranks globally
-        assert top == top_again
-        res = dict(loss=float(loss.detach()), Z=Z.detach().float().cpu(), grads=grads_of(enc, lossf), top=top,
-                   rm=enc.conv_blocks.conv2.batchnorm1.running_mean.cpu().clone())
-        if rank == 0:      # single-process reference on the whole batch, collectives switched off
-            enc1, lossf1 = build("fp32", P, d, DEV)
-            enc1.sync_batchnorm = False
-            lossf1.global_negatives = False
-            enc1.set_drop_centre(4)
-            Z1 = enc1(X.to(DEV), subj)
-            l1 = lossf1(Y.to(DEV), Z1)
-            l1.backward()
-            local_clf = Classifier(None)
-            local_clf.global_candidates = False
-            res["ref"] = dict(loss=float(l1.detach()), Z=Z1.detach().float().cpu(), grads=grads_of(enc1, lossf1),
-                              rm=enc1.conv_blocks.conv2.batchnorm1.running_mean.cpu().clone(),
-                              top=local_clf(Z1, Y.to(DEV)))
-        ret[rank] = res
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world, DEV, d):
+    from speech_decoding_amd.distributed import allreduce_gradients, shard_range
+    Bg = d["B"] * world
+    _, P, X, Y, subj = TB.toy_problem(d, Bg)
+    lo, hi = shard_range(Bg, rank, world)
+    enc, lossf = build("fp32", P, d, DEV)
+    enc.set_drop_centre(4)
+    Yl = Y[lo:hi].to(DEV)
+    lossf.prefetch(Yl, torch.float32)                          # async all-gather of Y overlapping the encoder
+    Z = enc(X[lo:hi].to(DEV), subj[lo:hi])
+    loss = lossf(Yl, Z)
+    loss.backward()
+    assert enc.grads_are_reduced                                  # encoder grads: all-reduced inside backward
+    allreduce_gradients(list(lossf.parameters()))
+    from speech_decoding.models import Classifier
+    top = Classifier(None)(Z, Yl)                              # served from the loss's global ranks
+    top_again = Classifier(None)(Z, Yl.clone())                # uncached path: gathers and ranks globally
+    assert top == top_again
+    res = dict(loss=float(loss.detach()), Z=Z.detach().float().cpu(), grads=TB.grads_of(enc, ("temp", lossf.temp)), top=top,
+               rm=enc.conv_blocks.conv2.batchnorm1.running_mean.cpu().clone())
+    if rank == 0:      # single-process reference on the whole batch, collectives switched off
+        enc1, lossf1 = build("fp32", P, d, DEV)
+        enc1.sync_batchnorm = False
+        lossf1.global_negatives = False
+        enc1.set_drop_centre(4)
+        Z1 = enc1(X.to(DEV), subj)
+        l1 = lossf1(Y.to(DEV), Z1)
+        l1.backward()
+        local_clf = Classifier(None)
+        local_clf.global_candidates = False
+        res["ref"] = dict(loss=float(l1.detach()), Z=Z1.detach().float().cpu(), grads=TB.grads_of(enc1, ("temp", lossf1.temp)),
+                          rm=enc1.conv_blocks.conv2.batchnorm1.running_mean.cpu().clone(),
+                          top=local_clf(Z1, Y.to(DEV)))
+    return res
 
 
 @pytest.mark.parametrize("world,dims", [(2, TOY), (4, TOY), (2, REAL_208), (2, REAL_60)],
@@ -115,23 +77,7 @@ def test_two_ranks_on_rccl_when_two_gpus_are_visible():
 
 
 def _run_ranks(world, dims, backend):
-    ctx = mp.get_context("spawn")
-    ret = ctx.Manager().dict()
-    import socket
-    with socket.socket() as sock:          # a port the kernel says is free right now (not one derived from the pid)
-        sock.bind(("127.0.0.1", 0))
-        port = sock.getsockname()[1]
-    procs = [ctx.Process(target=_worker, args=(r, world, port, ret, dims, backend)) for r in range(world)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(300)
-    for p in procs:
-        if p.is_alive():
-            p.terminate()
-            p.join(10)
-    assert [p.exitcode for p in procs] == [0] * world
-    out = dict(ret)
+    out = run_ranks(_worker, world, dims, backend=backend)
     ref = out[0]["ref"]
     B = dims["B"]
     for r in range(world):
@@ -141,7 +87,7 @@ def _run_ranks(world, dims, backend):
         for k, g in out[r]["grads"].items():
             gr = ref["grads"][k]
             scale = float(gr.abs().max()) + 1e-12
-            if k.startswith("conv_blocks.") and k.endswith((".conv0.bias", ".conv1.bias")):
+            if TB.null_bias_grad(k):
                 continue
             assert float((g - gr).abs().max()) <= 2e-3 * scale + 1e-7, (r, k)
     # retrieval accuracy over the global batch = mean of the per-rank accuracies

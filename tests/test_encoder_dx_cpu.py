@@ -3,12 +3,12 @@ on X, tests/golden/encoder_dx.npz) agrees with the oracle's float64 autograd, an
 launching anything."""
 import ctypes
 
-import numpy as np
 import pytest
 import torch
 
 from oracle import brain_oracle as O
 from tests import golden_io as G
+from tests.builders import TOY, encoder_args
 
 
 def fixture_case(npz, i):
@@ -87,12 +87,8 @@ def test_x_of_another_dtype_requiring_grad_is_refused_before_any_launch():
     from speech_decoding_amd import lib
     from speech_decoding_amd.models import BrainEncoder
 
-    class Args(dict):
-        __getattr__ = dict.__getitem__
-    d = dict(C=20, S=3, D1=32, D2=48, F=64, K=4)
-    loc = O.synthetic_positions(d["C"], seed=1)
-    enc = BrainEncoder(Args(num_subjects=d["S"], D1=d["D1"], D2=d["D2"], F=d["F"], K=d["K"], dataset="Gwilliams2022", d_drop=0.1,
-                            root_dir=".", preprocs={"last4layers": False}, sensor_positions=loc.numpy()))
+    d = TOY
+    enc = BrainEncoder(encoder_args(d, O.synthetic_positions(d["C"], seed=1)))
     X = torch.zeros(2, d["C"], 8, dtype=torch.float64, requires_grad=True)
     with pytest.raises(lib.SdaError, match="float64"):
         enc(X, torch.zeros(2, dtype=torch.int64))

@@ -8,6 +8,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import brain_oracle as O                                      # noqa: E402
+from tests import builders as TB                                           # noqa: E402
 from tests import golden_io as G                                           # noqa: E402
 from tests.parity import operands_as_device_sees_them, rel_l2, round_to   # noqa: E402
 
@@ -15,32 +16,20 @@ DEV = "cuda:0"
 DT = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
 GRAD_REL_L2 = {"fp32": 1e-4, "bf16": 6e-2, "fp16": 8e-3}        # every gradient 6e-2 / 8e-3 in the 16-bit modes
 OUT_REL_L2 = {"fp32": 0.0, "bf16": 6e-3, "fp16": 1e-3}          # + the rounding of dX to X's own dtype
-TOY = dict(C=20, S=3, D1=32, D2=48, F=64, K=4, T=70, B=6)
+TOY = dict(TB.TOY, B=6)
 WIDE = {"208": dict(C=208, S=27, D1=270, D2=320, F=1024, K=32, T=96, B=4), "60": dict(C=60, S=1, D1=270, D2=320, F=1024, K=32, T=96, B=4)}
 
 
-class Args(dict):
-    __getattr__ = dict.__getitem__
-
-
 def build_encoder(P, d, loc, dtype="fp32", training=True):
-    from speech_decoding.models import BrainEncoder
-    args = Args(num_subjects=d["S"], D1=d["D1"], D2=d["D2"], F=d["F"], K=d["K"], dataset="Gwilliams2022", d_drop=0.1,
-                root_dir=".", preprocs={"last4layers": False}, sensor_positions=loc.numpy(), compute_dtype=dtype)
-    enc = BrainEncoder(args)
-    enc.load_state_dict(P)
-    return enc.to(DEV).train(training)
+    return TB.build_encoder(P, TB.encoder_args(d, loc, dtype), DEV, training=training)
 
 
 def clip(temp=2.0):
-    from speech_decoding.utils.loss import CLIPLoss
-    return CLIPLoss(Args(reduction="mean", init_temperature=temp)).to(DEV)
+    return TB.clip_loss(temp, DEV)
 
 
 def setup(d, seed=2, dtype="fp32", training=True):
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=seed, loc=loc)
-    X, Y, subj = O.synthetic_batch(d["B"], d["C"], d["T"], d["F"], d["S"], seed=3)
+    loc, P, X, Y, subj = TB.toy_problem(d, d["B"], param_seed=seed)
     return loc, P, X, Y, subj, build_encoder(P, d, loc, dtype, training)
 
 
@@ -129,9 +118,7 @@ def test_config2_batch_256_bf16():
     """Config ② (C=208, S=27, D1=270, D2=320, F=1024, T=360) at B = 256 in bf16, eval mode so that samples are independent:
     a loss that is linear in Z gives every sample its own gradient, and the oracle checks four of them."""
     d = dict(C=208, S=27, D1=270, D2=320, F=1024, K=32, T=360, B=256)
-    loc = O.synthetic_positions(d["C"], seed=0)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=0, loc=loc)
-    X, _, subj = O.synthetic_batch(d["B"], d["C"], d["T"], d["F"], d["S"], seed=1234)
+    loc, P, X, _, subj = TB.toy_problem(d, d["B"], loc_seed=0, param_seed=0, batch_seed=1234)
     R = torch.randn(d["B"], d["F"], d["T"], generator=torch.Generator().manual_seed(8))
     enc = build_encoder(P, d, loc, "bf16", training=False)
     Xl = X.to(DEV).to(torch.bfloat16).requires_grad_(True)
@@ -249,9 +236,7 @@ def test_no_grad_forward_in_between_leaves_dx_unchanged(C):
 # ------------------------------------------------------------------------------------------------------------------------------
 def test_joint_front_end_adam_steps_match_cpu_float64():
     d = TOY
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=2, loc=loc)
-    X, Y, subj = O.synthetic_batch(d["B"], d["C"], d["T"], d["F"], d["S"], seed=3)
+    loc, P, X, Y, subj = TB.toy_problem(d, d["B"])
     torch.manual_seed(0)
     front = torch.nn.Conv1d(d["C"], d["C"], 1)
     front64 = torch.nn.Conv1d(d["C"], d["C"], 1)

@@ -16,7 +16,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import brain_oracle as O                                  # noqa: E402
 from tests.parity import operands_as_device_sees_them, rel_l2, round_to   # noqa: E402
-from tests.test_e2e_gpu import DTYPES16, build, check_lowprec_step, grads_by_state_key, make_args, null_grad   # noqa: E402
+from tests.builders import grads_by_state_key, null_bias_grad                        # noqa: E402
+from tests.test_e2e_gpu import DTYPES16, build, check_lowprec_step, make_args       # noqa: E402
 
 DEV = "cuda:0"
 C, S, D1, D2, F, K, T, B = 208, 27, 270, 320, 1024, 32, 360, 256
@@ -57,7 +58,7 @@ def test_config2_full_batch_fp32_train_step_vs_live_oracle():
             continue
         gf = (torch.view_as_real(g) if g.is_complex() else g).float().cpu().reshape(-1)
         rf = (torch.view_as_real(ref) if ref.is_complex() else ref).reshape(-1)
-        if null_grad(k):                                     # mathematically zero (feeds a training-mode BatchNorm)
+        if null_bias_grad(k):                                     # mathematically zero (feeds a training-mode BatchNorm)
             assert float(gf.abs().max()) < 1e-4, k
             continue
         assert float((gf - rf).abs().max()) <= 2e-3 * float(rf.abs().max()) + 1e-9, (k, float((gf - rf).abs().max()), float(rf.abs().max()))

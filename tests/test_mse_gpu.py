@@ -11,6 +11,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import brain_oracle as O      # noqa: E402
+from tests import builders as TB          # noqa: E402
 from tests import golden_io as G           # noqa: E402
 from tests.parity import operands_as_device_sees_them, rel_l2, round_to   # noqa: E402
 
@@ -220,20 +221,10 @@ def test_forward_and_backward_never_sync_the_host():
 # ------------------------------------------------------------------------------------------------------------------------------
 # 6-7. one training step through the encoder against the CPU oracle
 # ------------------------------------------------------------------------------------------------------------------------------
-class Args(dict):
-    __getattr__ = dict.__getitem__
-
-
 def make_encoder(C, S, D1, D2, F, K, P, loc, dtype, last4):
-    from speech_decoding.models import BrainEncoder
-    args = Args(num_subjects=S, D1=D1, D2=D2, F=F, K=K, dataset="Gwilliams2022", d_drop=0.1, root_dir="/nonexistent",
-                preprocs={"last4layers": last4}, reduction="mean", init_temperature=5.1, sensor_positions=loc.numpy(),
-                compute_dtype=dtype)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        enc = BrainEncoder(args)
-        enc.load_state_dict(P, strict=True)
-    return enc.to(DEV)
+        return TB.build_encoder(P, TB.encoder_args(dict(S=S, D1=D1, D2=D2, F=F, K=K), loc, dtype, last4), DEV)
 
 
 def oracle_mse_step(P, X, Y, subj, loc, centre, taps=None):
@@ -248,27 +239,10 @@ def oracle_mse_step(P, X, Y, subj, loc, centre, taps=None):
     return loss.detach(), Z.detach(), {k: v.grad for k, v in leaves.items()}
 
 
-def grads_by_state_key(enc):
-    out = {}
-    for n, p in enc.named_parameters():
-        if n == "subject_block.subject_layer.weight":
-            for s in range(p.shape[0]):
-                out[f"subject_block.subject_layer.{s}.weight"] = None if p.grad is None else p.grad[s]
-        else:
-            out[n] = p.grad
-    return out
-
-
-def null_grad(key):      # exactly zero in exact arithmetic (a bias in front of a training-mode BatchNorm)
-    return key.startswith("conv_blocks.") and key.endswith((".conv0.bias", ".conv1.bias"))
-
-
 def test_train_step_fp32_matches_oracle():
     C, S, D1, D2, F, K, T, B = 20, 3, 32, 48, 64, 4, 90, 6
-    loc = O.synthetic_positions(C, seed=1)
-    P = O.seeded_params(C, S, D1, D2, F, K, seed=2, loc=loc)
-    X, Y, subj = O.synthetic_batch(B, C, T, F, S, seed=3)
-    enc = make_encoder(C, S, D1, D2, F, K, P, loc, "fp32", False).train()
+    loc, P, X, Y, subj = TB.toy_problem(dict(C=C, S=S, D1=D1, D2=D2, F=F, K=K, T=T), B)
+    enc = make_encoder(C, S, D1, D2, F, K, P, loc, "fp32", False)
     enc.set_drop_centre(5)
     Z = enc(X.to(DEV), subj)
     loss = mse()(Y.to(DEV), Z)
@@ -277,9 +251,9 @@ def test_train_step_fp32_matches_oracle():
     assert float((Z.detach().cpu() - Zo).abs().max()) <= 1e-4 * float(Zo.abs().max())
     assert abs(float(loss) - float(lo)) <= 1e-4 * float(lo)
     checked = 0
-    for k, g in grads_by_state_key(enc).items():
+    for k, g in TB.grads_by_state_key(enc).items():
         ref = go[k]
-        if null_grad(k):
+        if TB.null_bias_grad(k):
             assert float(g.abs().max()) < 1e-4 * max(1.0, float(go[k.replace(".bias", ".weight")].abs().max())), k
             continue
         gf = (torch.view_as_real(g) if g.is_complex() else g).float().cpu()
@@ -301,10 +275,8 @@ CANCEL_REL = {"bf16": 6e-2, "fp16": 8e-3}
 def test_train_step_16bit_at_real_widths_against_oracle_on_rounded_operands(dtype):
     from speech_decoding_amd.amp import LossScaler
     C, S, D1, D2, F, K, T, B = 208, 27, 270, 320, 1024, 32, 360, 12
-    loc = O.synthetic_positions(C, seed=0)
-    P = O.seeded_params(C, S, D1, D2, F, K, seed=0, loc=loc)
-    X, Y, subj = O.synthetic_batch(B, C, T, F, S, seed=1234)
-    enc = make_encoder(C, S, D1, D2, 512, K, P, loc, dtype, True).train()
+    loc, P, X, Y, subj = TB.toy_problem(dict(C=C, S=S, D1=D1, D2=D2, F=F, K=K, T=T), B, 0, 0, 1234)
+    enc = make_encoder(C, S, D1, D2, 512, K, P, loc, dtype, True)
     scaler = LossScaler.for_dtype(DT[dtype])           # fp16: the static scale train.py starts from, halved on overflow
     for _ in range(12):
         enc.zero_grad(set_to_none=True)
@@ -322,12 +294,12 @@ def test_train_step_16bit_at_real_widths_against_oracle_on_rounded_operands(dtyp
     lo, Zo, go = oracle_mse_step(operands_as_device_sees_them(P, dtype), round_to(X, dtype), Y, subj, loc, 9, taps=taps)
     report = {"Z": (rel_l2(Z.detach().float(), Zo), Z_REL[dtype]),
               "loss": (abs(float(loss.detach()) - float(lo)) / float(lo), LOSS_REL[dtype])}
-    for k, g in grads_by_state_key(enc).items():
+    for k, g in TB.grads_by_state_key(enc).items():
         ref = go[k]
         if ref is None:                                  # a subject absent from the batch
             assert g is None or float(g.abs().max()) == 0.0, k
             continue
-        if null_grad(k):
+        if TB.null_bias_grad(k):
             assert float(g.abs().max()) < 5e-2 * max(1.0, float(go[k.replace(".bias", ".weight")].abs().max())), k
             continue
         if k == CANCEL_SUM:

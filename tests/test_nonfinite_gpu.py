@@ -25,6 +25,7 @@ Kernel -> test:
 import pytest
 import torch
 
+from tests import builders as TB
 from tests import elementwise_cases as E
 from tests import exact_cases as X
 from tests import nonfinite_cases as N
@@ -904,28 +905,16 @@ def test_conv3_data_gradient_with_bn_statistics_epilogue(ops, store_dg, dtype):
 # ---------------------------------------------------------------------------------------------------------------
 # whole-model containment: one bad sample must not reach another sample's result
 # ---------------------------------------------------------------------------------------------------------------
-TOY = dict(C=20, S=3, D1=32, D2=48, F=64, K=4, T=70, B=6)          # the toy shape of tests/test_dp_gpu.py, six samples
-
-
-class Args(dict):
-    __getattr__ = dict.__getitem__
+TOY = dict(TB.TOY, B=6)          # the toy shape of tests/test_dp_gpu.py, six samples
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 def test_eval_mode_encoder_keeps_an_inf_inside_its_sample(dtype):
     """eval-mode BrainEncoder (BatchNorm on its running statistics: nothing couples the samples), forward and dX: sample 2's input
     holds one inf; every other sample's Z and dX carry the bits of the clean run, and sample 2's own are non-finite"""
-    from oracle import brain_oracle as O
-    from speech_decoding.models import BrainEncoder
     d = TOY
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=2, loc=loc)
-    X, _, subj = O.synthetic_batch(d["B"], d["C"], d["T"], d["F"], d["S"], seed=3)
-    args = Args(num_subjects=d["S"], D1=d["D1"], D2=d["D2"], F=d["F"], K=d["K"], dataset="Gwilliams2022", d_drop=0.1, root_dir=".",
-                preprocs={"last4layers": False}, sensor_positions=loc.numpy(), compute_dtype=dtype)
-    enc = BrainEncoder(args)
-    enc.load_state_dict(P)
-    enc = enc.to(DEV).eval()
+    loc, P, X, _, subj = TB.toy_problem(d, d["B"])
+    enc = TB.build_encoder(P, TB.encoder_args(d, loc, dtype), DEV, training=False)
     dZ = torch.randn(d["B"], d["F"], d["T"], generator=torch.Generator().manual_seed(11))
     bad = 2
 

@@ -10,23 +10,19 @@ the smallest power of two s with s g >= 4 x 65504 — two binades past fp16's ra
 (GRAD_REL 8e-3 in tests/test_e2e_gpu.py), so the first stored activation gradient overflows whatever the rounding does.
 Backward is linear in the scale: no other number is needed.  The default scale (1024) at these shapes is the one
 tests/test_e2e_gpu.py asserts healthy: it is the "no false alarm" scale here."""
-import datetime
 import math
-import os
-import socket
 
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 import torch.nn.functional as TF
 
 pytestmark = pytest.mark.gpu
 
-from oracle import brain_oracle as O      # noqa: E402
+from oracle import brain_oracle as O                                                 # noqa: E402
+from tests.builders import TOY, build_encoder, clip_loss, encoder_args, toy_problem   # noqa: E402
+from tests.ranks import run_ranks                                                     # noqa: E402
 
 DEV = "cuda:0"
-TOY = dict(C=20, S=3, D1=32, D2=48, F=64, K=4, T=70)
 B = 12                        # one process; two ranks take 6 each
 TEMP = 3.0
 CENTRE = 4
@@ -35,16 +31,8 @@ MARGIN = 4.0
 LOSSES = ["clip", "mse"]
 
 
-class Args(dict):
-    __getattr__ = dict.__getitem__
-
-
 def problem():
-    d = TOY
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=2, loc=loc)
-    X, Y, subj = O.synthetic_batch(B, d["C"], d["T"], d["F"], d["S"], seed=3)
-    return loc, P, X, Y, subj
+    return toy_problem(TOY, B)
 
 
 def double(P):
@@ -76,17 +64,10 @@ def overflow_scale(dZ):
 
 
 def build(kind, P, loc):
-    from speech_decoding.models import BrainEncoder
-    from speech_decoding.utils.loss import CLIPLoss, MSELoss
-    d = TOY
-    args = Args(num_subjects=d["S"], D1=d["D1"], D2=d["D2"], F=d["F"], K=d["K"], dataset="Gwilliams2022", d_drop=0.1, root_dir=".",
-                preprocs={"last4layers": False}, reduction="mean", init_temperature=TEMP, sensor_positions=loc.numpy(),
-                compute_dtype="fp16")
-    enc = BrainEncoder(args)
-    enc.load_state_dict(P)
-    enc = enc.to(DEV).train()
+    from speech_decoding.utils.loss import MSELoss
+    enc = build_encoder(P, encoder_args(TOY, loc, "fp16"), DEV)
     enc.set_drop_centre(CENTRE)
-    lossf = (CLIPLoss(args) if kind == "clip" else MSELoss()).to(DEV)
+    lossf = clip_loss(TEMP, DEV) if kind == "clip" else MSELoss().to(DEV)
     lossf.train()
     return enc, lossf
 
@@ -253,50 +234,28 @@ def test_dp_problem_overflows_on_rank_0_only(kind):
 DP_CASES = [(kind, overlap) for kind in LOSSES for overlap in (True, False)]       # overlap: the engine's own reduction inside backward
 
 
-def _worker(rank, world, port, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      HSA_ENABLE_IPC_MODE_LEGACY="0")
-    torch.cuda.set_device(DEV)
-    # short collective timeout: if one rank fails, the other errors out instead of blocking the run
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=90))
-    try:
-        from speech_decoding_amd.distributed import shard_range
-        problems = {kind: dp_problem(kind) for kind in LOSSES}
-        lo, hi = shard_range(B, rank, world)
-        for kind, overlap in DP_CASES:
-            loc, P, X, Y, subj, scale, _ = problems[kind]
-            run = Run(kind, P, loc, world=world, scale=scale)
-            run.enc.engine.overlap_grad_allreduce = overlap
-            assert run.enc.grads_are_reduced == overlap
-            before = run.state()
-            loss = run.train_step(X[lo:hi], Y[lo:hi], subj[lo:hi])
-            after = run.state()
-            ret[(rank, kind, overlap)] = dict(ok=run.oks, scale=run.scaler.scale_value, skipped=run.scaler.skipped_steps, loss=loss, start_scale=scale,
-                                              moved=same_bits(after, before), params={k: v for k, v in after.items() if k.startswith("param")})
-    finally:
-        dist.destroy_process_group()
+def _worker(rank, world, dev):
+    from speech_decoding_amd.distributed import shard_range
+    problems = {kind: dp_problem(kind) for kind in LOSSES}
+    lo, hi = shard_range(B, rank, world)
+    res = {}
+    for kind, overlap in DP_CASES:
+        loc, P, X, Y, subj, scale, _ = problems[kind]
+        run = Run(kind, P, loc, world=world, scale=scale)
+        run.enc.engine.overlap_grad_allreduce = overlap
+        assert run.enc.grads_are_reduced == overlap
+        before = run.state()
+        loss = run.train_step(X[lo:hi], Y[lo:hi], subj[lo:hi])
+        after = run.state()
+        res[(kind, overlap)] = dict(ok=run.oks, scale=run.scaler.scale_value, skipped=run.scaler.skipped_steps, loss=loss, start_scale=scale,
+                                     moved=same_bits(after, before), params={k: v for k, v in after.items() if k.startswith("param")})
+    return res
 
 
 @pytest.fixture(scope="module")
 def two_ranks():
     """one pair of processes (the worker and spawn pattern of tests/test_dp_gpu.py) steps every case of DP_CASES once"""
-    world = 2
-    ctx = mp.get_context("spawn")
-    ret = ctx.Manager().dict()
-    with socket.socket() as sock:
-        sock.bind(("127.0.0.1", 0))
-        port = sock.getsockname()[1]
-    procs = [ctx.Process(target=_worker, args=(r, world, port, ret)) for r in range(world)]
-    for p in procs:
-        p.start()
-    for p in procs:
-        p.join(300)
-    for p in procs:
-        if p.is_alive():
-            p.terminate()
-            p.join(10)
-    assert [p.exitcode for p in procs] == [0] * world
-    return dict(ret)
+    return run_ranks(_worker, 2)
 
 
 @pytest.mark.parametrize("kind,overlap", DP_CASES, ids=[f"{k}-{'engine-reduction' if o else 'allreduce_gradients'}" for k, o in DP_CASES])
@@ -304,7 +263,7 @@ def test_two_ranks_skip_the_same_step(two_ranks, kind, overlap):
     """train.py: "SUM of the still-scaled gradients: every rank then sees the same overflow, or none".  If one rank skipped and
     the other stepped, the replicas would diverge and nothing would report it.  Both gradient paths: the engine's own reduction
     inside backward (grads_are_reduced) and allreduce_gradients after it."""
-    out = [two_ranks[(r, kind, overlap)] for r in range(2)]
+    out = [two_ranks[r][(kind, overlap)] for r in range(2)]
     for r in range(2):
         assert out[r]["ok"] == [False], (r, out[r]["ok"])
         assert out[r]["skipped"] == 1 and out[r]["scale"] == out[r]["start_scale"] / 2, (r, out[r]["scale"])

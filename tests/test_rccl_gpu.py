@@ -14,23 +14,23 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+from tests.ranks import single_rank_env      # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 WORKER = textwrap.dedent("""
     import os, sys, datetime
     import numpy as np, torch, torch.distributed as dist
     sys.path.insert(0, %r)
-    from oracle import brain_oracle as O
-    from tests.test_dp_gpu import TOY, REAL_208, build, grads_of
+    from tests.builders import clip_loss, grads_of, null_bias_grad, toy_problem
+    from tests.test_dp_gpu import TOY, REAL_208, build
     from speech_decoding_amd.distributed import allreduce_gradients, side_group, active_group
     DEV = "cuda:0"
     torch.cuda.set_device(DEV)
     dist.init_process_group("nccl", rank=0, world_size=1, timeout=datetime.timedelta(seconds=120), device_id=torch.device(DEV))
     assert active_group() is not None
     for d in (TOY, REAL_208):
-        loc = O.synthetic_positions(d["C"], seed=1)
-        P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], d["F"], d["K"], seed=2, loc=loc)
-        X, Y, subj = O.synthetic_batch(d["B"], d["C"], d["T"], d["F"], d["S"], seed=3)
+        _, P, X, Y, subj = toy_problem(d, d["B"])
         outs = []
         for dp in (True, False):
             enc, lossf = build("fp32", P, d, DEV)
@@ -49,29 +49,27 @@ WORKER = textwrap.dedent("""
                     assert enc.grads_are_reduced and enc.engine.group is not None
                     allreduce_gradients(list(lossf.parameters()))
             torch.cuda.synchronize()
-            outs.append((float(loss.detach()), Z.detach().float().cpu(), grads_of(enc, lossf)))
+            outs.append((float(loss.detach()), Z.detach().float().cpu(), grads_of(enc, ("temp", lossf.temp))))
         (l1, Z1, g1), (l0, Z0, g0) = outs
         # the DP path sums the BatchNorm partials in a different (fp32 slab) order: equal to fp32 rounding, not bitwise
         assert abs(l1 - l0) < 2e-5 * max(1.0, abs(l0)), (l1, l0)
         assert float((Z1 - Z0).abs().max()) <= 1e-4 * float(Z0.abs().max()), float((Z1 - Z0).abs().max()) / float(Z0.abs().max())
         for k in g0:
-            if k.startswith("conv_blocks.") and k.endswith((".conv0.bias", ".conv1.bias")):
+            if null_bias_grad(k):
                 continue                                        # null gradients: rounding noise on both sides
             assert float((g1[k] - g0[k]).abs().max()) <= 2e-3 * float(g0[k].abs().max()) + 1e-7, k
         assert side_group("grads", active_group()) is not active_group()        # communicators of their own exist
     # ---- bench.py --emulate-world: one rank behaving as rank 0 of W (distributed.emulate_world): the loss sees W * B speech
     # rows — its own through the real all-gather, (W - 1) * B resident stand-ins — and must equal the engine's block form on
     # exactly those rows (the tiled embedding gradient included: 288 speech rows x 96 columns, bf16)
-    from speech_decoding_amd import CLIPLoss, clip, lib as L, ops
+    from speech_decoding_amd import clip, lib as L, ops
     from speech_decoding_amd import loss as sda_loss
     from speech_decoding_amd.distributed import emulate_world
-    class A(dict):
-        __getattr__ = dict.__getitem__
     B, W, F, T = 96, 3, 64, 44
     g = torch.Generator().manual_seed(31)
     Yl, Zl = torch.randn(B, F, T, generator=g).to(DEV), torch.randn(B, F, T, generator=g).to(DEV)
     emulate_world(W)
-    lossf = CLIPLoss(A(reduction="mean", init_temperature=5.1)).to(DEV)
+    lossf = clip_loss(5.1, DEV)
     Zt = sda_loss.as_rows(Zl, B, F, T, torch.bfloat16, "Z")
     Zv = ops.rows_view(Zt, B, F, T).requires_grad_(True)
     lossf.prefetch(Yl, torch.bfloat16)
@@ -98,11 +96,7 @@ WORKER = textwrap.dedent("""
 
 
 def test_data_parallel_step_through_rccl_at_world_size_one():
-    with __import__("socket").socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    env = dict(os.environ, SDA_DP_SINGLE_RANK="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1",
-               HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONPATH=ROOT)
+    env = single_rank_env()
     out = subprocess.run([sys.executable, "-c", WORKER % ROOT], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     log_dir = os.path.join(ROOT, "gpurun_out")
     if os.path.isdir(log_dir):

@@ -16,6 +16,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import brain_oracle as O      # noqa: E402,F401  (the yardstick's formula: topk_accuracy)
+from tests import builders as TB          # noqa: E402
 
 DEV = "cuda:0"
 DT = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
@@ -26,10 +27,6 @@ SMALL_SCRATCH = 64 << 10      # (96, 1000, 64, 90): 8 query rows per block, 256 
 MEASURED = {"fp32": 2.7e-7, "bf16": 1.3e-7, "fp16": 1.2e-7}
 
 _cases = {}
-
-
-class Args(dict):
-    __getattr__ = dict.__getitem__
 
 
 def case(shape: str, dtype: str):
@@ -242,7 +239,6 @@ def test_bank_built_in_uneven_adds_equals_bank_built_at_once(dtype):
 # ---------------------------------------------------------------------------------------------------------------------------
 def test_same_call_same_bits_also_around_a_clip_loss_step():
     from speech_decoding_amd import SpeechBank, retrieve
-    from speech_decoding.utils.loss import CLIPLoss
     queries, bank, labels, _ = case("a", "bf16")
     b = SpeechBank.from_tensor(bank.to(DEV))
     q = queries.to(DEV)
@@ -250,7 +246,7 @@ def test_same_call_same_bits_also_around_a_clip_loss_step():
     second = retrieve(q, b, labels=labels)
     assert all(torch.equal(x, y) for x, y in zip(first, second))
     g = torch.Generator().manual_seed(7)
-    lossf = CLIPLoss(Args(reduction="mean", init_temperature=5.1)).to(DEV)
+    lossf = TB.clip_loss(5.1, DEV)
     Y = torch.randn(12, 64, 90, generator=g).to(DEV)
     Z = torch.randn(12, 64, 90, generator=g).to(DEV).requires_grad_(True)
     loss1 = lossf(Y, Z)
@@ -279,7 +275,7 @@ def test_square_case_agrees_with_classifier_ranks(dtype):
     Zd, Yd = Z.to(DT[dtype]).to(DEV), Y.to(DEV)
     res = retrieve(Yd, SpeechBank.from_tensor(Zd, dtype=DT[dtype]), labels=diag)
     check_ranks(res.ranks, ref, diag)
-    clf = Classifier(Args())
+    clf = Classifier(TB.Config())
     check_ranks(clf.ranks(Zd, Yd), ref, diag)
     # Classifier.decode: brain queries against a speech bank = retrieve the other way round
     bank = SpeechBank.from_tensor(Yd, dtype=DT[dtype])
@@ -295,17 +291,10 @@ def test_square_case_agrees_with_classifier_ranks(dtype):
 def test_encoder_output_view_equals_its_contiguous_copy():
     from speech_decoding_amd import SpeechBank, retrieve
     from speech_decoding_amd import ops
-    from speech_decoding.models import BrainEncoder
-    C, S, D1, D2, F, K, T, B = 20, 3, 32, 48, 64, 4, 90, 12
-    loc = O.synthetic_positions(C, seed=1)
-    P = O.seeded_params(C, S, D1, D2, F, K, seed=2, loc=loc)
-    args = Args(num_subjects=S, D1=D1, D2=D2, F=F, K=K, dataset="Gwilliams2022", d_drop=0.1, root_dir=".",
-                preprocs={"last4layers": False}, reduction="mean", init_temperature=5.1,
-                sensor_positions=loc.numpy(), compute_dtype="fp32")
-    enc = BrainEncoder(args)
-    enc.load_state_dict(P)
-    enc = enc.to(DEV).eval()
-    X, Y, subj = O.synthetic_batch(B, C, T, F, S, seed=3)
+    d, B = dict(TB.TOY, T=90), 12
+    F, T = d["F"], d["T"]
+    _, P, X, Y, subj = TB.toy_problem(d, B)
+    enc = TB.build_encoder(P, d, DEV, training=False)
     with torch.no_grad():
         Z = enc(X.to(DEV), subj)
     assert not Z.is_contiguous() and ops.rows_base(Z, B, F, T, torch.float32) is not None       # the zero-copy rows view

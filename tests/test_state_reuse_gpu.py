@@ -14,7 +14,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import brain_oracle as O                       # noqa: E402
-from tests.test_e2e_gpu import make_args, null_grad       # noqa: E402
+from tests.builders import build_encoder, null_bias_grad     # noqa: E402
+from tests.test_e2e_gpu import make_args                      # noqa: E402
 
 DEV = "cuda:0"
 LR = 1e-4
@@ -48,14 +49,13 @@ class World:
     """BrainEncoder + CLIPLoss + Classifier + torch.optim.Adam (as train.py) in a given state."""
 
     def __init__(self, shape, dtype, composed, snap, cold):
-        from speech_decoding.models import BrainEncoder, Classifier
+        from speech_decoding.models import Classifier
         from speech_decoding.utils.loss import CLIPLoss
         self.loc = O.synthetic_positions(shape["C"], seed=0)
         args = make_args(shape["C"], shape["S"], D1, D2, F, K, True, self.loc, dtype)
-        self.enc = BrainEncoder(args).to(DEV)
+        self.enc = build_encoder(snap["enc"], args, DEV)
         self.lossf = CLIPLoss(args).to(DEV)
         self.clf = Classifier(args)
-        self.enc.load_state_dict(snap["enc"], strict=True)
         with torch.no_grad():
             self.lossf.temp.copy_(snap["temp"])
         eng = self.enc.engine
@@ -307,7 +307,7 @@ def test_warm_sequence_anchor_against_the_oracle():
                 if n == "temp" or n.startswith("subject_block.subject_layer."):
                     continue
                 g = cpu(rec["grad " + n])
-                if null_grad(n):
+                if null_bias_grad(n):
                     assert float(g.abs().max()) < 1e-4, n
                     continue
                 scale = max(float(p.abs().max()), 1e-8)
@@ -337,7 +337,7 @@ def test_warm_sequence_anchor_against_the_oracle():
         if kind == "step":
             _, _, _, go = O.train_step(Po, otemp.detach(), X, Y, subj, loc=loc, drop_centre=centre, stats=ostats)
             for k, leaf in leaves.items():
-                leaf.grad = torch.zeros_like(leaf) if null_grad(k) else go[k]     # exactly zero in exact arithmetic
+                leaf.grad = torch.zeros_like(leaf) if null_bias_grad(k) else go[k]     # exactly zero in exact arithmetic
             otemp.grad = go["temp"]
             oopt.step()
             nsteps += 1

@@ -14,18 +14,14 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+from tests.ranks import single_rank_env      # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_multi_stream_step_is_bitwise_equal_to_single_stream_step(dtype):
-    with __import__("socket").socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    env = dict(os.environ, SDA_DP_SINGLE_RANK="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1",
-               HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONPATH=ROOT)
-    for k in [k for k in env if k.startswith("SDA_ENGINE_")]:
-        del env[k]
+    env = single_rank_env()
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "stream_race_worker.py"), dtype], env=env,
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     log_dir = os.path.join(ROOT, "gpurun_out")

@@ -10,6 +10,7 @@ import torch
 
 from oracle import brain_oracle as O
 from tests import golden_io as G
+from tests.builders import encoder_args
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -23,14 +24,8 @@ def lib():
     return L
 
 
-class Args(dict):
-    __getattr__ = dict.__getitem__
-
-
 def make_args(C=12, S=3, D1=16, D2=24, K=4, dtype="fp32"):
-    loc = O.synthetic_positions(C, seed=7)
-    return Args(num_subjects=S, D1=D1, D2=D2, F=32, K=K, dataset="Gwilliams2022", d_drop=0.1, root_dir=".",
-                preprocs={"last4layers": False}, sensor_positions=loc.numpy(), compute_dtype=dtype)
+    return encoder_args(dict(S=S, D1=D1, D2=D2, F=32, K=K), O.synthetic_positions(C, seed=7), dtype)
 
 
 def test_cpu_tensors_are_refused(lib):

@@ -10,6 +10,7 @@ import torch.nn.functional as TF
 pytestmark = pytest.mark.gpu
 
 from oracle import brain_oracle as O                                      # noqa: E402
+from tests import builders as TB                                           # noqa: E402
 from tests import golden_io as G                                           # noqa: E402
 from tests.parity import operands_as_device_sees_them, rel_l2, round_to   # noqa: E402
 
@@ -18,21 +19,20 @@ DT = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
 OUT_REL = {"fp32": 1e-4, "bf16": 4e-2, "fp16": 5e-3}           # activations (storage rounding between kernels)
 GRAD_REL = {"fp32": 1e-4, "bf16": 6e-2, "fp16": 8e-3}          # every gradient
 X_OUT_REL = {"fp32": 0.0, "bf16": 6e-3, "fp16": 1e-3}          # + the rounding of dX to X's own dtype
-TOY = dict(C=20, S=3, D1=32, D2=48, K=4, T=70, B=6)
+TOY = dict(TB.TOY, B=6)
 SHAPES = {"toy": TOY, "toy_c64": dict(TOY, C=64),
           "208": dict(C=208, S=27, D1=270, D2=320, K=32, T=96, B=4), "60": dict(C=60, S=1, D1=270, D2=320, K=32, T=96, B=4)}
 KINDS = ["sa", "sb", "cb0", "cb1", "cb2", "cb3", "cb4"]
 PREFIX = {"sa": "subject_block.spatial_attention.", "sb": "subject_block.", **{f"cb{k}": f"conv_blocks.conv{k}." for k in range(5)}}
 
 
-class Args(dict):
-    __getattr__ = dict.__getitem__
+def make_args(d, loc, dtype="fp32", F=8):
+    return TB.encoder_args(d, loc, dtype, F=F, reduction="mean", init_temperature=5.1)
 
 
-def make_args(d, loc, dtype="fp32"):
-    return Args(num_subjects=d["S"], D1=d["D1"], D2=d["D2"], F=8, K=d["K"], dataset="Gwilliams2022", d_drop=0.1, root_dir=".",
-                preprocs={"last4layers": False}, reduction="mean", init_temperature=5.1, sensor_positions=np.asarray(loc),
-                compute_dtype=dtype)
+def positions_and_params(d, F=8):
+    loc = O.synthetic_positions(d["C"], seed=1)
+    return loc, O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], F, d["K"], seed=2, loc=loc)
 
 
 def sub_state(P, prefix):
@@ -146,14 +146,10 @@ def test_reference_activations_and_running_statistics(small):
 def test_reference_gradients_from_standalone_calls(small):
     """The reference's step 0 rebuilt from the submodules: SubjectBlock, the five ConvBlocks through enc.conv_blocks, the final
     projections with GELU (torch, here in the test only), this package's CLIPLoss."""
-    from speech_decoding.models import BrainEncoder
     from speech_decoding.utils.loss import CLIPLoss
     d, P, temp, X, subj = small_setup(small)
-    args = make_args(d, small["loc"])
-    args["F"] = int(small["dims"][4])
-    enc = BrainEncoder(args)
-    enc.load_state_dict(P, strict=True)
-    enc = enc.to(DEV).train()
+    args = make_args(d, small["loc"], F=int(small["dims"][4]))
+    enc = TB.build_encoder(P, args, DEV)
     lossf = CLIPLoss(args)
     with torch.no_grad():
         lossf.temp.copy_(temp.reshape(1))
@@ -199,8 +195,7 @@ CASES = ([("toy", k, dt, xdt, mode) for k in KINDS for dt in DT for xdt in DT fo
 def test_against_float64_oracle(shape, kind, dtype, xdt, mode):
     d = SHAPES[shape]
     training = mode == "train"
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], 8, d["K"], seed=2, loc=loc)
+    loc, P = positions_and_params(d)
     m = build(kind, d, loc, P, dtype, training)
     cin, cout = channels(kind, d)
     g = torch.Generator().manual_seed(5)
@@ -253,8 +248,7 @@ def test_against_float64_oracle(shape, kind, dtype, xdt, mode):
 def test_frozen_parameters_and_inputs_without_gradient(kind, monkeypatch):
     from speech_decoding_amd import ops
     d = TOY
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], 8, d["K"], seed=2, loc=loc)
+    loc, P = positions_and_params(d)
     cin, cout = channels(kind, d)
     X = torch.randn(d["B"], cin, d["T"]).to(DEV)
     subj = torch.tensor([0, 1, 2, 0, 1, 2])
@@ -293,8 +287,7 @@ def rng_equal(a, b):
 
 def test_eval_draws_nothing_and_train_draws_once_per_call():
     d = TOY
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], 8, d["K"], seed=2, loc=loc)
+    loc, P = positions_and_params(d)
     X = torch.randn(d["B"], d["C"], d["T"]).to(DEV)
     subj = torch.tensor([0, 1, 2, 0, 1, 2])
     np.random.seed(7)
@@ -330,8 +323,7 @@ def test_eval_draws_nothing_and_train_draws_once_per_call():
 
 def test_absent_subject_gets_a_zero_gradient_slice():
     d = TOY
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], 8, d["K"], seed=2, loc=loc)
+    loc, P = positions_and_params(d)
     for dtype in ("fp32", "bf16"):
         sb = build("sb", d, loc, P, dtype)
         sb.spatial_attention.set_drop_centre(2)
@@ -343,8 +335,7 @@ def test_absent_subject_gets_a_zero_gradient_slice():
 
 def test_bad_subject_indices():
     d = TOY
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], 8, d["K"], seed=2, loc=loc)
+    loc, P = positions_and_params(d)
     sb = build("sb", d, loc, P)
     X = torch.randn(d["B"], d["C"], d["T"]).to(DEV)
     with pytest.raises(IndexError):
@@ -357,19 +348,13 @@ def test_bad_subject_indices():
 # 5. isolation from the encoder's engine
 # ------------------------------------------------------------------------------------------------------------------------------
 def build_encoder(P, d, loc, F=16):
-    from speech_decoding.models import BrainEncoder
-    args = make_args(d, loc)
-    args["F"] = F
-    enc = BrainEncoder(args)
-    enc.load_state_dict(P)
-    return enc.to(DEV).train()
+    return TB.build_encoder(P, make_args(d, loc, F=F), DEV)
 
 
 @pytest.mark.parametrize("C", [20, 64])
 def test_pending_encoder_backward_is_unaffected(C):
     d = dict(TOY, C=C)
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], 16, d["K"], seed=2, loc=loc)
+    loc, P = positions_and_params(d, F=16)
     g = torch.Generator().manual_seed(9)
     X = torch.randn(d["B"], d["C"], d["T"], generator=g)
     R = torch.randn(d["B"], 16, d["T"], generator=g)
@@ -403,8 +388,7 @@ def test_pending_encoder_backward_is_unaffected(C):
 
 def test_outputs_of_earlier_calls_stay_valid():
     d = TOY
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], 8, d["K"], seed=2, loc=loc)
+    loc, P = positions_and_params(d)
     sb, cb = build("sb", d, loc, P, "bf16"), build("cb0", d, loc, P, "bf16")
     subj = torch.tensor([0, 1, 2, 0, 1, 2])
     X1 = torch.randn(d["B"], d["C"], d["T"]).to(DEV)
@@ -424,8 +408,7 @@ def test_outputs_of_earlier_calls_stay_valid():
 def test_chained_calls_hand_over_row_layout_views(dtype, monkeypatch):
     from speech_decoding_amd import ops
     d = TOY
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], 16, d["K"], seed=2, loc=loc)
+    loc, P = positions_and_params(d, F=16)
     enc = build_encoder(P, d, loc)
     enc.set_compute_dtype(DT[dtype])
     subj = torch.tensor([0, 1, 2, 0, 1, 2])
@@ -524,8 +507,7 @@ def test_rows_of_roundtrip(T):
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 def test_16bit_input_gives_the_bits_of_its_fp32_values(kind, dtype):
     d = TOY
-    loc = O.synthetic_positions(d["C"], seed=1)
-    P = O.seeded_params(d["C"], d["S"], d["D1"], d["D2"], 8, d["K"], seed=2, loc=loc)
+    loc, P = positions_and_params(d)
     m = build(kind, d, loc, P, dtype, training=False)
     cin, _ = channels(kind, d)
     subj = torch.tensor([0, 1, 2, 0, 1, 2])

@@ -17,12 +17,9 @@ import torch.nn.functional as TF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from speech_decoding_amd.config import Config  # noqa: E402
 
 DT = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
-
-
-class Args(dict):
-    __getattr__ = dict.__getitem__
 
 
 def eager_sa(z, cos, sin, mask, X):
@@ -104,7 +101,7 @@ def main():
     for name in a.dtypes:
         dt = DT[name]
         torch.manual_seed(2)
-        args = Args(num_subjects=S, D1=D1, D2=D2, F=8, K=K, dataset="Gwilliams2022", d_drop=0.1, root_dir=".",
+        args = Config(num_subjects=S, D1=D1, D2=D2, F=8, K=K, dataset="Gwilliams2022", d_drop=0.1, root_dir=".",
                     preprocs={"last4layers": False}, sensor_positions=loc.numpy(), compute_dtype=name)
         sb = SubjectBlock(args).to(dev).train()
         sb.spatial_attention.set_drop_centre(5)

@@ -15,10 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from speech_decoding_amd import clip, lib as L, ops  # noqa: E402
-
-
-class Args(dict):
-    __getattr__ = dict.__getitem__
+from speech_decoding_amd.config import Config  # noqa: E402
 
 
 def timeit(fn, iters, warm=3):
@@ -44,7 +41,7 @@ def one(B, F, T, dtype, iters, dev="cuda:0"):
     Z = ops.rows_view(zbuf, B, F, T)
     Y = torch.randn(B, F, T, generator=g, device=dev)
     Yg = Y.clone().requires_grad_(True)
-    crit = CLIPLoss(Args(reduction="mean", init_temperature=2.0)).to(dev)
+    crit = CLIPLoss(Config(reduction="mean", init_temperature=2.0)).to(dev)
 
     def step(x):
         loss = crit(x, Z)

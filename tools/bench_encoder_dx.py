@@ -20,14 +20,11 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from speech_decoding_amd import lib as L, ops  # noqa: E402
+from speech_decoding_amd.config import Config  # noqa: E402
 
 SHAPES = [dict(name="config2", C=208, S=27, T=360, B=256, dtype="bf16"), dict(name="config1", C=60, S=1, T=360, B=64, dtype="fp32")]
 D1, D2, F, K = 270, 320, 1024, 32
 DT = {"fp32": torch.float32, "bf16": torch.bfloat16}
-
-
-class Args(dict):
-    __getattr__ = dict.__getitem__
 
 
 def timeit(fn, iters, rounds, warm=3):
@@ -51,7 +48,7 @@ def setup(s, dev="cuda:0"):
     from speech_decoding.utils.loss import CLIPLoss
     torch.manual_seed(0)
     loc = np.random.RandomState(0).uniform(0.1, 0.9, size=(s["C"], 2))     # sensor positions in the layout's unit square
-    args = Args(num_subjects=s["S"], D1=D1, D2=D2, F=512, K=K, dataset="Gwilliams2022", d_drop=0.1, root_dir=".",
+    args = Config(num_subjects=s["S"], D1=D1, D2=D2, F=512, K=K, dataset="Gwilliams2022", d_drop=0.1, root_dir=".",
                 preprocs={"last4layers": True}, reduction="mean", init_temperature=5.1, sensor_positions=loc,
                 compute_dtype=s["dtype"])
     enc = BrainEncoder(args).to(dev).train()          # the reference's own initialisation
