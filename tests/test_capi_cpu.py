@@ -1,6 +1,6 @@
 """CPU checks of the drop-in boundary: libsdamd.so loads, exports every symbol include/sd_amd.h declares,
-the ctypes mirror of the argument structs matches the C layout, and the product refuses to run without
-a GPU (no silent CPU fallback).  No kernel is launched here."""
+the binding lib.py derives from that header agrees with what the C compiler makes of it (struct layouts, prototypes, scalar sizes),
+and the product refuses to run without a GPU (no silent CPU fallback).  No kernel is launched here."""
 import ctypes
 import os
 import re
@@ -62,23 +62,90 @@ def test_tile_rules_are_the_library_s(lib):
     assert [ops.wgrad_tile_m(c) for c in (320, 640, 256, 1024, 192)] == [160, 160, 128, 128, 64]
 
 
-def test_struct_layout_matches_c(lib, tmp_path):
-    """sizeof/offsetof of the two argument structs as the C compiler sees them vs the ctypes mirror."""
-    src = tmp_path / "probe.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sd_amd.h"\nint main(void){\n'
-                   'printf("%zu %zu %zu %zu %zu\\n", sizeof(sda_conv_args), offsetof(sda_conv_args, B), '
-                   'offsetof(sda_conv_args, x_pitch), offsetof(sda_conv_args, w_rows_limit), offsetof(sda_conv_args, dtype));\n'
-                   'printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(sda_wgrad_args), offsetof(sda_wgrad_args, nseg), '
-                   'offsetof(sda_wgrad_args, dy_pitch), offsetof(sda_wgrad_args, rows_limit), offsetof(sda_wgrad_args, dtype), offsetof(sda_wgrad_args, flags));\n'
-                   'return 0;}\n')
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
-    ca, wa = lib.ConvArgs, lib.WgradArgs
-    assert [int(v) for v in out[0].split()] == [ctypes.sizeof(ca), ca.B.offset, ca.x_pitch.offset,
-                                                ca.w_rows_limit.offset, ca.dtype.offset]
-    assert [int(v) for v in out[1].split()] == [ctypes.sizeof(wa), wa.nseg.offset, wa.dy_pitch.offset,
-                                                wa.rows_limit.offset, wa.dtype.offset, wa.flags.offset]
+@pytest.fixture(scope="module")
+def c_probe(lib, tmp_path_factory):
+    """What the C compiler makes of sd_amd.h: {"sizeof T": n, "sda_x.field": (offset, size)} for every field of every struct
+    the binding parsed, and for the scalar types it maps; {"SDA_X": value} for every constant.  The probe program is generated from
+    the parsed field lists."""
+    types = list(lib.SCALARS) + ["void*", "const char*"] + list(lib.STRUCTS)
+    lines = ['printf("sizeof %s=%%zu\\n", sizeof(%s));' % (t, t) for t in types]
+    lines += ['printf("%s.%s=%%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (c, f, c, f, c, f)
+              for c, cls in lib.STRUCTS.items() for f, _ in cls._fields_]
+    lines += ['printf("SDA_%s=%%ld\\n", (long)SDA_%s);' % (k, k) for k in lib.CONSTANTS]
+    work = tmp_path_factory.mktemp("probe")
+    (work / "probe.c").write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sd_amd.h"\nint main(void){\n%s\nreturn 0;}\n'
+                                  % "\n".join(lines))
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(work / "probe.c"), "-o", str(work / "probe")], check=True)
+    out = subprocess.run([str(work / "probe")], check=True, capture_output=True, text=True).stdout
+    return {k: tuple(int(x) for x in v.split()) for k, v in (ln.split("=") for ln in out.splitlines())}
+
+
+def test_struct_layout_matches_c(lib, c_probe):
+    """sizeof of all five argument structs and offsetof / sizeof of every field as the C compiler sees them vs the ctypes classes
+    the binding derived from the header."""
+    assert {c: cls.__name__ for c, cls in lib.STRUCTS.items()} == {
+        "sda_conv_args": "ConvArgs", "sda_wgrad_args": "WgradArgs", "sda_pack_desc": "PackDesc", "sda_pgemm_args": "PgemmArgs",
+        "sda_adam_desc": "AdamDesc"}
+    assert [len(lib.STRUCTS[c]._fields_) for c in ("sda_conv_args", "sda_wgrad_args", "sda_pack_desc", "sda_pgemm_args",
+                                                   "sda_adam_desc")] == [28, 27, 14, 17, 6]
+    for c, cls in lib.STRUCTS.items():
+        assert getattr(lib, cls.__name__) is cls
+        assert c_probe["sizeof " + c] == (ctypes.sizeof(cls),), c
+        for f, _ in cls._fields_:
+            assert c_probe[f"{c}.{f}"] == (getattr(cls, f).offset, getattr(cls, f).size), f"{c}.{f}"
+
+
+def test_scalar_map_and_constants_match_c(lib, c_probe):
+    assert set(lib.SCALARS) == {"int", "long", "float", "double"}
+    for c, t in list(lib.SCALARS.items()) + [("void*", ctypes.c_void_p), ("const char*", ctypes.c_char_p)]:
+        assert c_probe["sizeof " + c] == (ctypes.sizeof(t),), c
+    assert len(lib.CONSTANTS) >= 21
+    for k, v in lib.CONSTANTS.items():
+        assert c_probe["SDA_" + k] == (v,) and getattr(lib, k) == v, k
+
+
+def test_prototypes_match_c(lib, tmp_path):
+    """Every prototype, rebuilt from the C type strings the parser kept next to the ctypes types, is the type of the function
+    sd_amd.h declares: a dropped, merged or mis-split argument fails the compilation and names the function."""
+    assert set(lib.PROTOTYPES) == set(lib.SIGNATURES) == set(declared_symbols())
+    scalars = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double}
+    asserts = []
+    for name, (ret, args) in lib.PROTOTYPES.items():
+        res, argtypes = lib.SIGNATURES[name]
+        assert len(args) == len(argtypes), name
+        assert res is (ctypes.c_char_p if ret == "const char*" else scalars[ret]), name
+        for c, t in zip(args, argtypes):                        # the ctypes type is the one the C string maps to
+            block = re.fullmatch(r"const (sda_\w+_args)\*", c)
+            want = ctypes.POINTER(lib.STRUCTS[block.group(1)]) if block else ctypes.c_void_p if c.endswith("*") else scalars[c]
+            assert t is want, (name, c, t)
+        asserts.append('_Static_assert(__builtin_types_compatible_p(__typeof__(&%s), %s (*)(%s)), "%s");'
+                       % (name, ret, ", ".join(args) or "void", name))
+    assert len(asserts) >= 100
+    (tmp_path / "protos.c").write_text('#include "sd_amd.h"\n' + "\n".join(asserts) + "\n")
+    r = subprocess.run(["gcc", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(tmp_path / "protos.c")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+@pytest.mark.parametrize("name,text", [
+    ("sda_probe_a", "int sda_ok(int n);\nint sda_probe_a(const float* x, unsigned short n, void* stream);"),       # scalar outside the table
+    ("sda_probe_b", "int sda_probe_b(void (*done)(int), void* stream);"),                                           # function pointer
+    ("sda_probe_c", "int sda_probe_c(int n[4], void* stream);"),                                                    # array
+    ("sda_probe_d", "typedef struct sda_probe_d {\n  const float* p;\n  long long total;\n} sda_probe_d;"),         # field type
+    ("sda_probe_e", "typedef struct sda_probe_e {\n  float* a, b;\n} sda_probe_e;"),                                # field it cannot split
+    ("sda_probe_f", "int sda_ok(int n);\nint sda_probe_f(int a), int b);\nlong sda_ok2(void);"),                    # stray )
+    ("sda_probe_g", "enum { SDA_A = 1 };\ndouble* sda_probe_g(int n);"),                                            # pointer return
+])
+def test_parser_refuses_what_it_cannot_map(lib, name, text):
+    from speech_decoding_amd import SdaError
+    with pytest.raises(SdaError, match=name):
+        lib.parse_header("#define SDA_ABI_VERSION 4\n" + text + "\n")
+
+
+def test_missing_header_is_an_error(lib, tmp_path):
+    from speech_decoding_amd import SdaError
+    with pytest.raises(SdaError, match="missing.h"):
+        lib.read_abi(str(tmp_path / "missing.h"))
 
 
 def test_argument_validation_without_launch(lib):
