@@ -686,6 +686,51 @@ int sda_mel_power_f32(const float* spec, long spec_row_stride, long spec_pitch, 
 int sda_stft_fft_f32(const float* x, long x_row_stride, int rows, long frames, int hop, int n_fft, const float* window,
                      const float* twiddle, float* out, long out_row_stride, long out_pitch, void* stream);
 
+/* ---- Gradient guard (ABI 4, addition): global-norm clipping and the fp16 overflow guard decided on the device, three launches
+ * over the descriptor table sda_adam_multi takes (csrc/grad_guard.hip, csrc/param_ops.hip).  No host read-back anywhere: the
+ * decision lives in `state`, SDA_GUARD_STATE doubles on the device, at the slot indices below.
+ *   SCALE     the loss scale the NEXT backward is multiplied by (set by the caller before the first step, >= 1)
+ *   SKIP      1 when the last finish found a non-finite gradient (the guarded Adam then writes nothing), else 0
+ *   STEP      number of APPLIED steps (the bias corrections' exponent)     GOOD     applied steps since the last skip or growth
+ *   SKIPPED   number of skipped steps                                      NORM     last unscaled gradient norm (+inf on a skip)
+ *   COEF      last factor on the stored gradients: (1 / scale used) x clip factor (0 on a skip)
+ *   BC1, BC2_SQRT   1 - beta1^STEP and sqrt(1 - beta2^STEP), rounded to float, as sda_adam_multi's host code computes them
+ *   NONFINITE last count of inf / NaN gradient elements                    SUMSQ    last sum of squares of the finite ones */
+#define SDA_GUARD_SCALE 0
+#define SDA_GUARD_SKIP 1
+#define SDA_GUARD_STEP 2
+#define SDA_GUARD_GOOD 3
+#define SDA_GUARD_SKIPPED 4
+#define SDA_GUARD_NORM 5
+#define SDA_GUARD_COEF 6
+#define SDA_GUARD_BC1 7
+#define SDA_GUARD_BC2_SQRT 8
+#define SDA_GUARD_NONFINITE 9
+#define SDA_GUARD_SUMSQ 10
+#define SDA_GUARD_STATE 16
+/* doubles sda_grad_sumsq_multi writes for n tensors of at most max_n elements: 2 * n * gx, gx = min(ceil(max_n / 1024), 256)
+ * (sda_adam_multi's grid rule); -1 for n < 1 or max_n < 1 */
+long sda_grad_guard_parts(int n, long max_n);
+/* partials[t][b][0] = sum of g^2 over the FINITE gradient elements workgroup b of tensor t reads (the elements
+ * sda_adam_multi's workgroup b updates), every product and every add in double; partials[t][b][1] = how many of them are inf or
+ * NaN.  Dense [n][gx][2]; every slot is written, zeros by a workgroup past its tensor's end.  Only descs[t].grad, n and aligned
+ * are read.  Fixed summation order (a thread's elements in index order, then a fixed tree over the 256 threads): the same bits
+ * on every call. */
+int sda_grad_sumsq_multi(const sda_adam_desc* descs, int n, long max_n, double* partials, void* stream);
+/* One workgroup: sums the n * gx slots (thread t adds slots t, t + 256, ... in index order, then the fixed tree) and takes the
+ * decision in double.  scale = state[SCALE], norm = sqrt(sum) / scale.
+ *   count > 0:  SKIP = 1, SKIPPED += 1, GOOD = 0, STEP stays, COEF = 0, NORM = +inf, and with dynamic != 0 SCALE = max(1, SCALE / 2).
+ *   otherwise:  SKIP = 0, STEP += 1, GOOD += 1; with dynamic != 0 and GOOD >= growth_interval, SCALE = min(max_scale, 2 SCALE) and
+ *               GOOD = 0; COEF = (1 / scale) * min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_'s rule; max_norm <= 0
+ *               or +inf: the clip factor is exactly 1); BC1 / BC2_SQRT from the new STEP and the float betas.
+ * Null pointers, n < 1, gx < 1, growth_interval < 0, a NaN max_norm and max_scale < 1 return -1 (sda_last_error), no launch. */
+int sda_grad_guard_finish(const double* partials, int n, int gx, double* state, double max_norm, float beta1, float beta2,
+                          long growth_interval, double max_scale, int dynamic, void* stream);
+/* sda_adam_multi behind the guard: nothing is written when state[SKIP] is set; otherwise the update of sda_adam_multi on
+ * fl32(grad * (float)state[COEF]) with the bias corrections read from state.  The stored gradients are not modified. */
+int sda_adam_multi_guarded(const sda_adam_desc* descs, int n, long max_n, float lr, float beta1, float beta2, float eps,
+                           const double* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,14 +184,18 @@ extern "C" int sda_unpack_conv_wgrad(const float* g, float* dst, int nW, int Cou
 
 // Adam (train.py:161-163: torch.optim.Adam defaults, no weight decay / amsgrad) over ALL parameter tensors in
 // one launch: blockIdx.y selects the tensor, complex parameters are updated through their real view.
-__global__ __launch_bounds__(256) void adam_multi_kernel(const sda_adam_desc* __restrict__ descs, float lr, float beta1,
-                                                         float beta2, float eps, float bc1, float bc2_sqrt) {
-  const sda_adam_desc d = descs[blockIdx.y];
+// adam_multi_body is the update of both kernels below, so that they compile the same arithmetic: COEF = false is
+// sda_adam_multi's (the gradient as stored), COEF = true sda_adam_multi_guarded's (the gradient times `coef`, rounded to fp32
+// by a multiply of its own — __fmul_rn is never contracted into the sums behind it).
+template <bool COEF>
+__device__ __forceinline__ void adam_multi_body(const sda_adam_desc& d, float lr, float beta1, float beta2, float eps, float bc1,
+                                                float bc2_sqrt, float coef) {
   const float step_size = lr / bc1;
   for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < d.n; i += (long)gridDim.x * 1024) {
     if (i + 4 <= d.n && d.aligned) {
       float4 p = *reinterpret_cast<float4*>(d.param + i);
-      const float4 g = *reinterpret_cast<const float4*>(d.grad + i);
+      float4 g = *reinterpret_cast<const float4*>(d.grad + i);
+      if (COEF) { g.x = __fmul_rn(g.x, coef); g.y = __fmul_rn(g.y, coef); g.z = __fmul_rn(g.z, coef); g.w = __fmul_rn(g.w, coef); }
       float4 m = *reinterpret_cast<float4*>(d.exp_avg + i), v = *reinterpret_cast<float4*>(d.exp_avg_sq + i);
 #define SDA_ADAM(f)                                                     \
       m.f = beta1 * m.f + (1.f - beta1) * g.f;                          \
@@ -204,7 +208,7 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const sda_adam_desc* __
       *reinterpret_cast<float4*>(d.exp_avg_sq + i) = v;
     } else {
       for (long j = i; j < min(i + 4, d.n); ++j) {
-        const float g = d.grad[j];
+        const float g = COEF ? __fmul_rn(d.grad[j], coef) : d.grad[j];
         const float m = beta1 * d.exp_avg[j] + (1.f - beta1) * g;
         const float v = beta2 * d.exp_avg_sq[j] + (1.f - beta2) * g * g;
         d.exp_avg[j] = m;
@@ -213,6 +217,24 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const sda_adam_desc* __
       }
     }
   }
+}
+
+__global__ __launch_bounds__(256) void adam_multi_kernel(const sda_adam_desc* __restrict__ descs, float lr, float beta1,
+                                                         float beta2, float eps, float bc1, float bc2_sqrt) {
+  const sda_adam_desc d = descs[blockIdx.y];
+  adam_multi_body<false>(d, lr, beta1, beta2, eps, bc1, bc2_sqrt, 1.f);
+}
+
+// The same update behind the gradient guard (grad_guard.hip): the step is decided on the device.  state[SDA_GUARD_SKIP] set:
+// every thread returns before its first load, nothing is written.  Otherwise the gradient is multiplied by
+// (float)state[SDA_GUARD_COEF] (un-scaling and clipping in one factor) and both bias corrections are the ones
+// sda_grad_guard_finish left in `state` for the step it counted.
+__global__ __launch_bounds__(256) void adam_multi_guarded_kernel(const sda_adam_desc* __restrict__ descs, float lr, float beta1,
+                                                                 float beta2, float eps, const double* __restrict__ state) {
+  if (state[SDA_GUARD_SKIP] != 0.0) return;
+  const sda_adam_desc d = descs[blockIdx.y];
+  adam_multi_body<true>(d, lr, beta1, beta2, eps, (float)state[SDA_GUARD_BC1], (float)state[SDA_GUARD_BC2_SQRT],
+                        (float)state[SDA_GUARD_COEF]);
 }
 
 extern "C" int sda_adam_multi(const sda_adam_desc* descs_dev, int n, long max_n, float lr, float beta1, float beta2, float eps,
@@ -225,6 +247,16 @@ extern "C" int sda_adam_multi(const sda_adam_desc* descs_dev, int n, long max_n,
   hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, (hipStream_t)stream, descs_dev, lr, beta1,
                      beta2, eps, (float)bc1, (float)sqrt(bc2));
   return check_launch("adam_multi");
+}
+
+extern "C" int sda_adam_multi_guarded(const sda_adam_desc* descs_dev, int n, long max_n, float lr, float beta1, float beta2,
+                                      float eps, const double* state, void* stream) {
+  if (!descs_dev || !state || n < 1 || max_n < 1) { set_error("adam_multi_guarded: bad arguments (null pointer, n or max_n < 1)"); return -1; }
+  long gx = (max_n + 1023) / 1024;
+  if (gx > 256) gx = 256;
+  hipLaunchKernelGGL(adam_multi_guarded_kernel, dim3((unsigned)gx, (unsigned)n), dim3(256), 0, (hipStream_t)stream, descs_dev, lr,
+                     beta1, beta2, eps, state);
+  return check_launch("adam_multi_guarded");
 }
 
 extern "C" int sda_pack_multi(const sda_pack_desc* descs_dev, int n, long max_total, int dtype, void* stream) {

@@ -1282,3 +1282,46 @@ def stft_fft(rows_padded: torch.Tensor, window: torch.Tensor, twiddle: torch.Ten
         L.check(L.load().sda_stft_fft_f32(_p(rows_padded), rows_padded.shape[1], rows, frames, hop, n_fft, _p(window), _p(twiddle),
                                           _p(out), frames * n_freqs * 2, n_freqs * 2, _st()), "stft_fft")
     return out
+
+
+# ---- gradient guard (csrc/grad_guard.hip, csrc/param_ops.hip): three launches over Adam's descriptor table, no read-back ----
+def grad_guard_parts(n: int, max_n: int) -> int:
+    """Doubles `grad_sumsq_multi` writes for n tensors of at most max_n elements: 2 n gx, gx = min(ceil(max_n / 1024), 256)."""
+    parts = int(L.load().sda_grad_guard_parts(int(n), int(max_n)))
+    if parts < 0:
+        L.check(-1, "grad_guard_parts")
+    return parts
+
+
+def _need_guard_state(state: torch.Tensor, who: str):
+    _need_values(state, torch.float64, L.GUARD_STATE, "{}: state is {} contiguous device doubles", who, L.GUARD_STATE)
+
+
+def grad_sumsq_multi(table: torch.Tensor, n: int, max_n: int, partials: torch.Tensor) -> torch.Tensor:
+    """`sda_grad_sumsq_multi`: partials[t][b] = (sum of g^2 over the finite elements, count of the non-finite ones) of the slice
+    of tensor t that Adam's workgroup b updates; table: the uploaded sda_adam_desc array of n entries.  Every slot is written."""
+    _need_cuda(table)
+    _need_values(partials, torch.float64, grad_guard_parts(n, max_n), "grad_sumsq_multi: partials holds {} contiguous device doubles",
+                 grad_guard_parts(n, max_n))
+    L.check(L.load().sda_grad_sumsq_multi(_p(table), int(n), int(max_n), _p(partials), _st()), "grad_sumsq_multi")
+    return partials
+
+
+def grad_guard_finish(partials: torch.Tensor, n: int, gx: int, state: torch.Tensor, max_norm: float, beta1: float, beta2: float,
+                      growth_interval: int, max_scale: float, dynamic: bool) -> torch.Tensor:
+    """`sda_grad_guard_finish`: the step's decision from the n x gx partial slots into `state` (lib.GUARD_* slots), on the device."""
+    _need_values(partials, torch.float64, 2 * int(n) * int(gx), "grad_guard_finish: partials holds {} contiguous device doubles",
+                 2 * int(n) * int(gx))
+    _need_guard_state(state, "grad_guard_finish")
+    L.check(L.load().sda_grad_guard_finish(_p(partials), int(n), int(gx), _p(state), float(max_norm), float(beta1), float(beta2),
+                                           int(growth_interval), float(max_scale), int(bool(dynamic)), _st()), "grad_guard_finish")
+    return state
+
+
+def adam_multi_guarded(table: torch.Tensor, n: int, max_n: int, lr: float, beta1: float, beta2: float, eps: float,
+                       state: torch.Tensor) -> None:
+    """`sda_adam_multi_guarded`: Adam over the table's tensors on grad * (float)state[COEF], or nothing when state[SKIP] is set."""
+    _need_cuda(table)
+    _need_guard_state(state, "adam_multi_guarded")
+    L.check(L.load().sda_adam_multi_guarded(_p(table), int(n), int(max_n), float(lr), float(beta1), float(beta2), float(eps),
+                                            _p(state), _st()), "adam_multi_guarded")

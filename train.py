@@ -25,6 +25,8 @@ shapes; a real dataset object can be passed to `run()` as (train_batches, test_b
 
 Layout: `build_data` makes the synthetic data of a `data=` kind (the feed, or None for the pool, and the two callables; sampler,
 epoch seed and test shard are written there once), `make_backward_and_step` the update, `run` the loop around them.
+`max_grad_norm=1.0` clips the gradients by their global norm and `fp16_guard=device` moves fp16's overflow guard off the host;
+either one runs the step through `make_guarded_step` (GuardedAdam: norm, guard, clipping and Adam on the device, no read-back).
 """
 from __future__ import annotations
 
@@ -161,9 +163,43 @@ def make_backward_and_step(brain_encoder, loss_func, params, optimizer, scaler, 
     return backward_and_step
 
 
+def make_guarded_step(brain_encoder, loss_func, params, optimizer, world: int, device):
+    """backward_and_step(loss) with the guard on the device (`optimizer`: speech_decoding_amd.optim.GuardedAdam): backward of the
+    scaled loss, the same gradient all-reduce as make_backward_and_step, and optimizer.step() — the gradient norm, the overflow
+    check, the loss-scale update, clipping and Adam in three launches.  Nothing here reads the device back: the host goes on
+    enqueueing the next step.  Under data parallelism the guard runs after the SUM of the still-scaled gradients, so every rank
+    reduces the same bits and takes the same decision — no further collective.  A non-finite gradient skips the step in every
+    dtype (bf16 / fp32 run at scale 1, not dynamic): torch.nn.utils.clip_grad_norm_ would pass the NaN on to every parameter
+    instead; that difference is deliberate.  As in make_backward_and_step, a skipped step has still moved BatchNorm's statistics."""
+    clip = isinstance(loss_func, CLIPLoss)
+    one = torch.ones((), dtype=torch.float32, device=device)
+
+    def backward_and_step(loss):
+        optimizer.zero_grad()
+        optimizer.scale(loss).backward(gradient=one)
+        if world > 1:
+            if not brain_encoder.grads_are_reduced:
+                allreduce_gradients(params)
+            elif clip:
+                allreduce_gradients(list(loss_func.parameters()))
+        optimizer.step()
+    return backward_and_step
+
+
+def guard_mode(args):
+    """(guarded, max_grad_norm) from the optional keys max_grad_norm (unset / null: no clipping) and fp16_guard (host: the
+    per-step read-back of amp.LossScaler, the default; device: GuardedAdam).  Either one selects the guarded step."""
+    where = str(args.get("fp16_guard", "host"))
+    if where not in ("host", "device"):
+        raise ValueError(f"fp16_guard={where}: expected host or device")
+    max_grad_norm = args.get("max_grad_norm", None)
+    return where == "device" or max_grad_norm is not None, None if max_grad_norm is None else float(max_grad_norm)
+
+
 def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Callable] = None, log=print):
     import torch.distributed as dist
     data_kind = str(args.get("data", "pool"))
+    guarded, max_grad_norm = guard_mode(args)          # (an unknown fp16_guard is refused before anything touches the device)
     if train_batches is None and data_kind == "continuous" and args.dataset != "Brennan2018":
         raise ValueError("data=continuous is Brennan2018's input path (one stimulus, every subject): use dataset=Brennan2018")
     if train_batches is None and data_kind == "tracks" and args.dataset != "Gwilliams2022":
@@ -215,7 +251,8 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
     broadcast_parameters(brain_encoder)
     # MSELoss has no parameters of its own: Adam steps the encoder alone
     params = list(brain_encoder.parameters()) + (list(loss_func.parameters()) if clip else [])
-    optimizer = torch.optim.Adam(params, lr=float(args.lr))
+    if not guarded:
+        optimizer = torch.optim.Adam(params, lr=float(args.lr))
     wandb = None
     if args.get("use_wandb", False) and rank == 0:
         import wandb as _wandb
@@ -226,7 +263,13 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
     from speech_decoding_amd.amp import LossScaler
     scaler = LossScaler.for_dtype(brain_encoder.compute_dtype, float(args.get("fp16_loss_scale", 1024.0)),
                                   global_batch=int(args.batch_size), T=D.segment_dims(args).T)     # no-op unless fp16
-    backward_and_step = make_backward_and_step(brain_encoder, loss_func, params, optimizer, scaler, world, device)
+    if guarded:          # the same starting scale and growth rules, kept and applied on the device (bf16 / fp32: scale 1, fixed)
+        from speech_decoding_amd.optim import GuardedAdam
+        optimizer = GuardedAdam(params, lr=float(args.lr), max_grad_norm=max_grad_norm, loss_scale=scaler.scale_value,
+                                dynamic=scaler.enabled, growth_interval=scaler.growth_interval, max_scale=scaler.max_scale)
+        backward_and_step = make_guarded_step(brain_encoder, loss_func, params, optimizer, world, device)
+    else:
+        backward_and_step = make_backward_and_step(brain_encoder, loss_func, params, optimizer, scaler, world, device)
 
     history = []
     for epoch in range(int(args.epochs)):
@@ -287,6 +330,9 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
                "lrate": optimizer.param_groups[0]["lr"]}
         if clip:
             row["temp"] = loss_func.temp.item()
+        if guarded:          # read back here, once per epoch: the last step's unscaled norm and the skips so far
+            row["grad_norm"] = optimizer.last_grad_norm
+            row["skipped_steps"] = optimizer.skipped_steps
         history.append(row)
         if rank == 0:
             log(f"Ep {epoch}/{args.epochs} | ", f"train l: {row['train_loss']:.3f} | ", f"test l: {row['test_loss']:.3f} | ",
