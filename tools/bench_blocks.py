@@ -8,16 +8,12 @@ Shapes default to config 2 (C = 208, S = 27, D1 = 270, D2 = 320).  Both sides ru
 input requiring a gradient; the backward is driven by a fixed incoming gradient of the output's dtype.  Prints one JSON line per
 (module, dtype) with milliseconds per call."""
 import argparse
-import json
-import os
-import sys
 
 import torch
 import torch.nn.functional as TF
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from speech_decoding_amd.config import Config  # noqa: E402
+from harness import emit, need_gpu, window
+from speech_decoding_amd.config import Config
 
 DT = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
 
@@ -66,19 +62,6 @@ def eager_params(module, dt):
     return out
 
 
-def timed(fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtypes", nargs="+", default=["bf16", "fp32"])
@@ -91,6 +74,7 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     a = ap.parse_args()
+    need_gpu()
     from speech_decoding.models import ConvBlock, SubjectBlock
     from speech_decoding_amd.layout import synthetic_positions
     dev = "cuda:0"
@@ -122,9 +106,9 @@ def main():
             row = {"module": mod, "dtype": name, "B": B, "T": T, "C": C, "S": S, "D1": D1, "D2": D2}
             for side, fn in (("hip", hip), ("torch", eager)):
                 with torch.no_grad():
-                    row[f"{side}_fwd_ms"] = round(timed(fn, a.iters, a.warmup), 4)
-                row[f"{side}_fwd_bwd_ms"] = round(timed(lambda: fn().backward(G), a.iters, a.warmup), 4)
-            print(json.dumps(row), flush=True)
+                    row[f"{side}_fwd_ms"] = round(window(fn, a.iters, a.warmup), 4)
+                row[f"{side}_fwd_bwd_ms"] = round(window(lambda: fn().backward(G), a.iters, a.warmup), 4)
+            emit(row)
 
 
 if __name__ == "__main__":

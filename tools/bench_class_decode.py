@@ -10,36 +10,17 @@ profiles/class_decode_bench.json), times in milliseconds per call.  Class sizes 
 class ~ 1 / r, every class at least one member), members dealt over the bank at random.  The byte floor the reduction is
 compared against is one read of the score matrix, n * M * 4 bytes (`order` stays in L2).  The default bank takes about 24 GB."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import harness
 
 HBM_TB_S = 6.29        # measured float4 copy rate of one MI355X (8.0 TB/s is the specification)
 
 
 def timed(fns, iters, warmup, reps=1):
-    """Milliseconds per call of each callable: warm-up, then `iters` rounds that alternate the callables, events around `reps`
-    back-to-back calls of one of them."""
-    import torch
-    for _ in range(warmup):
-        for f in fns:
-            f()
-    torch.cuda.synchronize()
-    total = [0.0] * len(fns)
-    for _ in range(iters):
-        for i, f in enumerate(fns):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(reps):
-                f()
-            b.record()
-            b.synchronize()
-            total[i] += a.elapsed_time(b)
-    return [t / (iters * reps) for t in total]
+    """Milliseconds per call of each callable, the callables alternating, reps back-to-back calls per bracket."""
+    return [harness.summarize(s).mean for s in harness.alternating(fns, iters, warmup, reps)]
 
 
 def zipf_classes(M, C, seed):
@@ -56,6 +37,7 @@ def measure(a):
     import torch
     from speech_decoding_amd import ClassIndex, SpeechBank, retrieve, retrieve_classes, lib as L, ops
     from speech_decoding_amd.retrieval import _ScorePass, plan_class_blocks
+    harness.need_gpu()
     dev = "cuda:0"
     dt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[a.dtype]
     N, M, C, F, T, k, scale = a.N, a.M, a.C, a.F, a.T, a.k, a.scale
@@ -180,18 +162,14 @@ def main():
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        print(json.dumps(measure(a)), flush=True)
+        harness.emit(measure(a))
         return 0
     cmd = [sys.executable, os.path.abspath(__file__), "--child"]      # this process never opens the GPU: one fresh child
     for name in ("N", "M", "C", "F", "T", "dtype", "k", "scale", "iters", "warmup", "scratch"):
         cmd += [f"--{name}", str(getattr(a, name))]
-    try:
-        rc = subprocess.run(cmd, timeout=a.limit).returncode
-    except subprocess.TimeoutExpired:
-        print(json.dumps({"bench": "class_decode", "error": f"time limit of {a.limit} s"}), flush=True)
-        return 1
-    if rc != 0:
-        print(json.dumps({"bench": "class_decode", "error": f"exit status {rc}"}), flush=True)
+    status = harness.run_child(cmd, a.limit)
+    if status != 0:
+        harness.emit({"bench": "class_decode", "error": harness.child_error(status, a.limit)})
         return 1
     return 0
 

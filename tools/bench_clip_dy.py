@@ -7,32 +7,17 @@ unpack.  Device events after warm-up.  Diagnostic; not part of the product.
 Shapes: configs[1] (B = 256, F = 1024, T = 360) in bf16, fp16 and fp32, and 1024 speech rows in bf16.  Z is an encoder-style
 row-layout buffer of the compute dtype, x a plain fp32 (B, F, T) tensor (the wav2vec 2.0 features or a speech module's output)."""
 import argparse
-import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import torch
 
-from speech_decoding_amd import clip, lib as L, ops  # noqa: E402
-from speech_decoding_amd.config import Config  # noqa: E402
-
-
-def timeit(fn, iters, warm=3):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e3          # us per call
+from harness import emit, need_gpu, us, window
+from speech_decoding_amd import clip, lib as L, ops
+from speech_decoding_amd.config import Config
 
 
 def one(B, F, T, dtype, iters, dev="cuda:0"):
     from speech_decoding.utils.loss import CLIPLoss
+    timeit = lambda fn: us(window(fn, iters, 3))
     g = torch.Generator(device=dev).manual_seed(0)
     Cp = L.pad_channels(F)
     zbuf = ops.new_rows(B, T, Cp, dtype, dev)
@@ -52,8 +37,8 @@ def one(B, F, T, dtype, iters, dev="cuda:0"):
             x.grad = None
 
     r = {"B": B, "F": F, "T": T, "dtype": str(dtype).replace("torch.", "")}
-    r["loss_fwd_bwd_us"] = timeit(lambda: step(Y), iters)
-    r["loss_fwd_bwd_with_dx_us"] = timeit(lambda: step(Yg), iters)
+    r["loss_fwd_bwd_us"] = timeit(lambda: step(Y))
+    r["loss_fwd_bwd_with_dx_us"] = timeit(lambda: step(Yg))
     r["extra_us"] = r["loss_fwd_bwd_with_dx_us"] - r["loss_fwd_bwd_us"]
     # the parts alone, on the context of one forward
     Yt = ops.new_rows(B, T, Cp, dtype, dev)
@@ -66,13 +51,13 @@ def one(B, F, T, dtype, iters, dev="cuda:0"):
         Gy, part = ops.clip_grad_y(c.logits, c.row_lse, c.col_lse, c.zsq, c.zsq, 0, dtype)
         return Gy, ops.clip_grad_y_finish(part, c.ysq, c.zsq, temp, c.inv_norm, 0, B)
 
-    r["coef_us"] = timeit(coefs, iters)
+    r["coef_us"] = timeit(coefs)
     Gy, (rs, cs) = coefs()
     out = ops.new_rows_uninit(B, T, Cp, dtype, dev)
-    r["dy_gemm_us"] = timeit(lambda: ops.clip_dz(Gy, Zt, Yt, out, rs, cs, Bm=B, Bn=B, row_elems=c.row_elems), iters)
-    r["dz_gemm_us"] = timeit(lambda: ops.clip_dz(c.G, Yt, Zt, out, c.rscale, c.cscale, Bm=B, Bn=B, row_elems=c.row_elems), iters)
+    r["dy_gemm_us"] = timeit(lambda: ops.clip_dz(Gy, Zt, Yt, out, rs, cs, Bm=B, Bn=B, row_elems=c.row_elems))
+    r["dz_gemm_us"] = timeit(lambda: ops.clip_dz(c.G, Yt, Zt, out, c.rscale, c.cscale, Bm=B, Bn=B, row_elems=c.row_elems))
     r["dy_over_dz"] = r["dy_gemm_us"] / r["dz_gemm_us"]
-    r["unpack_us"] = timeit(lambda: ops.unpack_rows(out, B, F, T), iters)
+    r["unpack_us"] = timeit(lambda: ops.unpack_rows(out, B, F, T))
     moved = B * F * T * (torch.finfo(dtype).bits // 8 + 4)             # read the valid stored elements, write fp32
     r["unpack_TBps"] = moved / (r["unpack_us"] * 1e-6) / 1e12
     crit.release_buffers()
@@ -84,13 +69,10 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
-    rows = [one(256, 1024, 360, dt, a.iters) for dt in (torch.bfloat16, torch.float16, torch.float32)]
-    rows.append(one(1024, 1024, 360, torch.bfloat16, a.iters))
-    for r in rows:
-        print(json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items()}))
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(rows, f, indent=1)
+    need_gpu()
+    shapes = [(256, 1024, 360, dt) for dt in (torch.bfloat16, torch.float16, torch.float32)] + [(1024, 1024, 360, torch.bfloat16)]
+    for shape in shapes:
+        emit(one(*shape, a.iters), a.json, append=True, digits=3)
 
 
 if __name__ == "__main__":

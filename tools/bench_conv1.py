@@ -1,19 +1,14 @@
 """Micro-benchmark of the 1x1 convs of the step (diagnostic): conv_final1/2 forward and data gradient, SubjectBlock GEMM."""
-import sys, os, math
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch
-from speech_decoding_amd import ops, lib as L
+import math
 
-def timeit(fn, n=20, warm=3):
-    for _ in range(warm): fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n): fn()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3
+import torch
+
+from harness import need_gpu, us, window
+from speech_decoding_amd import lib as L, ops
+
 
 def main():
+    need_gpu()
     dev, dtype = "cuda:0", torch.bfloat16
     B, T = 256, 360
     for name, cin, cout, gelu, pre, widx in [("x0 (composed SubjectBlock)", 256, 320, False, False, True), ("conv_final1 fwd", 320, 640, True, True, False),
@@ -31,8 +26,9 @@ def main():
         for tag, flags in (("single", 0), ("paired", L.CONV_PAIR_TILES)):
             if widx and flags:
                 continue
-            us = timeit(lambda: ops.conv_gemm(x, wp, y, B=B, T=T, KS=1, dil=0, bias=bias, gelu=gelu, y_pre=yp if pre else None, widx=idx, flags=flags))
-            print(f"{name:28s} {cin:4d}->{cout:4d} {tag:7s} {us:7.1f} us  {fl / us / 1e6:6.1f} TF  {mb:5.0f} MB  {mb / us:5.2f} TB/s", flush=True)
+            t = us(window(lambda: ops.conv_gemm(x, wp, y, B=B, T=T, KS=1, dil=0, bias=bias, gelu=gelu, y_pre=yp if pre else None, widx=idx, flags=flags), 20, 3))
+            print(f"{name:28s} {cin:4d}->{cout:4d} {tag:7s} {t:7.1f} us  {fl / t / 1e6:6.1f} TF  {mb:5.0f} MB  {mb / t:5.2f} TB/s", flush=True)
+
 
 if __name__ == "__main__":
     main()

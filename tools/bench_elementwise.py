@@ -1,19 +1,12 @@
 """Micro-benchmark of the HBM-bound row passes at config-2 shapes (diagnostic; not part of the product)."""
-import sys, os
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+
+from harness import need_gpu, us, window
 from speech_decoding_amd import ops
 
-def timeit(fn, n=30, warm=3):
-    for _ in range(warm): fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n): fn()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3   # us
 
 def main():
+    need_gpu()
     dev = "cuda:0"
     B, T, C = 256, 360, 320
     for dtype in (torch.bfloat16, torch.float32):
@@ -46,8 +39,9 @@ def main():
             ("torch sum (read only)", mb, lambda: x.sum()),
         ]
         for name, mbytes, fn in cases:
-            us = timeit(fn)
-            print(f"{str(dtype)[6:]:9s} {name:30s} {us:7.1f} us  {mbytes:6.0f} MB  {mbytes / us:5.2f} TB/s", flush=True)
+            t = us(window(fn, 30, 3))
+            print(f"{str(dtype)[6:]:9s} {name:30s} {t:7.1f} us  {mbytes:6.0f} MB  {mbytes / t:5.2f} TB/s", flush=True)
+
 
 if __name__ == "__main__":
     main()

@@ -10,37 +10,22 @@ Shapes: configs[1] (C=208, S=27, T=360, B=256) in bf16 and configs[0] (C=60, S=1
                        forward + backward into X (the saliency-map case)
   kernel               sda_input_grad alone on the step's shapes; bytes = G read + dX written, against 8 TB/s"""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
 
-from speech_decoding_amd import lib as L, ops  # noqa: E402
-from speech_decoding_amd.config import Config  # noqa: E402
+import harness
+from speech_decoding_amd import lib as L, ops
+from speech_decoding_amd.config import Config
 
 SHAPES = [dict(name="config2", C=208, S=27, T=360, B=256, dtype="bf16"), dict(name="config1", C=60, S=1, T=360, B=64, dtype="fp32")]
 D1, D2, F, K = 270, 320, 1024, 32
 DT = {"fp32": torch.float32, "bf16": torch.bfloat16}
 
 
-def timeit(fn, iters, rounds, warm=3):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(rounds):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / iters)          # ms per call
-    return {"median_ms": statistics.median(out), "min_ms": min(out), "max_ms": max(out)}
+def timeit(fn, iters, rounds):
+    s = harness.summarize(harness.rounds(fn, iters, rounds, 3))
+    return {"median_ms": s.median, "min_ms": s.min, "max_ms": s.max}
 
 
 def setup(s, dev="cuda:0"):
@@ -124,13 +109,11 @@ def main():
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
+    harness.need_gpu()
     rows = [kernel(s, a.iters, a.rounds) | {"shape": s["name"]} for s in SHAPES] if a.kernel_only else \
         [one(s, a.iters, a.rounds) for s in SHAPES]
     for r in rows:
-        print(json.dumps(r, default=lambda v: round(v, 4) if isinstance(v, float) else v))
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(rows, f, indent=1)
+        harness.emit(r, a.json, append=True)
 
 
 if __name__ == "__main__":

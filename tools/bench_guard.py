@@ -12,76 +12,30 @@ Diagnostic; not part of the product.
 3. bf16 with max_grad_norm=1 against bf16 without (the cost of clipping where there is no guard to replace).
 Prints the table DESIGN.md §7 quotes and writes the JSON."""
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
-import warnings
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+import numpy as np
+import torch
+
+import harness
 
 C, S, T, B, F = 208, 27, 360, 256, 1024
 
 
-def timeit(fn, iters, warm=10):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e3          # us per call
+def timeit(fn, iters):
+    return harness.us(harness.window(fn, iters, 10))          # us per call
 
 
-def host_timeit(fn, iters, warm=10):
+def host_timeit(fn, iters):
     """for a call that ends in a host synchronisation: a host clock around it"""
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / iters * 1e6
-
-
-def build(dtype, dev):
-    import train  # noqa: F401
-    from speech_decoding_amd import BrainEncoder, CLIPLoss, load_config
-    from speech_decoding_amd.layout import synthetic_positions
-    cfg = load_config(overrides=[f"num_subjects={S}", f"compute_dtype={dtype}", "dataset=Gwilliams2022"])
-    cfg["sensor_positions"] = synthetic_positions(C, seed=0).numpy()
-    torch.manual_seed(0)
-    np.random.seed(0)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        enc = BrainEncoder(cfg).to(dev).train()
-    lossf = CLIPLoss(cfg).to(dev).train()
-    return cfg, enc, lossf, list(enc.parameters()) + list(lossf.parameters())
-
-
-def data_pool(dev, n=4):
-    """bench.py's synthetic pool: X ~ N(0, 1) clamped to +-20, Y = P X + 0.5 eps"""
-    g = torch.Generator(device=dev).manual_seed(1234)
-    Pm = torch.randn(F, C, generator=torch.Generator().manual_seed(7)).to(dev) / np.sqrt(C)
-    pool = []
-    for _ in range(n):
-        X = torch.randn(B, C, T, generator=g, device=dev).clamp_(-20, 20)
-        Y = torch.einsum("fc,bct->bft", Pm, X) + 0.5 * torch.randn(B, F, T, generator=g, device=dev)
-        pool.append((X, Y.contiguous()))
-    return pool
+    return harness.us(harness.host_clock(fn, iters, 10)[1])
 
 
 def launches_alone(dev, iters):
     from speech_decoding_amd import lib as L, ops
     from speech_decoding_amd.optim import _real, adam_table
-    _, _, _, params = build("fp16", dev)
+    _, _, _, params = harness.headline_modules("fp16")
     g = torch.Generator(device=dev).manual_seed(1)
     items = []
     for p in params:
@@ -130,7 +84,7 @@ class Loop:
         import train
         from speech_decoding_amd.amp import LossScaler
         from speech_decoding_amd.optim import FusedAdam, GuardedAdam
-        cfg, self.enc, self.lossf, params = build(dtype, dev)
+        cfg, self.enc, self.lossf, params = harness.headline_modules(dtype)
         scaler = LossScaler.for_dtype(self.enc.compute_dtype, global_batch=B, T=T)
         if guarded:
             self.opt = GuardedAdam(params, lr=float(cfg.lr), max_grad_norm=max_grad_norm, loss_scale=scaler.scale_value,
@@ -142,20 +96,18 @@ class Loop:
         self.pool, self.i = pool, 0
         self.rng = np.random.RandomState(100)
 
+    def one(self):
+        """train.py's step: its own step builders behind the headline forward, no retrieval ranks"""
+        X, Y = self.pool[self.i % len(self.pool)]
+        self.i += 1
+        subj = torch.from_numpy(self.rng.randint(0, S, size=B).astype(np.int32))
+        self.lossf.prefetch(Y, self.enc.compute_dtype)
+        loss = self.lossf(Y, self.enc(X, subj))
+        self.step(loss)
+
     def run(self, n):
-        """n steps; host seconds to enqueue them, wall seconds until the device is done"""
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            X, Y = self.pool[self.i % len(self.pool)]
-            self.i += 1
-            subj = torch.from_numpy(self.rng.randint(0, S, size=B).astype(np.int32))
-            self.lossf.prefetch(Y, self.enc.compute_dtype)
-            loss = self.lossf(Y, self.enc(X, subj))
-            self.step(loss)
-        t1 = time.perf_counter()
-        torch.cuda.synchronize()
-        return (t1 - t0) / n, (time.perf_counter() - t0) / n
+        """n steps; host ms per step to enqueue them, wall ms per step until the device is done"""
+        return harness.host_clock(self.one, n, 0)
 
 
 def alternate(names, loops, reps, steps, warm=12):
@@ -166,11 +118,15 @@ def alternate(names, loops, reps, steps, warm=12):
     for _ in range(reps):
         for n, lp in zip(names, loops):
             h, w = lp.run(steps)
-            host[n].append(h * 1e3)
-            wall[n].append(w * 1e3)
-    return {n: dict(step_ms_median=round(statistics.median(wall[n]), 4), step_ms_min=round(min(wall[n]), 4), step_ms_max=round(max(wall[n]), 4),
-                    spread_ms=round(max(wall[n]) - min(wall[n]), 4), host_enqueue_ms_median=round(statistics.median(host[n]), 4),
-                    windows_ms=[round(x, 4) for x in wall[n]]) for n in names}
+            host[n].append(h)
+            wall[n].append(w)
+    out = {}
+    for n in names:
+        w = harness.summarize(wall[n])
+        out[n] = dict(step_ms_median=round(w.median, 4), step_ms_min=round(w.min, 4), step_ms_max=round(w.max, 4),
+                      spread_ms=round(w.max - w.min, 4), host_enqueue_ms_median=round(harness.summarize(host[n]).median, 4),
+                      windows_ms=[round(x, 4) for x in wall[n]])
+    return out
 
 
 def main():
@@ -182,11 +138,12 @@ def main():
     a = ap.parse_args()
     if a.reps < 5:
         sys.exit("bench_guard.py: at least five repetitions of each path")
+    harness.need_gpu()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     out = dict(shape=dict(C=C, S=S, T=T, batch=B, F=F), device=torch.cuda.get_device_name(0), iters=a.iters, reps=a.reps, steps=a.steps)
     out["launches"] = launches_alone(dev, a.iters)
-    pool = data_pool(dev)
+    pool = [harness.headline_batch(B, C, T, F, seed=i) for i in range(4)]
     import gc
     for key, dtype, names, specs in (("fp16_step", "fp16", ("host guard", "device guard"), ((False, None), (True, None))),
                                      ("bf16_step", "bf16", ("no clipping", "max_grad_norm=1"), ((False, None), (True, 1.0)))):
@@ -214,10 +171,7 @@ def main():
             if isinstance(r, dict) and "step_ms_median" in r:
                 print(f"| {key[:4]}, {n} | {r['step_ms_median']:.3f} | {r['step_ms_min']:.3f} .. {r['step_ms_max']:.3f} | {r['host_enqueue_ms_median']:.3f} |")
     print(f"fp16: device - host = {out['fp16_step']['device_minus_host_ms']:+.3f} ms, spread {spread:.3f} ms, within spread: {out['fp16_step']['within_spread']}")
-    os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-    with open(a.json, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
+    harness.emit(out, a.json)
 
 
 if __name__ == "__main__":

@@ -11,13 +11,9 @@ times in milliseconds per call.  The mel kernel's bytes = the spectrum read once
 once; its share of peak is against the 8 TB/s HBM rate (MI355X data sheet), its FLOP = 2 rows frames n_freqs n_mels.  The FFT
 kernel's bytes = the padded rows read once and the spectrum written once: rows (padded samples + frames 2 n_freqs) 4."""
 import argparse
-import json
-import os
-import sys
 import warnings
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import harness
 
 HBM_PEAK_TBS = 8.0
 FP32_MATRIX_PEAK_TF = 157.3
@@ -25,21 +21,7 @@ FP32_MATRIX_PEAK_TF = 157.3
 
 def timed_pair(fa, fb, iters, warmup):
     """fa and fb alternating, each call between its own pair of events: ((mean, min, max) of fa, of fb)"""
-    import torch
-    for _ in range(warmup):
-        fa()
-        fb()
-    torch.cuda.synchronize()
-    ms = ([], [])
-    for _ in range(iters):
-        for k, fn in enumerate((fa, fb)):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            ms[k].append(a.elapsed_time(b))
-    return tuple((sum(m) / len(m), min(m), max(m)) for m in ms)
+    return tuple((s.mean, s.min, s.max) for s in map(harness.summarize, harness.alternating((fa, fb), iters, warmup)))
 
 
 def main():
@@ -54,8 +36,7 @@ def main():
     import torch
     from speech_decoding_amd import ops
     from speech_decoding_amd import signal_prep as SP
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_mel needs the GPU: nothing is measured without one")
+    harness.need_gpu()
     sr, n_fft, hop, n_mels, eps = 16000, 512, 128, 120, 1e-5
     n_freqs = n_fft // 2 + 1
     with warnings.catch_warnings():
@@ -69,11 +50,7 @@ def main():
     wnorm = float(window.pow(2).sum().sqrt())
 
     def emit(rec):
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if a.out:
-            with open(a.out, "a") as f:
-                f.write(line + "\n")
+        harness.emit(rec, a.out, append=True)
 
     for rows in a.rows:
         n = a.seconds * sr

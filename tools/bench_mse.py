@@ -6,27 +6,11 @@ warm-up, as effective TB/s over the bytes each must move (valid elements only). 
 Cases: the training one (Z a bf16 row-layout buffer, Y plain fp32), the fp32 one (Z fp32 rows, Y plain fp32), both operands in
 row layout (bf16), and a torch copy of the Y tensor as the chip's practical 1 read : 1 write ceiling on the same box."""
 import argparse
-import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
+import torch
 
-from speech_decoding_amd import lib as L, ops  # noqa: E402
-
-
-def timeit(fn, iters, warm=5):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e3          # us per call
+from harness import emit, need_gpu, us, window
+from speech_decoding_amd import lib as L, ops
 
 
 def main():
@@ -34,6 +18,7 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
+    need_gpu()
     dev = "cuda:0"
     B, F, T = 256, 1024, 360
     n = B * F * T
@@ -56,20 +41,19 @@ def main():
             yop, ybytes = Y, n * 4
         zbytes = n * torch.finfo(zdt).bits // 8
         dz = ops.new_rows_uninit(B, T, Cp, zdt, dev)
-        fwd_us = timeit(lambda: ops.mse_forward(zbuf, yop, B, F, T, B), a.iters)
-        bwd_us = timeit(lambda: ops.mse_backward(zbuf, yop, B, F, T, B, dloss, dz, None), a.iters)
-        for kind, us, nbytes in (("forward", fwd_us, zbytes + ybytes), ("backward", bwd_us, 2 * zbytes + ybytes)):
-            rows.append(dict(case=name, kind=kind, us=round(us, 1), MB=round(nbytes / 1e6, 1), TBps=round(nbytes / us / 1e6, 3)))
+        fwd_us = us(window(lambda: ops.mse_forward(zbuf, yop, B, F, T, B), a.iters, 5))
+        bwd_us = us(window(lambda: ops.mse_backward(zbuf, yop, B, F, T, B, dloss, dz, None), a.iters, 5))
+        for kind, t, nbytes in (("forward", fwd_us, zbytes + ybytes), ("backward", bwd_us, 2 * zbytes + ybytes)):
+            rows.append(dict(case=name, kind=kind, us=round(t, 1), MB=round(nbytes / 1e6, 1), TBps=round(nbytes / t / 1e6, 3)))
         del zbuf, dz
     out = torch.empty_like(Y)
-    us = timeit(lambda: out.copy_(Y), a.iters)
-    rows.append(dict(case="torch copy_ of Y (fp32)", kind="copy", us=round(us, 1), MB=round(2 * n * 4 / 1e6, 1),
-                     TBps=round(2 * n * 4 / us / 1e6, 3)))
+    t = us(window(lambda: out.copy_(Y), a.iters, 5))
+    rows.append(dict(case="torch copy_ of Y (fp32)", kind="copy", us=round(t, 1), MB=round(2 * n * 4 / 1e6, 1),
+                     TBps=round(2 * n * 4 / t / 1e6, 3)))
     for r in rows:
         print(f"{r['case']:28s} {r['kind']:9s} {r['us']:8.1f} us {r['MB']:7.1f} MB {r['TBps']:6.3f} TB/s", flush=True)
     if a.json:
-        with open(a.json, "w") as f:
-            json.dump(rows, f, indent=1)
+        emit(rows, a.json)
 
 
 if __name__ == "__main__":

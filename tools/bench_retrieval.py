@@ -9,39 +9,22 @@ Every bank size runs in a process of its own under a time limit of its own (--li
 out of time no further size is started.  Prints one JSON line per size (kept as profiles/retrieval_bench.json), times in
 milliseconds per call.  The M = 32768 bank of the default shape takes about 24 GB."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import harness
 
 
 def timed(fns, iters, warmup, reps=1):
-    """Milliseconds per call of each callable: warm-up, then `iters` rounds that alternate the callables, events around `reps`
-    back-to-back calls of one of them (short kernels: the events' own resolution is a few microseconds)."""
-    import torch
-    for _ in range(warmup):
-        for f in fns:
-            f()
-    torch.cuda.synchronize()
-    total = [0.0] * len(fns)
-    for _ in range(iters):
-        for i, f in enumerate(fns):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(reps):
-                f()
-            b.record()
-            b.synchronize()
-            total[i] += a.elapsed_time(b)
-    return [t / (iters * reps) for t in total]
+    """Milliseconds per call of each callable, the callables alternating (short kernels: reps back-to-back calls per bracket,
+    the events' own resolution is a few microseconds)."""
+    return [harness.summarize(s).mean for s in harness.alternating(fns, iters, warmup, reps)]
 
 
 def one_size(a, M):
     import torch
     from speech_decoding_amd import SpeechBank, retrieve, lib as L, ops
+    harness.need_gpu()
     from speech_decoding_amd.retrieval import _ScorePass, plan_blocks
     dev = "cuda:0"
     dt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[a.dtype]
@@ -54,8 +37,8 @@ def one_size(a, M):
     queries = torch.randn((N, F, T), generator=g, device=dev)
     for m0 in range(0, M, batch):
         Y = torch.randn((min(batch, M - m0), F, T), generator=g, device=dev)
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
+        s, e = harness.timing_event(), harness.timing_event()      # (behind the batch's randn on a busy stream, no drain in
+        s.record()                                                 # front: not a harness form, whose windows start idle)
         bank.add(Y)
         e.record()
         e.synchronize()
@@ -142,18 +125,14 @@ def main():
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        print(json.dumps(one_size(a, a.M[0])), flush=True)
+        harness.emit(one_size(a, a.M[0]))
         return 0
     for M in a.M:                                      # this process never opens the GPU: one fresh child per size
         cmd = [sys.executable, os.path.abspath(__file__), "--child", "--M", str(M), "--N", str(a.N), "--F", str(a.F), "--T", str(a.T),
                "--dtype", a.dtype, "--k", str(a.k), "--iters", str(a.iters), "--warmup", str(a.warmup), "--scratch", str(a.scratch)]
-        try:
-            rc = subprocess.run(cmd, timeout=a.limit).returncode
-        except subprocess.TimeoutExpired:
-            print(json.dumps({"bench": "retrieval", "M": M, "error": f"time limit of {a.limit} s"}), flush=True)
-            return 1
-        if rc != 0:
-            print(json.dumps({"bench": "retrieval", "M": M, "error": f"exit status {rc}"}), flush=True)
+        status = harness.run_child(cmd, a.limit)
+        if status != 0:                                # the sweep ends here: nothing is started after a child that ended badly
+            harness.emit({"bench": "retrieval", "M": M, "error": harness.child_error(status, a.limit)})
             return 1
     return 0
 

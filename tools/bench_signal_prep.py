@@ -9,32 +9,17 @@ Device events after warm-up; every line is one JSON object, printed and appended
 profiles/signal_prep_bench.json), times in milliseconds per call.  "useful" FLOP = 2 rows L K: the taps, not the zeros the
 grouped matrix adds.  The share of peak is against the 157.3 TFLOP/s fp32 matrix rate, which bounds this kernel."""
 import argparse
-import json
-import os
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import harness
 
 FP32_MATRIX_PEAK_TF = 157.3
 LINES = ("filter", "conv1d", "cpu", "audio", "brain")
 
 
 def timed(fn, iters, warmup):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return sum(ms) / len(ms), min(ms), max(ms)
+    """every call between its own pair of events: (mean, min, max) in ms"""
+    s = harness.summarize(harness.alternating((fn,), iters, warmup)[0])
+    return s.mean, s.min, s.max
 
 
 def padded_recording(rows, n, K, seed=0):
@@ -60,8 +45,7 @@ def main():
     import numpy as np
     import torch
     from speech_decoding_amd import signal_prep as SP
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_signal_prep needs the GPU: nothing is measured without one")
+    harness.need_gpu()
     rows, n = a.rows, a.samples
     taps = SP.bandpass_taps(1000, 1.0, 60)
     K = len(taps)
@@ -69,11 +53,7 @@ def main():
     base = {"bench": "signal_prep", "rows": rows, "samples": n, "taps": K, "iters": a.iters, "warmup": a.warmup}
 
     def emit(rec):
-        line = json.dumps(dict(base, **rec))
-        print(line, flush=True)
-        if a.out:
-            with open(a.out, "a") as f:
-                f.write(line + "\n")
+        harness.emit(dict(base, **rec), a.out, append=True)
 
     x, xp = padded_recording(rows, n, K)
     h32 = torch.from_numpy(taps.astype(np.float32)).to("cuda:0")
@@ -122,12 +102,7 @@ def main():
         def run():
             with ThreadPoolExecutor(threads) as ex:
                 return list(ex.map(lambda idx: oaconvolve(xh[idx], taps[None, :], mode="valid", axes=-1), [p for p in parts if len(p)]))
-        run()
-        t0 = time.perf_counter()
-        reps = 2
-        for _ in range(reps):
-            run()
-        ms = (time.perf_counter() - t0) / reps * 1e3
+        ms = harness.host_clock(run, 2, 1)[1]
         emit({"line": "cpu_oaconvolve", "what": "scipy.signal.oaconvolve, float64, 16 threads over the rows, host clock", "threads": threads,
               "ms": round(ms, 1), "useful_tflops": round(flop / (ms * 1e-3) / 1e12, 3)})
     if "audio" in a.only:

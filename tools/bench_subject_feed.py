@@ -9,30 +9,17 @@ Prints microseconds and achieved bytes/s per stage (bytes = the compulsory traff
 statistics, one read and one write for the scaling, one read and one write of the batch for the gather) and one JSON line.
 No threshold: nobody had measured these when the path was written."""
 import argparse
-import json
-import os
-import sys
 import time
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import harness
+from speech_decoding_amd import collate
 
-from speech_decoding_amd import collate                     # noqa: E402
 
-
-def time_us(fn, iters, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(iters):
-        fn()
-    end.record()
-    torch.cuda.synchronize()
-    return start.elapsed_time(end) * 1e3 / iters
+def time_us(fn, iters):
+    return harness.us(harness.window(fn, iters, 3))
 
 
 def main():
@@ -45,6 +32,7 @@ def main():
     ap.add_argument("--host-baseline", action="store_true", help="also time sklearn's RobustScaler on the host")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    harness.need_gpu()
     dev = torch.device("cuda", 0)
     S, C, Ln, T = a.subjects, a.channels, a.length // a.seg * a.seg, a.seg
     g = torch.Generator().manual_seed(0)
@@ -84,10 +72,7 @@ def main():
         tag = f"subject_wise={r['subject_wise']}" if "subject_wise" in r else f"B={r['B']} T={r['T']}"
         print(f"{r['stage']:32s} {tag:20s} {r['us']:12.1f} us {rate}")
     result = {"shape": [S, C, Ln], "device": torch.cuda.get_device_name(0), "rows": rows}
-    print(json.dumps(result))
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(result, f, indent=1)
+    harness.emit(result, a.out)
 
 
 if __name__ == "__main__":

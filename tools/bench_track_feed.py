@@ -13,15 +13,12 @@ two series of ONE kernel, and the margin the comparison gets.  feed.batch() in b
 call and a device synchronise (collate of X, index upload and the gather; the two forms alternate as well).  Bytes are the
 compulsory traffic computed from shapes below; the share is of the 8 TB/s HBM3E rate.  Needs the GPU: there is no fallback."""
 import argparse
-import json
-import os
-import sys
-import time
+import itertools
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import harness
 
 HBM_BYTES_PER_S = 8.0e12
 ROW_PAD = 16
@@ -38,9 +35,9 @@ def gather_samples_bytes(B, T, rows_alloc, row_bytes):
     return B * (T + ROW_PAD) * row_bytes, (B * (T + ROW_PAD) + B * ROW_PAD + (rows_alloc - B * (T + ROW_PAD))) * row_bytes
 
 
-def stats(us):
-    us = np.asarray(us, dtype=np.float64)
-    return {"mean_us": float(us.mean()), "median_us": float(np.median(us)), "min_us": float(us.min()), "max_us": float(us.max()), "calls": int(us.size)}
+def stats(ms):
+    s = harness.us(harness.summarize(ms))
+    return {"mean_us": s.mean, "median_us": s.median, "min_us": s.min, "max_us": s.max, "calls": s.n}
 
 
 def main():
@@ -55,8 +52,7 @@ def main():
     a = ap.parse_args()
     if a.iters < 20:
         raise SystemExit("bench_track_feed: --iters must be at least 20")
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_track_feed: needs the MI355X (nothing is timed without the GPU)")
+    harness.need_gpu()
     from speech_decoding_amd import lib as L, load_config, ops
     from speech_decoding_amd.data import ResidentSegmentFeed, synthetic_track_dataset
     dev = torch.device("cuda", 0)
@@ -105,33 +101,18 @@ def main():
     torch.cuda.synchronize()
     assert torch.equal(dst_w.view(torch.int16), dst_s.view(torch.int16))        # the two paths hand the loss the same bytes
 
-    series = {"reference_A": [], "gather_windows": [], "reference_B": []}
-    order = [("reference_A", reference), ("gather_windows", new), ("reference_B", reference)]
-    events = []
-    for it in range(a.warmup + a.iters):
-        for k, (name, fn) in enumerate(order):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn(dev_idx[(3 * it + k) % len(dev_idx)])
-            e1.record()
-            if it >= a.warmup:
-                events.append((name, e0, e1))
-    torch.cuda.synchronize()
-    for name, e0, e1 in events:
-        series[name].append(e0.elapsed_time(e1) * 1e3)
+    # A / new / A again, every call on the next of the index sets, the GPU kept fed (the brackets are read at the end)
+    idx = itertools.cycle(dev_idx)
+    order = [lambda: reference(next(idx)), lambda: new(next(idx)), lambda: reference(next(idx))]
+    series = dict(zip(("reference_A", "gather_windows", "reference_B"), harness.alternating(order, a.iters, a.warmup, sync_each=False)))
 
-    def batch_us(f, idx):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        f.batch(idx)
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e6
-    feed_us = {"tracks": [], "materialised": []}
+    # feed.batch() ends in the host's wait for its batch: the host's clock around every single call, the two feeds taking turns
+    feed_ms = {"tracks": [], "materialised": []}
     for it in range(a.warmup + a.iters):
         for name, f in (("tracks", feed), ("materialised", mat)):
-            us = batch_us(f, host_idx[it % len(host_idx)])
+            ms = harness.host_clock(lambda: f.batch(host_idx[it % len(host_idx)]), 1, 0)[1]
             if it >= a.warmup:
-                feed_us[name].append(us)
+                feed_ms[name].append(ms)
 
     rd_w, wr_w = gather_windows_bytes(B, T, rows, row_bytes)
     rd_s, wr_s = gather_samples_bytes(B, T, rows, row_bytes)
@@ -149,7 +130,7 @@ def main():
         "aa_spread": spread,
         "new_over_reference": W["mean_us"] / ref_mean,
         "inside_margin": bool(W["mean_us"] <= ref_mean * (1.0 + spread)),
-        "feed_batch": {k: stats(v) for k, v in feed_us.items()},
+        "feed_batch": {k: stats(v) for k, v in feed_ms.items()},
         "resident_bytes": {"tracks": int(bank.nbytes),
                            "materialised": {"packed_table": int(table_m.numel() * 2), "segments_fp32": int(Y32.numel() * 4)}},
     }
@@ -161,11 +142,7 @@ def main():
     for k, v in result["feed_batch"].items():
         print(f"feed.batch() {k:13s} {v['mean_us']:9.1f} us mean ({v['median_us']:.1f} median)")
     print(f"resident: tracks {bank.nbytes / 1e9:.3f} GB; materialised {table_m.numel() * 2 / 1e9:.3f} GB packed + {Y32.numel() * 4 / 1e9:.3f} GB fp32")
-    print(json.dumps(result))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(result, f, indent=1)
+    harness.emit(result, a.out)
 
 
 if __name__ == "__main__":

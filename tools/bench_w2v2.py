@@ -13,13 +13,10 @@ the 8 TB/s HBM rate (MI355X data sheet).  When `transformers` is importable, the
 through the reference's chunked last-four mean, alternating call by call with `embed()`.  Every line is one JSON object,
 printed and appended to --out (kept as profiles/w2v2_variants_bench.json)."""
 import argparse
-import json
-import os
-import sys
-import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+
+import harness
 from speech_decoding_amd import ops
 from speech_decoding_amd.wav2vec2 import Wav2Vec2Config, Wav2Vec2Embedder, chunk_bounds
 
@@ -66,29 +63,25 @@ def gemm_flop_per_frame(cfg):
             + 2 * C * H + 2 * C * C * conv)
 
 
+def mean_min_max(ms, digits):
+    s = harness.summarize(ms)
+    return {"ms": round(s.mean, digits), "min_ms": round(s.min, digits), "max_ms": round(s.max, digits)}
+
+
 def timed(fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(); fn(); b.record(); b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return {"ms": round(sum(ms) / len(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
+    """every call between its own pair of events"""
+    return mean_min_max(harness.alternating((fn,), iters, warmup)[0], 4)
 
 
 def timed_pair(fa, fb, iters, warmup):
     """fa and fb alternating call by call, wall clock around a device synchronisation: (ms of fa, ms of fb)"""
     for _ in range(warmup):
         fa(); fb()
-    torch.cuda.synchronize()
     ms = ([], [])
     for _ in range(iters):
         for k, fn in enumerate((fa, fb)):
-            t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
-            ms[k].append((time.perf_counter() - t0) * 1e3)
-    return tuple({"ms": round(sum(m) / len(m), 3), "min_ms": round(min(m), 3), "max_ms": round(max(m), 3)} for m in ms)
+            ms[k].append(harness.host_clock(fn, 1, 0)[1])
+    return tuple(mean_min_max(m, 3) for m in ms)
 
 
 def hf_model(cfg, sd, dtype):
@@ -127,12 +120,10 @@ def main():
     dtype = dict(bf16=torch.bfloat16, fp16=torch.float16, fp32=torch.float32)[a.dtype]
     es = 4 if dtype == torch.float32 else 2
 
+    harness.need_gpu()
+
     def emit(rec):
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if a.out:
-            with open(a.out, "a") as f:
-                f.write(line + "\n")
+        harness.emit(rec, a.out, append=True)
 
     for name in a.variants:
         cfg = Wav2Vec2Config(**VARIANTS[name])
@@ -143,11 +134,9 @@ def main():
         base = {"bench": "w2v2", "variant": name, "dtype": a.dtype, "seconds": secs, "samples": wave.shape[1],
                 "feat_extract_norm": cfg.feat_extract_norm, "do_stable_layer_norm": cfg.do_stable_layer_norm,
                 "hidden_size": cfg.hidden_size, "num_hidden_layers": cfg.num_hidden_layers}
-        for _ in range(2): out = emb.embed(wave)
-        torch.cuda.synchronize(); t0 = time.perf_counter()
         n = 3
-        for _ in range(n): out = emb.embed(wave)
-        torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / n
+        dt = harness.host_clock(lambda: emb.embed(wave), n, 2)[1] * 1e-3
+        out = emb.embed(wave)
         frames = out.shape[1]
         flop = frames * gemm_flop_per_frame(cfg)
         print(f"{name}: {secs:.0f} s of audio, {frames} frames, {str(dtype)[6:]}: {dt * 1e3:.1f} ms per call = {secs / dt:.0f} x real time, "

@@ -10,37 +10,19 @@ candidates of the default shape would take 101 GB), the point is that it runs.  
 time limit of its own (--limit seconds); after a size that fails or runs out of time no further size is started.  Prints one
 JSON line per size and keeps them in --out (profiles/window_bank_bench.json), times in milliseconds per call."""
 import argparse
-import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import harness
 
 
 def timed(fns, iters, warmup):
-    """Per callable (mean, standard deviation, min, max) in milliseconds of `iters` calls, each between its own pair of events;
-    the callables alternate call by call, after `warmup` rounds of all of them."""
-    import torch
-    for _ in range(warmup):
-        for f in fns:
-            f()
-    torch.cuda.synchronize()
-    ms = [[] for _ in fns]
-    for _ in range(iters):
-        for i, f in enumerate(fns):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            f()
-            b.record()
-            b.synchronize()
-            ms[i].append(a.elapsed_time(b))
+    """Per callable (mean, standard deviation, min, max) in milliseconds of `iters` calls, the callables alternating call by call."""
     out = []
-    for v in ms:
-        mean = sum(v) / len(v)
-        out.append({"mean": round(mean, 3), "std": round((sum((x - mean) ** 2 for x in v) / len(v)) ** 0.5, 3),
-                    "min": round(min(v), 3), "max": round(max(v), 3)})
+    for v in harness.alternating(fns, iters, warmup):
+        s = harness.summarize(v)
+        out.append({"mean": round(s.mean, 3), "std": round((sum((x - s.mean) ** 2 for x in v) / s.n) ** 0.5, 3),
+                    "min": round(s.min, 3), "max": round(s.max, 3)})
     return out
 
 
@@ -49,6 +31,7 @@ def one_size(a, M, hop, rows, with_speech_bank):
     import torch
     from speech_decoding_amd import SpeechBank, WindowBank, retrieve, lib as L
     from speech_decoding_amd.retrieval import _ScorePass, plan_blocks
+    harness.need_gpu()
     dev = "cuda:0"
     dt = {"bf16": torch.bfloat16, "fp16": torch.float16}[a.dtype]
     N, F, T, k = a.N, a.F, a.T, a.k
@@ -118,12 +101,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scratch", type=int, default=1 << 30)
     ap.add_argument("--limit", type=int, default=420, help="seconds one size may take")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "window_bank_bench.json"))
+    ap.add_argument("--out", default=os.path.join(harness.ROOT, "profiles", "window_bank_bench.json"))
     ap.add_argument("--child", nargs=4, type=int, metavar=("M", "HOP", "ROWS", "SPEECH"), help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
         M, hop, rows, speech = a.child
-        print(json.dumps(one_size(a, M, hop, rows, bool(speech))), flush=True)
+        harness.emit(one_size(a, M, hop, rows, bool(speech)))
         return 0
     sizes = [(M, a.hop, (M - 1) * a.hop + a.T, 1) for M in a.M]
     if a.dense_M:
@@ -133,17 +116,13 @@ def main():
     for size in sizes:                                 # this process never opens the GPU: one fresh child per size
         cmd = [sys.executable, os.path.abspath(__file__), "--child", *map(str, size), "--N", str(a.N), "--F", str(a.F), "--T", str(a.T),
                "--dtype", a.dtype, "--k", str(a.k), "--iters", str(a.iters), "--warmup", str(a.warmup), "--scratch", str(a.scratch)]
-        try:
-            done = subprocess.run(cmd, timeout=a.limit, stdout=subprocess.PIPE, text=True)
-        except subprocess.TimeoutExpired:
-            print(json.dumps({"bench": "window_bank", "M": size[0], "error": f"time limit of {a.limit} s"}), flush=True)
+        said = []
+        status = harness.run_child(cmd, a.limit, lines=said)
+        if status != 0:                                # the sweep ends here: nothing is started after a child that ended badly
+            harness.emit({"bench": "window_bank", "M": size[0], "error": harness.child_error(status, a.limit)})
             return 1
-        if done.returncode != 0:
-            print(json.dumps({"bench": "window_bank", "M": size[0], "error": f"exit status {done.returncode}"}), flush=True)
-            return 1
-        line = done.stdout.strip().splitlines()[-1]
-        print(line, flush=True)
-        lines.append(line)
+        print(said[-1], flush=True)
+        lines.append(said[-1])
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
     return 0

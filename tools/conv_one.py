@@ -1,11 +1,17 @@
-"""Run one conv_gemm / wgrad_gemm configuration a few times (for rocprofv3 counter passes; diagnostic)."""
-import sys, os, math
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
+"""Run one conv_gemm / wgrad_gemm configuration a few times (for rocprofv3 counter passes; diagnostic).
+    [N=20] [DTYPE=fp32] python tools/conv_one.py [conv|wgrad] [cin cout KS dil] [flags]"""
+import math
+import os
+import sys
+
 import torch
-from speech_decoding_amd import ops
+
+from harness import need_gpu
+from speech_decoding_amd import layers, ops
+
 
 def main():
+    need_gpu()
     what = sys.argv[1] if len(sys.argv) > 1 else "conv"
     cin, cout, KS, dil = (int(v) for v in (sys.argv[2:6] if len(sys.argv) > 5 else (320, 320, 3, 4)))
     flags = int(sys.argv[6]) if len(sys.argv) > 6 else 0
@@ -23,12 +29,13 @@ def main():
             ops.conv_gemm(x, wp, y, B=B, T=T, KS=KS, dil=dil, bias=bias, res=res, stats=stats, flags=flags)
     else:
         dy = ops.new_rows(B, T, cout, dtype, dev); dy.normal_()
-        nseg = int(os.environ.get("NSEG", 24))
-        seg = torch.from_numpy(np.floor(np.linspace(0, B, nseg + 1)).astype(np.int32)).to(dev)
+        nseg = layers.uniform_nseg(B, cout, cin)              # the step's own plan
+        seg = torch.from_numpy(layers.uniform_segment_edges(B, nseg)).to(dev)
         perm = torch.arange(B, dtype=torch.int32, device=dev)
         for _ in range(n):
             ops.wgrad_gemm(dy, x, B=B, T=T, KS=KS, dil=dil, perm=perm, seg_start=seg, nseg=nseg)
     torch.cuda.synchronize()
+
 
 if __name__ == "__main__":
     main()

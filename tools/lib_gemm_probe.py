@@ -4,19 +4,9 @@ Gives a yardstick for the hand-written kernels: the k=3 conv as an im2col GEMM (
 handed the unfolded operand for free, which the conv kernels never materialise), its weight gradient (3*Cin x rows @ rows x Cout),
 the two 1x1 projections.  Prints microseconds, TFLOP/s and the kernel the library chose (macro tile in its name).
 """
-import sys, os
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-
-def timeit(fn, n=20, warm=5):
-    for _ in range(warm): fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n): fn()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3
+from harness import need_gpu, us, window
 
 
 def kernel_name(fn):
@@ -28,6 +18,7 @@ def kernel_name(fn):
 
 
 def main():
+    need_gpu()
     dev, dt = "cuda:0", torch.bfloat16
     R = 256 * 360
     shapes = [("k=3 conv 320->320 as im2col GEMM", R, 320, 960, "nn"), ("k=3 conv 320->640", R, 640, 960, "nn"),
@@ -40,8 +31,8 @@ def main():
         else:
             A = torch.randn(K, M, device=dev, dtype=dt); B = torch.randn(K, N, device=dev, dtype=dt)
             fn = lambda: torch.matmul(A.t(), B)
-        us = timeit(fn)
-        print(f"{name:36s} M={M:6d} N={N:5d} K={K:6d} {us:7.1f} us {2.0 * M * N * K / us / 1e6:7.1f} TFLOP/s  {kernel_name(fn)}", flush=True)
+        t = us(window(fn, 20, 5))
+        print(f"{name:36s} M={M:6d} N={N:5d} K={K:6d} {t:7.1f} us {2.0 * M * N * K / t / 1e6:7.1f} TFLOP/s  {kernel_name(fn)}", flush=True)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,8 @@
 # Diagnostic: loss-stage micro-benchmarks (tools/bench_loss.py) for library variants under variants/: bash tools/probes/ab_loss_lib.sh a b
-cd $GRAFT_REPO_ROOT
+# (every run under its own time limit; the first failure ends the script)
+. "$(dirname "$0")/libswap.sh"
 for V in "$@" "$@"; do
-  cp variants/libsdamd_$V.so speech_decoding_amd/libsdamd.so
-  echo "== $V"; timeout -k 10 100 python tools/bench_loss.py 2>/dev/null | grep -E "Bm=|sim gemm|dZ gemm"
+  use_lib "$V"
+  OUT=$(timeout -k 10 100 python tools/bench_loss.py 2>/dev/null)
+  echo "== $V"; echo "$OUT" | grep -E "Bm=|sim gemm|dZ gemm"
 done

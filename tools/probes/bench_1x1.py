@@ -1,22 +1,14 @@
 """The row-layout 1 x 1 convs of the config-2 step alone (f1, f2 forward; their data gradients) on each tiling.
 Diagnostic, not part of the product."""
-import sys, os, math
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+import math, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # tools/: the harness
+from harness import need_gpu, us, window
 import torch
 from speech_decoding_amd import ops, lib as L
 
 
-def timeit(fn, n=20, warm=3):
-    for _ in range(warm): fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n): fn()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / n * 1e3
-
-
 def main():
+    need_gpu()
     dev, dt = "cuda:0", torch.bfloat16
     B, T = 256, 360
     for (name, cin, cout, fwd) in [("f1 fwd", 320, 640, True), ("f2 fwd", 640, 1024, True), ("f2 dgrad", 1024, 640, False),
@@ -38,9 +30,9 @@ def main():
         for vn, kw in [("full", full), ("plain", dict()),
                        ("flat", dict(flags=L.CONV_FLAT_TILES, **fullf)), ("flat_plain", dict(flags=L.CONV_FLAT_TILES)),
                        ("flat_1percu", dict(flags=L.CONV_FLAT_TILES | L.CONV_ONE_PER_CU, **fullf))]:
-            us = timeit(lambda: ops.conv_gemm(x, wp, y, B=B, T=T, KS=1, dil=0, **kw))
-            print(f"{name:9s} {cin:4d}->{cout:4d} {vn:8s} {us:7.1f} us  {fl / us / 1e6:6.1f} TF  (reads {rd:.0f} MB, writes {wr:.0f} MB"
-                  f" -> {(rd + wr) / us:.2f} TB/s)", flush=True)
+            t = us(window(lambda: ops.conv_gemm(x, wp, y, B=B, T=T, KS=1, dil=0, **kw), 20, 3))
+            print(f"{name:9s} {cin:4d}->{cout:4d} {vn:8s} {t:7.1f} us  {fl / t / 1e6:6.1f} TF  (reads {rd:.0f} MB, writes {wr:.0f} MB"
+                  f" -> {(rd + wr) / t:.2f} TB/s)", flush=True)
 
 
 if __name__ == "__main__":
