@@ -42,7 +42,9 @@ extern "C" {
                                   sda_conv_tile_co / sda_wgrad_tile_m — the output-channel tile rules, asked instead of mirrored;
                                   sda_sim_gemm_windows / sda_sim_gemm_windows_span / sda_window_sumsq — decoding against windows of
                                   continuous speech tracks;
-                                  sda_gather_windows — training batches gathered from such tracks) */
+                                  sda_gather_windows — training batches gathered from such tracks;
+                                  sda_lagged_cov_f32 / sda_lagged_cov_slices / sda_lagged_cov_scratch_floats — the lag products of the
+                                  time-lagged ridge baseline) */
 #define SDA_ROW_PAD 16
 #define SDA_CH_ALIGN 64
 
@@ -730,6 +732,24 @@ int sda_grad_guard_finish(const double* partials, int n, int gx, double* state, 
  * fl32(grad * (float)state[COEF]) with the bias corrections read from state.  The stored gradients are not modified. */
 int sda_adam_multi_guarded(const sda_adam_desc* descs, int n, long max_n, float lr, float beta1, float beta2, float eps,
                            const double* state, void* stream);
+
+/* ---- Lag products of a time-lagged ridge regression (ABI 4, addition): the normal equations of the backward mTRF, the linear
+ * decoding baseline (mne.decoding.TimeDelayingRidge, edge_correction=False), csrc/lagged_cov.hip:
+ *     out[s][d][i][j] = sum_{r in row slice s} a[r + d][i] * b[r][j],     d < L, i < Ap, j < Bp
+ * fp32 in and out, exact-fp32 MFMA (per output a k-ordered fmaf chain over the slice's rows).  Lag layout: a and b are `rows` rows
+ * of a_pitch / b_pitch floats, channels-last, of which the first Ap / Bp are read (the channel counts padded to 64, pad channels
+ * zero); sample n of a (B, C, T) tensor owns rows n (T + H) ... n (T + H) + T - 1 and H >= L - 1 zero rows follow it, so a lagged
+ * row that leaves its sample reads zeros and nothing is masked per sample.  rows = B (T + H).  Rows >= rows are never read and count
+ * as zero.  a = b gives the Gram blocks A_d, a = x, b = y the cross products R_l.  The rows are cut into
+ * sda_lagged_cov_slices(rows, L, Ap, Bp) slices, a number that depends on these four alone; slice s writes every element of slab s
+ * of out = [slices][L][Ap][Bp] (sda_lagged_cov_scratch_floats floats) and the caller sums the slabs in fixed order
+ * (sda_reduce_slabs, or in double).  No atomics: the same bits on every call.  Null pointers, non-positive sizes, Ap or Bp not a
+ * multiple of 64, a pitch smaller than its width or not a multiple of 4, operands not 16-byte aligned and L - 1 > H return -1
+ * (sda_last_error) and launch nothing; the two size functions return -1 the same way. */
+int sda_lagged_cov_slices(long rows, int L, int Ap, int Bp);
+long sda_lagged_cov_scratch_floats(long rows, int L, int Ap, int Bp);
+int sda_lagged_cov_f32(const float* a, long a_pitch, const float* b, long b_pitch, long rows, int L, int H, int Ap, int Bp,
+                       float* out, void* stream);
 
 #ifdef __cplusplus
 }

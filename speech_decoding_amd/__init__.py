@@ -7,5 +7,6 @@ from .retrieval import SpeechBank, WindowBank, Retrieval, retrieve, ClassIndex, 
 from .config import Config, load_config                   # noqa: F401
 from .data import ResidentSubjectFeed                     # noqa: F401
 from .signal_prep import mel_spectrogram, log_mel, mel_embeddings   # noqa: F401
+from .ridge import LaggedRidge                            # noqa: F401
 
-__all__ = ["BrainEncoder", "Classifier", "CLIPLoss", "MSELoss", "SpeechBank", "WindowBank", "Retrieval", "retrieve", "ClassIndex", "ClassRetrieval", "retrieve_classes", "ResidentSubjectFeed", "mel_spectrogram", "log_mel", "mel_embeddings", "torch_exp", "torch_log", "Config", "load_config", "load_library", "SdaError"]
+__all__ = ["BrainEncoder", "Classifier", "CLIPLoss", "MSELoss", "SpeechBank", "WindowBank", "Retrieval", "retrieve", "ClassIndex", "ClassRetrieval", "retrieve_classes", "ResidentSubjectFeed", "mel_spectrogram", "log_mel", "mel_embeddings", "LaggedRidge", "torch_exp", "torch_log", "Config", "load_config", "load_library", "SdaError"]

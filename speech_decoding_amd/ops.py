@@ -1284,6 +1284,39 @@ def stft_fft(rows_padded: torch.Tensor, window: torch.Tensor, twiddle: torch.Ten
     return out
 
 
+# ---- lag products of the time-lagged ridge baseline (csrc/lagged_cov.hip) ----
+def lagged_cov_slices(rows: int, n_lags: int, Ap: int, Bp: int) -> int:
+    """Row slices (= slabs) `lagged_cov` writes for this shape: `sda_lagged_cov_slices`, a function of the four numbers alone."""
+    n = int(L.load().sda_lagged_cov_slices(int(rows), int(n_lags), int(Ap), int(Bp)))
+    if n < 0:
+        L.check(-1, "lagged_cov_slices")
+    return n
+
+
+def lagged_cov(a: torch.Tensor, b: torch.Tensor, n_lags: int, H: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`sda_lagged_cov_f32`: a (rows, Ap) and b (rows, Bp) fp32 lag-layout buffers (rows of channels, pad channels zero, H >=
+    n_lags - 1 zero rows behind every sample; a row stride wider than the width is taken as the pitch) -> the slabs
+    (slices, n_lags, Ap, Bp) fp32, slab[s][d][i][j] = sum over the rows r of slice s of a[r + d][i] b[r][j].  Every element is
+    written; the caller sums the slabs in fixed order (`reduce_slabs`, or in double).  `out`: a contiguous fp32 tensor to write
+    them into instead of a new one."""
+    _need_cuda(a, b, out)
+    for t in (a, b):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+            raise L.SdaError("lagged_cov: a and b are fp32 (rows, channels) device tensors with unit-stride channels")
+    if a.shape[0] != b.shape[0]:
+        raise L.SdaError(f"lagged_cov: a has {a.shape[0]} rows, b {b.shape[0]}")
+    rows, Ap, Bp, n_lags = a.shape[0], a.shape[1], b.shape[1], int(n_lags)
+    shape = (lagged_cov_slices(rows, n_lags, Ap, Bp), n_lags, Ap, Bp)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=a.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != shape:
+        raise L.SdaError(f"lagged_cov: out must be a contiguous fp32 tensor of shape {shape}")
+    with torch.cuda.device(a.device):
+        L.check(L.load().sda_lagged_cov_f32(_p(a), a.stride(0), _p(b), b.stride(0), rows, n_lags, int(H), Ap, Bp, _p(out), _st()),
+                "lagged_cov")
+    return out
+
+
 # ---- gradient guard (csrc/grad_guard.hip, csrc/param_ops.hip): three launches over Adam's descriptor table, no read-back ----
 def grad_guard_parts(n: int, max_n: int) -> int:
     """Doubles `grad_sumsq_multi` writes for n tensors of at most max_n elements: 2 n gx, gx = min(ceil(max_n / 1024), 256)."""
