@@ -44,7 +44,8 @@ extern "C" {
                                   continuous speech tracks;
                                   sda_gather_windows — training batches gathered from such tracks;
                                   sda_lagged_cov_f32 / sda_lagged_cov_slices / sda_lagged_cov_scratch_floats — the lag products of the
-                                  time-lagged ridge baseline) */
+                                  time-lagged ridge baseline;
+                                  sda_conv_kernel — which kernel sda_conv_gemm routes a convolution to, asked instead of mirrored) */
 #define SDA_ROW_PAD 16
 #define SDA_CH_ALIGN 64
 
@@ -66,9 +67,12 @@ enum { SDA_EPI_GELU = 1,
        SDA_CONV_ONE_PER_CU = 32768, /* with SDA_CONV_FLAT_TILES: at most one workgroup per CU (half the LDS stays free) */
        SDA_CONV_FLAT_TILES = 16384, /* kernel size 3 with Cout_p % 160 == 0: 256-row x 160-channel tiles cut from the
                                        flat row space, two workgroups per CU (conv3_flat.hip); kernel size 1 with
-                                       Cout_p % 160 == 0 or Cout_p % 128 == 0, shared weights, no residual / statistics:
-                                       the same tiling (conv1_flat.hip); other shapes ignore the flag.  `stats` then has
-                                       sda_conv_stats_rows(...) rows instead of B * n_t_tiles */
+                                       Cout_p % 160 == 0 or Cout_p % 128 == 0: the same tiling (conv1_flat.hip).  Other shapes
+                                       ignore the flag (sda_conv_kernel tells), and so does a kernel-size-1 launch that writes no
+                                       statistics and is not a plain row-layout convolution with shared weights and no residual;
+                                       one that writes statistics (SDA_EPI_GELU_BWD, SDA_EPI_ROW_SUMSQ, `stats`) is refused there,
+                                       never served by a kernel with another row count.  `stats` has sda_conv_stats_rows(...)
+                                       rows: those of the kernel that runs */
        SDA_CONV_FLAT_STAGGER = 1024,/* with SDA_CONV_FLAT_TILES, kernel size 3 (conv3_flat.hip): the second workgroup of a CU takes its
                                        128-row tile(s) first and its 256-row tiles after them, the first workgroup the other way
                                        round, so that the two reach their epilogues at different times.  Same results either way;
@@ -80,9 +84,11 @@ enum { SDA_EPI_GELU = 1,
                                        flag is an error, not a fallback */
        SDA_CONV_WAVE_PRIO = 1048576,/* the tile-per-workgroup kernels: the launch's waves run at s_setprio 3 (they win a SIMD's issue
                                        arbitration against co-resident waves of other kernels) */
-       SDA_EPI_GELU_BWD = 65536,    /* kernel size 1 (flat tiles or one tile per workgroup): the conv's output is the gradient entering a GELU whose input u = bn_x ([rows][Cout_p],
+       SDA_EPI_GELU_BWD = 65536,    /* kernel size 1 (any of its kernels): the conv's output is the gradient entering a GELU whose input u = bn_x ([rows][Cout_p],
                                        same layout as y) the forward kept: y = round(conv) * GELU'(u) (what sda_gelu_backward_colsum
-                                       computes from the stored gradient), `stats` rows (sda_conv_stats_rows) = per-unit column
+                                       computes from the stored gradient), `stats` rows (sda_conv_stats_rows: one per unit of the kernel
+                                       the flags and the width route to — with SDA_CONV_FLAT_TILES and a Cout_p that divides by neither
+                                       160 nor 128 that is the tile-per-workgroup kernel, B * n_t_tiles rows) = per-unit column
                                        sums of the products in plane 0 (the bias gradient of the layer that fed the GELU), plane 1
                                        zero.  No bias / y_pre / SDA_EPI_GELU */
        SDA_EPI_BN_STORE_DG = 262144,/* with bn_x (the BatchNorm-backward statistics epilogue): y = dg = round(dy) * GELU'(gamma * xhat + beta),
@@ -204,10 +210,16 @@ typedef struct sda_conv_args {
 int sda_conv_gemm(const sda_conv_args* a, void* stream);
 int sda_conv_n_t_tiles(int T);
 /* output-channel tile (160 / 128 / 64) of the tile-per-workgroup kernels for Cout_p channels, kernel size KS, with or without a
- * `stats` buffer: what sda_conv_gemm dispatches on when neither SDA_CONV_FLAT_TILES nor SDA_CONV_WIDE_TILES applies.  Host only. */
+ * `stats` buffer: what sda_conv_gemm dispatches on where sda_conv_kernel says SDA_CONV_KERNEL_TILE.  Host only. */
 int sda_conv_tile_co(int Cout_p, int KS, int has_stats);
-/* number of [2][Cout_p] rows of `stats` a launch with these parameters writes */
+/* number of [2][Cout_p] rows of `stats` a launch with these parameters writes: one per unit of the kernel sda_conv_kernel names
+ * (-1 where it refuses).  Host only. */
 int sda_conv_stats_rows(int B, int T, int KS, int Cout_p, int flags);
+/* the kernel sda_conv_gemm routes a convolution of kernel size KS and Cout_p output channels with these flags and storage type to:
+ * TILE = one 128-row tile per workgroup (conv_gemm.hip), FLAT3 / FLAT1 = conv3_flat.hip / conv1_flat.hip, WIDE = conv1_wide.hip;
+ * -1 (sda_last_error set) where the flags demand a kernel the shape or the storage type cannot have.  Host only. */
+enum { SDA_CONV_KERNEL_TILE = 0, SDA_CONV_KERNEL_FLAT3 = 1, SDA_CONV_KERNEL_FLAT1 = 2, SDA_CONV_KERNEL_WIDE = 3 };
+int sda_conv_kernel(int KS, int Cout_p, int flags, int dtype);
 
 /* BatchNorm1d (training statistics) over valid rows.
  * finalize: per-tile partial (sum, sumsq) -> mean/rstd, fused affine scale/shift, running-stat update

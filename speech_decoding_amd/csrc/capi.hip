@@ -37,6 +37,13 @@ bool first_use_on_device(unsigned long long& done) {
   return true;
 }
 
+int reserve_lds_once(unsigned long long& done, const void* kern, int lds, const char* what) {
+  if (!first_use_on_device(done)) return 0;
+  if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess) return 0;
+  set_error("%s: cannot reserve %d bytes of LDS", what, lds);
+  return -3;
+}
+
 static thread_local int g_cu_limit = 0;
 
 int launch_cus() {

@@ -23,7 +23,7 @@ namespace sda {
 
 namespace {
 
-constexpr int G_UNIT = 128;                          // rows per work unit
+// (G_UNIT = 128 rows per work unit: conv_tile.h, the route counts with it)
 constexpr int G_EP_ROWS = 64;
 
 template <int NREP> struct G1 {                      // geometry for NREP 16-channel fragments per wave
@@ -37,6 +37,7 @@ template <int NREP> struct G1 {                      // geometry for NREP 16-cha
   static constexpr int EP_BYTES = G_EP_ROWS * STRIDE * 4;
   static_assert(2 * LDS <= 160 * 1024, "two workgroups per CU");
 };
+static_assert(G1<5>::CO == G_CO[0] && G1<4>::CO == G_CO[1], "the channel tiles the route chooses between");
 template <int NREP, int CH> struct G1Epi {
   static constexpr int NCH = G1<NREP>::CO / CH;      // CH-channel chunks (16 bytes of E) per row
   static constexpr int RG = 256 / NCH;               // row groups
@@ -297,22 +298,9 @@ __global__ __launch_bounds__(256, 2) void conv1_flat_kernel(const sda_conv_args 
   c.nslab = a.Cin_p / (ROW_B / (int)sizeof(E));
   c.Tp = Tp;
   c.total_rows = total_rows;
-  // XCD-aware order (blocks i and i + 8 share an XCD/L2): the n_co workgroups that read the same input rows are dealt to the
-  // same XCD.  Pure speed: any placement is correct.
-  int bid = blockIdx.x, co_tile, run;
+  int co_tile, run;
   const int n_co = a.Cout_p / P::CO;
-  {
-    const int group = 8 * n_co, full = (int)(gridDim.x / group) * group;
-    if (bid < full) {
-      const int base = bid / group * group, rem = bid - base;
-      co_tile = rem / 8;
-      run = base / n_co + (rem & 7);
-    } else {
-      const int rem = bid - full;
-      co_tile = rem % n_co;
-      run = full / n_co + rem / n_co;
-    }
-  }
+  xcd_block_order(n_co, co_tile, run);
   c.co_tile = co_tile;
   c.n_co = n_co;
   c.co0 = co_tile * P::CO;
@@ -332,27 +320,16 @@ int launch_flat1(const sda_conv_args& a, hipStream_t st) {
   using P = G1<NREP>;
   static unsigned long long attr_done = 0;        // per device
   auto kern = conv1_flat_kernel<E, NREP, GB, RSQ>;
-  if (first_use_on_device(attr_done)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, P::LDS) != hipSuccess) {
-      set_error("conv1_flat: cannot reserve %d bytes of LDS", P::LDS);
-      return -3;
-    }
-  }
-  const long total_rows = (long)a.B * rows_tp(a.T);
-  const int n_units = (int)((total_rows + G_UNIT - 1) / G_UNIT);
-  const int n_co = a.Cout_p / P::CO;
-  const long slots = ((a.flags & SDA_CONV_ONE_PER_CU) ? 1L : 2L) * launch_cus();
-  int units_per_wg = (int)(((long)n_units * n_co + slots - 1) / slots);
-  if (units_per_wg < 1) units_per_wg = 1;
-  const int runs_per_co = (n_units + units_per_wg - 1) / units_per_wg;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(runs_per_co * n_co)), dim3(256), P::LDS, st, a, n_units, units_per_wg, total_rows, rows_tp(a.T));
+  if (const int rc = reserve_lds_once(attr_done, kern, P::LDS, "conv1_flat")) return rc;
+  const FlatPlan p = flat_plan(a, G_UNIT, P::CO);
+  hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(256), P::LDS, st, a, p.n_units, p.units_per_wg, (long)a.B * rows_tp(a.T), rows_tp(a.T));
   return check_launch("conv1_flat");
 }
 
-template <typename E> int launch_flat1_e(const sda_conv_args& a, hipStream_t st) {
+template <typename E> int launch_flat1_e(const sda_conv_args& a, hipStream_t st, bool co160) {
   if (a.flags & SDA_EPI_ROW_SUMSQ) return launch_flat1<E, 4, false, true>(a, st);
-  if (a.flags & SDA_EPI_GELU_BWD) return a.Cout_p % 160 == 0 ? launch_flat1<E, 5, true, false>(a, st) : launch_flat1<E, 4, true, false>(a, st);
-  return a.Cout_p % 160 == 0 ? launch_flat1<E, 5, false, false>(a, st) : launch_flat1<E, 4, false, false>(a, st);
+  if (a.flags & SDA_EPI_GELU_BWD) return co160 ? launch_flat1<E, 5, true, false>(a, st) : launch_flat1<E, 4, true, false>(a, st);
+  return co160 ? launch_flat1<E, 5, false, false>(a, st) : launch_flat1<E, 4, false, false>(a, st);
 }
 
 }  // namespace
@@ -360,18 +337,14 @@ template <typename E> int launch_flat1_e(const sda_conv_args& a, hipStream_t st)
 bool conv1_flat_supports(const sda_conv_args& a) {
   const bool gb = a.flags & SDA_EPI_GELU_BWD, rsq = a.flags & SDA_EPI_ROW_SUMSQ;
   if (gb && (rsq || !a.bn_x || !a.stats || a.bias || a.y_pre || (a.flags & SDA_EPI_GELU))) return false;
-  if (rsq && (!a.stats || a.Cout_p % 128)) return false;
+  if (rsq && !a.stats) return false;
   if (!gb && !rsq && (a.stats || a.bn_x)) return false;
-  return a.KS == 1 && (a.Cout_p % 160 == 0 || a.Cout_p % 128 == 0) && !a.widx && !a.res && a.ksplit == 1 && !a.partial && a.y &&
-         !(a.flags & (SDA_EPI_GLU | SDA_EPI_GLU_BWD)) && a.x_row0 == PAD && a.x_pitch == a.w_pitch && a.x_pitch == a.Cin_p &&
-         a.x_sample_rows == rows_tp(a.T) && a.x_rows_limit >= (long)a.B * rows_tp(a.T) + 3 * PAD && a.x_rows_limit < (1L << 31) &&
-         a.w_rows_limit >= a.Cout_p && (long)a.x_pitch * 16 * (a.dtype == SDA_F32 ? 4 : 2) < (1L << 31);
+  return !a.widx && !a.res && a.ksplit == 1 && !a.partial && a.y && !(a.flags & (SDA_EPI_GLU | SDA_EPI_GLU_BWD)) &&
+         a.x_pitch == a.Cin_p && plain_row_layout(a, 3 * PAD);
 }
 
-int launch_conv1_flat(const sda_conv_args& a, hipStream_t st) {
-  if (a.dtype == SDA_F32) return launch_flat1_e<float>(a, st);
-  if (a.dtype == SDA_F16) return launch_flat1_e<half_t>(a, st);
-  return launch_flat1_e<uint16_t>(a, st);
+int launch_conv1_flat(const sda_conv_args& a, hipStream_t st, int tile_co) {
+  SDA_DISPATCH(a.dtype, return launch_flat1_e<E>(a, st, tile_co == G1<5>::CO));
 }
 
 }  // namespace sda

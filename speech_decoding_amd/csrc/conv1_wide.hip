@@ -44,12 +44,13 @@ template <int AFR_, int BFR_, int WJ_, int WI_, int NS_> struct W1 {
   static constexpr int NPASS = (16 + RPP - 1) / RPP;
   static constexpr int PATCH = 16 * PB * 16 * 4;       // per wave: 16 rows x PB * 16 channels, fp32
   static constexpr int LDS = NS * STAGE + 8 * PATCH;
-  static_assert(TM == 256 && WJ * WI == 8, "eight waves, 256-row tiles");
+  static_assert(TM == W_UNIT && WJ * WI == 8, "eight waves, 256-row tiles");
   static_assert(LDS <= 160 * 1024, "one workgroup per CU");
   static_assert(8 * PATCH >= 8 * 64 * NBLK * 8 * 4, "the column-sum image reuses the patches");
 };
 using W1A = W1<8, 4, 2, 4, 4>;     // 256 channels: 32 KB stages, ring of 4
 using W1B = W1<5, 8, 4, 2, 3>;     // 320 channels: 36 KB stages, ring of 3
+static_assert(W1A::TN == W_CO[0] && W1B::TN == W_CO[1], "the channel tiles the route chooses between");
 
 // byte offset of 16-byte chunk `cidx` (4 floats) of patch row `row`: rows are PB * 64 bytes apart — for PB = 4 (256 B: every
 // row on the same banks) the chunk is XOR-ed with the row; for PB = 5 (320 B) rotated by row / 4: 16 rows, 16 distinct slots
@@ -334,12 +335,7 @@ template <typename E, typename P, int MODE, bool RSQ>
 int launch_wide(const sda_conv_args& a, hipStream_t st) {
   static unsigned long long attr_done = 0;        // per device
   auto kern = conv1_wide_kernel<E, P, MODE, RSQ>;
-  if (first_use_on_device(attr_done)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, P::LDS) != hipSuccess) {
-      set_error("conv1_wide: cannot reserve %d bytes of LDS", P::LDS);
-      return -3;
-    }
-  }
+  if (const int rc = reserve_lds_once(attr_done, kern, P::LDS, "conv1_wide")) return rc;
   const long total_rows = (long)a.B * rows_tp(a.T);
   const int n_row_tiles = (int)((total_rows + P::TM - 1) / P::TM);
   const int n_ch = a.Cout_p / P::TN;
@@ -352,36 +348,29 @@ int launch_wide(const sda_conv_args& a, hipStream_t st) {
   return check_launch("conv1_wide");
 }
 
-template <typename E> int launch_wide_e(const sda_conv_args& a, hipStream_t st) {
+template <typename E> int launch_wide_e(const sda_conv_args& a, hipStream_t st, int tile_co) {
   const bool gb = a.flags & SDA_EPI_GELU_BWD, rsq = a.flags & SDA_EPI_ROW_SUMSQ;
-  if (a.Cout_p % 256 == 0) {
+  if constexpr (sizeof(E) != 2) { set_error("conv1_wide: 16-bit storage only"); return -1; }      // (the route refuses fp32)
+  else if (tile_co == W1A::TN) {
     if (gb) return launch_wide<E, W1A, 1, false>(a, st);
     return rsq ? launch_wide<E, W1A, 0, true>(a, st) : launch_wide<E, W1A, 0, false>(a, st);
+  } else {
+    return gb ? launch_wide<E, W1B, 1, false>(a, st) : launch_wide<E, W1B, 0, false>(a, st);
   }
-  if (gb) return launch_wide<E, W1B, 1, false>(a, st);
-  return launch_wide<E, W1B, 0, false>(a, st);
 }
 
 }  // namespace
 
 bool conv1_wide_supports(const sda_conv_args& a) {
   const bool gb = a.flags & SDA_EPI_GELU_BWD, rsq = a.flags & SDA_EPI_ROW_SUMSQ;
-  if (a.KS != 1 || (a.dtype != SDA_BF16 && a.dtype != SDA_F16)) return false;
-  if (!(a.Cout_p % 256 == 0 || a.Cout_p % 320 == 0) || a.Cin_p % 32 != 0 || a.Cin_p < 32) return false;
-  if (rsq && (a.Cout_p % 256 != 0 || gb)) return false;
+  if (a.Cin_p % 32 != 0 || a.Cin_p < 32 || (rsq && gb)) return false;
   if (a.res || a.widx || a.partial || a.ksplit != 1 || !a.y || (a.flags & (SDA_EPI_GLU | SDA_EPI_GLU_BWD))) return false;
   if (gb ? (!a.bn_x || !a.stats || a.bias || a.y_pre || (a.flags & SDA_EPI_GELU)) : (a.bn_x != nullptr)) return false;
   if (!gb && !rsq && a.stats) return false;
   if (rsq && !a.stats) return false;
-  return a.x_row0 == PAD && a.x_pitch == a.w_pitch && a.x_pitch >= a.Cin_p && a.x_sample_rows == rows_tp(a.T) &&
-         a.x_rows_limit >= (long)a.B * rows_tp(a.T) + PAD && a.x_rows_limit < (1L << 31) && a.w_rows_limit >= a.Cout_p &&
-         (long)a.x_pitch * 16 * 2 < (1L << 31);
+  return a.x_pitch >= a.Cin_p && plain_row_layout(a, PAD);
 }
 
-int launch_conv1_wide(const sda_conv_args& a, hipStream_t st) {
-  return a.dtype == SDA_BF16 ? launch_wide_e<uint16_t>(a, st) : launch_wide_e<half_t>(a, st);
-}
-
-int conv1_wide_stat_rows(int B, int T) { return (int)(((long)B * rows_tp(T) + 255) / 256); }
+int launch_conv1_wide(const sda_conv_args& a, hipStream_t st, int tile_co) { SDA_DISPATCH(a.dtype, return launch_wide_e<E>(a, st, tile_co)); }
 
 }  // namespace sda

@@ -29,8 +29,7 @@ namespace sda {
 
 namespace {
 
-constexpr int F_UNIT = 128;                          // rows per work unit
-constexpr int F_CO = 160;                            // output channels per workgroup
+// (F_UNIT = 128 rows per work unit and F_CO = 160 output channels per workgroup: conv_tile.h, the route counts with them)
 constexpr int F_NREP = 5;                            // 16-channel fragments per wave (80 channels)
 constexpr int F_XROWS_MAX = 256 + 2 * PAD;           // 288 staged input rows (256-row tile, worst-case halo)
 constexpr int F_XB = F_XROWS_MAX * ROW_B;            // 18 KB
@@ -485,22 +484,8 @@ __global__ __launch_bounds__(256, 2) void conv3_flat_kernel(const sda_conv_args 
   c.Tp = Tp;
   c.total_rows = total_rows;
 
-  // XCD-aware order (blocks i and i+8 share an XCD/L2): the n_co workgroups that read the same input rows are dealt
-  // to the same XCD.  Pure speed: any placement is correct.
-  int bid = blockIdx.x, co_tile, run;
-  const int n_co = a.Cout_p / F_CO;
-  {
-    const int group = 8 * n_co, full = (int)(gridDim.x / group) * group;
-    if (bid < full) {
-      const int base = bid / group * group, rem = bid - base;
-      co_tile = rem / 8;
-      run = base / n_co + (rem & 7);
-    } else {
-      const int rem = bid - full;
-      co_tile = rem % n_co;
-      run = full / n_co + rem / n_co;
-    }
-  }
+  int co_tile, run;
+  xcd_block_order(a.Cout_p / F_CO, co_tile, run);
   c.co0 = co_tile * F_CO;
   int u = run * units_per_wg;                               // this workgroup's 128-row units: [u, u_end)
   const int u_end = min(n_units, u + units_per_wg);
@@ -536,35 +521,12 @@ __global__ __launch_bounds__(256, 2) void conv3_flat_kernel(const sda_conv_args 
   if (tail) flat_tile<E, BN, 4, RESX, GLU>(a, smem, c, (long)u * F_UNIT, u);
 }
 
-struct FlatPlan { int n_units, units_per_wg, runs_per_co, grid; };
-
-FlatPlan flat_plan(const sda_conv_args& a) {
-  FlatPlan p;
-  const long total_rows = (long)a.B * rows_tp(a.T);
-  p.n_units = (int)((total_rows + F_UNIT - 1) / F_UNIT);
-  const int n_co = a.Cout_p / F_CO;
-  const int cus = launch_cus();
-  // two workgroups per CU; one with SDA_CONV_ONE_PER_CU (the caller wants the other half of every CU's LDS for a kernel on
-  // another stream: in backward the weight-gradient GEMMs run beside the data-gradient convs)
-  const long slots = ((a.flags & SDA_CONV_ONE_PER_CU) ? 1L : 2L) * cus;
-  p.units_per_wg = (int)(((long)p.n_units * n_co + slots - 1) / slots);
-  if (p.units_per_wg < 1) p.units_per_wg = 1;
-  p.runs_per_co = (p.n_units + p.units_per_wg - 1) / p.units_per_wg;
-  p.grid = p.runs_per_co * n_co;
-  return p;
-}
-
 template <typename E, bool BN, bool RESX, bool GLU = false>
 int launch_flat(const sda_conv_args& a, hipStream_t st) {
   static unsigned long long attr_done = 0;        // per device
   auto kern = conv3_flat_kernel<E, BN, RESX, GLU>;
-  if (first_use_on_device(attr_done)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS) != hipSuccess) {
-      set_error("conv3_flat: cannot reserve %d bytes of LDS", F_LDS);
-      return -3;
-    }
-  }
-  const FlatPlan p = flat_plan(a);
+  if (const int rc = reserve_lds_once(attr_done, kern, F_LDS, "conv3_flat")) return rc;
+  const FlatPlan p = flat_plan(a, F_UNIT, F_CO);
   hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(256), F_LDS, st, a, p.n_units, p.units_per_wg, p.runs_per_co,
                      (long)a.B * rows_tp(a.T), rows_tp(a.T));
   return check_launch("conv3_flat");
@@ -572,15 +534,11 @@ int launch_flat(const sda_conv_args& a, hipStream_t st) {
 
 }  // namespace
 
-int conv3_flat_stat_rows(int B, int T) { return (int)(((long)B * rows_tp(T) + F_UNIT - 1) / F_UNIT); }
-
 bool conv3_flat_supports(const sda_conv_args& a) {
   const bool glu = a.flags & SDA_EPI_GLU;
   if (glu ? (a.res || a.stats || a.bn_x) : a.y_pre != nullptr) return false;
-  return a.KS == 3 && a.Cout_p % F_CO == 0 && !a.widx && a.ksplit == 1 && !a.partial && !(a.flags & SDA_EPI_GELU) &&
-         a.y && a.x_row0 == PAD && a.x_pitch == a.w_pitch && a.x_sample_rows == rows_tp(a.T) && (!a.bn_x || (a.bn_coef && a.stats)) &&
-         a.x_rows_limit >= (long)a.B * rows_tp(a.T) + 3 * PAD && a.x_rows_limit < (1L << 31) && a.w_rows_limit >= a.Cout_p &&
-         a.Cin_p / (ROW_B / (a.dtype == SDA_F32 ? 4 : 2)) >= 1;
+  return !a.widx && a.ksplit == 1 && !a.partial && !(a.flags & SDA_EPI_GELU) && a.y && (!a.bn_x || (a.bn_coef && a.stats)) &&
+         a.Cin_p / (ROW_B / (a.dtype == SDA_F32 ? 4 : 2)) >= 1 && plain_row_layout(a, 3 * PAD);
 }
 
 template <typename E> static int launch_flat_e(const sda_conv_args& a, hipStream_t st) {
@@ -589,19 +547,6 @@ template <typename E> static int launch_flat_e(const sda_conv_args& a, hipStream
   return a.res ? launch_flat<E, false, true>(a, st) : launch_flat<E, false, false>(a, st);
 }
 
-int launch_conv3_flat(const sda_conv_args& a, hipStream_t st) {
-  if (a.dtype == SDA_F32) return launch_flat_e<float>(a, st);
-  if (a.dtype == SDA_F16) return launch_flat_e<half_t>(a, st);
-  return launch_flat_e<uint16_t>(a, st);
-}
+int launch_conv3_flat(const sda_conv_args& a, hipStream_t st) { SDA_DISPATCH(a.dtype, return launch_flat_e<E>(a, st)); }
 
 }  // namespace sda
-
-// rows of sda_conv_args.stats one launch writes: the tile-per-workgroup kernels write B * sda_conv_n_t_tiles(T) rows
-// (one per 128-row tile of a sample), the flat-tile kernel one per 128-row unit of the flat row space
-extern "C" int sda_conv_stats_rows(int B, int T, int KS, int Cout_p, int flags) {
-  if ((flags & SDA_CONV_FLAT_TILES) && KS == 3 && Cout_p % sda::F_CO == 0) return sda::conv3_flat_stat_rows(B, T);
-  if ((flags & SDA_CONV_WIDE_TILES) && KS == 1 && (flags & SDA_EPI_GELU_BWD)) return sda::conv1_wide_stat_rows(B, T);   // conv1_wide: one row per 256-row tile
-  if ((flags & SDA_CONV_FLAT_TILES) && KS == 1 && (flags & SDA_EPI_GELU_BWD)) return sda::conv3_flat_stat_rows(B, T);   // conv1_flat: same units
-  return B * ((T + sda::TILE_T - 1) / sda::TILE_T);
-}

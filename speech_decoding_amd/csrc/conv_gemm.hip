@@ -79,6 +79,7 @@ __global__ __launch_bounds__(256 * NT, 2) void conv_gemm_kernel(const sda_conv_a
   const int n_co = a.Cout_p / TILE_CO;
   // XCD-aware order (blocks i and i+8 share an XCD/L2): the n_co workgroups that read the same input rows
   // are dealt to the same XCD.  Pure speed: any placement is correct.
+  // (flat_tile.h's xcd_block_order in a form of its own, algebraically equal: with the helper this kernel's instructions change)
   int co_tile;
   {
     const int group = 8 * n_co, full = (int)(gridDim.x / group) * group;
@@ -604,13 +605,7 @@ static int launch_conv(const sda_conv_args& a, hipStream_t st) {
   constexpr int lds = conv_lds_bytes<TILE_CO, KS, NT, SV>();
   static unsigned long long attr_done = 0;        // per device
   auto kern = conv_gemm_kernel<E, TILE_CO, KS, NT, BN, SV>;
-  if (first_use_on_device(attr_done)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            lds) != hipSuccess) {
-      set_error("conv_gemm: cannot reserve %d bytes of LDS", lds);
-      return -3;
-    }
-  }
+  if (const int rc = reserve_lds_once(attr_done, kern, lds, "conv_gemm")) return rc;
   const int n_t = (a.T + TILE_T - 1) / TILE_T;
   const long groups = ((long)a.B * n_t + NT - 1) / NT;
   const long grid = (long)(a.Cout_p / TILE_CO) * groups * a.ksplit;
@@ -652,28 +647,34 @@ static int dispatch_conv_nt(const sda_conv_args& a, hipStream_t st) {
 
 template <typename E>
 static int dispatch_conv(const sda_conv_args& a, hipStream_t st) {
-  if ((a.flags & SDA_CONV_FLAT_TILES) && a.KS == 3 && a.Cout_p % 160 == 0) {
-    // (exactly the condition sda_conv_stats_rows uses: the statistics rows a caller sized must be the rows written)
+  // The route (conv_route.hip) is what sda_conv_stats_rows counts with: a launch that writes statistics runs the routed kernel
+  // or is refused, so the rows a caller sized are the rows written.
+  ConvRoute r = conv_route(a.KS, a.Cout_p, a.flags, a.dtype, a.stats != nullptr);
+  if (r.kernel == SDA_CONV_KERNEL_FLAT3) {
     if (!conv3_flat_supports(a)) { set_error("conv_gemm: SDA_CONV_FLAT_TILES needs a plain row-layout kernel-3 convolution"); return -1; }
     return launch_conv3_flat(a, st);
   }
-  if ((a.flags & SDA_CONV_WIDE_TILES) && a.KS == 1) {
-    // (an error, not a fallback: the statistics rows a caller sized with sda_conv_stats_rows must be the rows written)
-    if (!conv1_wide_supports(a)) { set_error("conv_gemm: SDA_CONV_WIDE_TILES needs a plain row-layout kernel-1 convolution, 16-bit storage, Cout_p %% 256 == 0 or %% 320 == 0"); return -1; }
-    return launch_conv1_wide(a, st);
+  if (r.kernel == SDA_CONV_KERNEL_WIDE) {
+    if (!conv1_wide_supports(a)) { set_error("conv_gemm: SDA_CONV_WIDE_TILES needs a plain row-layout kernel-1 convolution, shared weights, no residual"); return -1; }
+    return launch_conv1_wide(a, st, r.tile_co);
   }
-  if ((a.flags & SDA_CONV_FLAT_TILES) && a.KS == 1 && conv1_flat_supports(a)) return launch_conv1_flat(a, st);
-  if (a.flags & SDA_EPI_ROW_SUMSQ) {
-    set_error("conv_gemm: SDA_EPI_ROW_SUMSQ needs SDA_CONV_FLAT_TILES (or SDA_CONV_WIDE_TILES) and a plain row-layout kernel-1 convolution with Cout_p % 128 == 0");
-    return -1;
+  if (r.kernel == SDA_CONV_KERNEL_FLAT1) {
+    if (conv1_flat_supports(a)) return launch_conv1_flat(a, st, r.tile_co);
+    if (a.stats || (a.flags & (SDA_EPI_GELU_BWD | SDA_EPI_ROW_SUMSQ))) {
+      set_error("conv_gemm: the flat kernel-1 route (SDA_CONV_FLAT_TILES, conv1_flat) with statistics needs a plain row-layout "
+                "convolution: x_pitch == w_pitch == Cin_p, shared weights, no residual");
+      return -1;
+    }
+    // (a plain launch writes no statistics: any kernel serves it, the flag is a preference)
+    r = conv_route(a.KS, a.Cout_p, a.flags & ~SDA_CONV_FLAT_TILES, a.dtype, false);
   }
-  if ((a.flags & SDA_EPI_GELU_BWD) && (!a.bn_x || !a.stats || a.bias || a.y_pre || a.res || a.partial || a.KS != 1 ||
-                                       (a.flags & (SDA_EPI_GELU | SDA_EPI_GLU | SDA_EPI_GLU_BWD)))) {
+  if (r.kernel != SDA_CONV_KERNEL_TILE) return -1;    // refused: the route has set the error
+  if ((a.flags & SDA_EPI_GELU_BWD) && (!a.bn_x || !a.stats || a.bias || a.y_pre || a.res || a.partial ||
+                                       (a.flags & (SDA_EPI_GELU | SDA_EPI_GLU_BWD)))) {
     set_error("conv_gemm: SDA_EPI_GELU_BWD needs kernel size 1, bn_x (the GELU's input) and stats, and no bias / y_pre / residual / other epilogue");
     return -1;
   }
-  if (a.flags & SDA_EPI_GLU) { set_error("conv_gemm: SDA_EPI_GLU needs SDA_CONV_FLAT_TILES, kernel size 3 and Cout_p % 160 == 0"); return -1; }
-  switch (sda_conv_tile_co(a.Cout_p, a.KS, a.stats != nullptr)) {
+  switch (r.tile_co) {
     case 128: return dispatch_conv_nt<E, 128>(a, st);    // (128 before 160: the order the kernels are instantiated in, so the code object's layout)
     case 160: return dispatch_conv_nt<E, 160>(a, st);
     default: return dispatch_conv_nt<E, 64>(a, st);
@@ -685,13 +686,6 @@ static int dispatch_conv(const sda_conv_args& a, hipStream_t st) {
 using namespace sda;
 
 extern "C" int sda_conv_n_t_tiles(int T) { return (T + TILE_T - 1) / TILE_T; }
-
-extern "C" int sda_conv_tile_co(int Cout_p, int KS, int has_stats) {
-  // 1x1 convs whose width divides both ways (640): 128-channel tiles (conv_final1 forward 125 -> 113 us, conv_final2's data
-  // gradient 225 -> 195 us; the k = 3 convs and the statistics-row contract stay on 160)
-  if (KS == 1 && Cout_p % 128 == 0 && !has_stats) return 128;
-  return Cout_p % 160 == 0 ? 160 : Cout_p % 128 == 0 ? 128 : 64;
-}
 
 extern "C" int sda_conv_gemm(const sda_conv_args* a, void* stream) {
   if (!a || !a->x || !a->w || (!a->y && !a->partial)) { set_error("conv_gemm: null argument"); return -1; }
@@ -717,9 +711,5 @@ extern "C" int sda_conv_gemm(const sda_conv_args* a, void* stream) {
     set_error("conv_gemm: bn_x needs bn_coef and stats, and excludes split-K / GELU epilogues"); return -1;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (a->dtype == SDA_F32) return dispatch_conv<float>(*a, st);
-  if (a->dtype == SDA_BF16) return dispatch_conv<uint16_t>(*a, st);
-  if (a->dtype == SDA_F16) return dispatch_conv<half_t>(*a, st);
-  set_error("conv_gemm: unknown dtype %d", a->dtype);
-  return -1;
+  SDA_DISPATCH(a->dtype, return dispatch_conv<E>(*a, st));
 }

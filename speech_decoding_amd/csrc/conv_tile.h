@@ -1,4 +1,4 @@
-// LDS tile geometry shared by the conv kernels (conv_gemm.hip, conv3_flat.hip).
+// LDS tile geometry shared by the conv kernels, and the route between them (conv_route.hip).
 #pragma once
 #include "sd_common.h"
 
@@ -17,18 +17,30 @@ constexpr int XS_BYTES = XROWS * ROW_B;            // 10 KB
 __device__ inline int sw64(int row) { return (row >> 1) & 2; }
 __device__ inline int lds_sw64(int row, int chunk) { return row * ROW_B + ((chunk ^ sw64(row)) << 4); }
 
-// conv3_flat.hip
-int launch_conv3_flat(const sda_conv_args& a, hipStream_t st);
+// Tile geometry of the flat-row-space kernels: written here once, for the kernels and for the route that counts with it.
+constexpr int F_UNIT = 128;            // conv3_flat: rows per work unit (one `stats` row each)
+constexpr int F_CO = 160;              // conv3_flat: output channels per workgroup
+constexpr int G_UNIT = 128;            // conv1_flat: rows per work unit
+constexpr int G_CO[2] = {160, 128};    // conv1_flat: output channels per workgroup, in order of preference
+constexpr int W_UNIT = 256;            // conv1_wide: rows per tile
+constexpr int W_CO[2] = {256, 320};    // conv1_wide: output channels per tile, in order of preference
+
+// conv_route.hip — the ONE place that decides which kernel serves a convolution.  kernel: SDA_CONV_KERNEL_*, or -1 with the
+// error set where the flags demand a kernel the shape or storage type cannot have; tile_co: its output-channel tile;
+// unit_rows: the rows one [2][Cout_p] row of `stats` covers (TILE: per sample, B * ceil(T / unit_rows) rows; the others: of
+// the flat row space, ceil(B * rows_tp(T) / unit_rows) rows).
+struct ConvRoute { int kernel, tile_co, unit_rows; };
+ConvRoute conv_route(int KS, int Cout_p, int flags, int dtype, bool has_stats);
+// Plain row-layout operands, what the flat-row-space kernels address: samples back to back from row SDA_ROW_PAD, one pitch
+// for x and w, fully padded weights, `slack_rows` readable rows behind the last sample, 31-bit row and piece offsets.
+bool plain_row_layout(const sda_conv_args& a, int slack_rows);
+
+// the routed kernels: what the descriptor must satisfy beyond the route, and the launch
 bool conv3_flat_supports(const sda_conv_args& a);
-int conv3_flat_stat_rows(int B, int T);
-
-// conv1_flat.hip
-int launch_conv1_flat(const sda_conv_args& a, hipStream_t st);
+int launch_conv3_flat(const sda_conv_args& a, hipStream_t st);
 bool conv1_flat_supports(const sda_conv_args& a);
-
-// conv1_wide.hip
-int launch_conv1_wide(const sda_conv_args& a, hipStream_t st);
+int launch_conv1_flat(const sda_conv_args& a, hipStream_t st, int tile_co);
 bool conv1_wide_supports(const sda_conv_args& a);
-int conv1_wide_stat_rows(int B, int T);
+int launch_conv1_wide(const sda_conv_args& a, hipStream_t st, int tile_co);
 
 }  // namespace sda

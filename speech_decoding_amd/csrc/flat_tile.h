@@ -44,4 +44,39 @@ __device__ __forceinline__ void lds_dma16_lean(const void* sbase, uint32_t voff,
 using TrueC = std::integral_constant<bool, true>;
 using FalseC = std::integral_constant<bool, false>;
 
+// The grid of the flat kernels: ONE round of persistent workgroups, each owning a run of `units_per_wg` consecutive
+// `unit_rows`-row units of one `tile_co`-channel tile.
+struct FlatPlan { int n_units, units_per_wg, runs_per_co, grid; };
+inline FlatPlan flat_plan(const sda_conv_args& a, int unit_rows, int tile_co) {
+  FlatPlan p;
+  const long total_rows = (long)a.B * rows_tp(a.T);
+  p.n_units = (int)((total_rows + unit_rows - 1) / unit_rows);
+  const int n_co = a.Cout_p / tile_co;
+  // two workgroups per CU; one with SDA_CONV_ONE_PER_CU (the caller wants the other half of every CU's LDS for a kernel on
+  // another stream: in backward the weight-gradient GEMMs run beside the data-gradient convs)
+  const long slots = ((a.flags & SDA_CONV_ONE_PER_CU) ? 1L : 2L) * launch_cus();
+  p.units_per_wg = (int)(((long)p.n_units * n_co + slots - 1) / slots);
+  if (p.units_per_wg < 1) p.units_per_wg = 1;
+  p.runs_per_co = (p.n_units + p.units_per_wg - 1) / p.units_per_wg;
+  p.grid = p.runs_per_co * n_co;
+  return p;
+}
+
+// This workgroup's (channel tile, run) under that plan, in XCD-aware order (blocks i and i + 8 share an XCD/L2): the n_co
+// workgroups that read the same input rows are dealt to the same XCD.  Pure speed: any placement is correct.
+// (gridDim.x stays unsigned in the division: with an int the compiler emits a signed division and a different kernel)
+__device__ __forceinline__ void xcd_block_order(const int n_co, int& co_tile, int& run) {
+  const int bid = blockIdx.x;
+  const int group = 8 * n_co, full = (int)(gridDim.x / group) * group;
+  if (bid < full) {
+    const int base = bid / group * group, rem = bid - base;
+    co_tile = rem / 8;
+    run = base / n_co + (rem & 7);
+  } else {
+    const int rem = bid - full;
+    co_tile = rem % n_co;
+    run = full / n_co + rem / n_co;
+  }
+}
+
 }  // namespace sda

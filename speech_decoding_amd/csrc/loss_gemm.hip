@@ -203,12 +203,7 @@ int launch_dz(const void* G, long g_pitch, const void* Y, const void* Z, void* o
               const float* out_scale, int Bm, int Bn, long row_elems, hipStream_t st) {
   static unsigned long long attr_done = 0;        // per device
   auto kern = clip_dz_kernel<E>;
-  if (first_use_on_device(attr_done)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, DZ_LDS) != hipSuccess) {
-      set_error("clip_dz: cannot reserve %d bytes of LDS", DZ_LDS);
-      return -3;
-    }
-  }
+  if (const int rc = reserve_lds_once(attr_done, kern, DZ_LDS, "clip_dz")) return rc;
   const int cus = launch_cus();
   const int ntiles = (int)(row_elems / DZ_KT);
   const int jblocks = (Bn + 255) / 256;
@@ -375,12 +370,7 @@ int launch_dz_tiles(const void* G, long g_pitch, const void* Y, const void* Z, v
                     const float* out_scale, int Bm, int Bn, long row_elems, hipStream_t st) {
   static unsigned long long attr_done = 0;        // per device
   auto kern = clip_dz_tiles_kernel<E>;
-  if (first_use_on_device(attr_done)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, DT_LDS) != hipSuccess) {
-      set_error("clip_dz: cannot reserve %d bytes of LDS", DT_LDS);
-      return -3;
-    }
-  }
+  if (const int rc = reserve_lds_once(attr_done, kern, DT_LDS, "clip_dz")) return rc;
   const int ntiles = (int)(row_elems / DT_TILE);
   const int jblocks = (Bn + DT_TILE - 1) / DT_TILE;
   int gx = launch_cus() / jblocks;                     // one persistent workgroup per CU in all

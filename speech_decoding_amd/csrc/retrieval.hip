@@ -412,13 +412,7 @@ extern "C" int sda_retrieval_select(const float* S, const float* qsq, const floa
   if (chunk_cols < 64 || chunk_cols % 64 != 0) { set_error("retrieval_select: chunk_cols must be a positive multiple of 64"); return -1; }
   if (((uintptr_t)S & 15) != 0) { set_error("retrieval_select: the score matrix must be 16-byte aligned"); return -1; }
   static unsigned long long attr_done = 0;         // per device
-  if (first_use_on_device(attr_done)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(retrieval_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            RS_LDS) != hipSuccess) {
-      set_error("retrieval_select: cannot reserve %d bytes of LDS", RS_LDS);
-      return -3;
-    }
-  }
+  if (const int rc = reserve_lds_once(attr_done, retrieval_select_kernel, RS_LDS, "retrieval_select")) return rc;
   hipLaunchKernelGGL(retrieval_select_kernel, dim3((unsigned)n), dim3(RS_THREADS), RS_LDS, (hipStream_t)stream, S, qsq, csq,
                      reinterpret_cast<const long long*>(labels), reinterpret_cast<long long*>(indices), scores, ranks, n, M, k,
                      chunk_cols);

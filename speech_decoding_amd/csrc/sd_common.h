@@ -345,6 +345,11 @@ int check_launch(const char* what);
 // Per-DEVICE launch state (a process may drive several GPUs): `done` is a static bit mask owned by the call site; true the
 // first time the CURRENT device asks (hipFuncSetAttribute is per device).
 bool first_use_on_device(unsigned long long& done);
+// Reserve `lds` bytes of dynamic LDS for `kern`, once per device: 0, or -3 with the error "<what>: cannot reserve ..." set
+int reserve_lds_once(unsigned long long& done, const void* kern, int lds, const char* what);
+template <typename K> int reserve_lds_once(unsigned long long& done, K* kern, int lds, const char* what) {
+  return reserve_lds_once(done, reinterpret_cast<const void*>(kern), lds, what);
+}
 // CUs a persistent grid may count on: the current device's CU count, or the limit the caller set for launches that go to
 // a CU-masked stream (sda_set_cu_limit; thread-local, 0 = none)
 int launch_cus();

@@ -193,12 +193,7 @@ int launch_sim_ns(const void* X, const void* W, float* partial, int M, int N, in
   constexpr int lds = NS * SG_STAGE;
   static unsigned long long attr_done = 0;        // per device
   auto kern = sim_gemm_kernel<E, NS>;
-  if (first_use_on_device(attr_done)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      set_error("sim_gemm: cannot reserve %d bytes of LDS", lds);
-      return -3;
-    }
-  }
+  if (const int rc = reserve_lds_once(attr_done, kern, lds, "sim_gemm")) return rc;
   const int m_tiles = (M + SG_TILE - 1) / SG_TILE, n_tiles = (N + SG_TILE - 1) / SG_TILE;
   const int nslab = (int)(K / (ROW_B / (long)sizeof(E)));
   const long grid = (long)m_tiles * n_tiles * ksplit;
@@ -217,12 +212,7 @@ int launch_sim_windows(const void* X, long x_pitch, const void* table, const int
   constexpr int lds = SG_NS * SG_STAGE;
   static unsigned long long attr_done = 0;        // per device
   auto kern = sim_gemm_kernel<E, SG_NS, true>;
-  if (first_use_on_device(attr_done)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      set_error("sim_gemm_windows: cannot reserve %d bytes of LDS", lds);
-      return -3;
-    }
-  }
+  if (const int rc = reserve_lds_once(attr_done, kern, lds, "sim_gemm_windows")) return rc;
   const int m_tiles = (M + SG_TILE - 1) / SG_TILE, n_tiles = (N + SG_TILE - 1) / SG_TILE;
   const int nslab = (int)(K / (ROW_B / (long)sizeof(E)));
   const long grid = (long)m_tiles * n_tiles * ksplit;

@@ -416,13 +416,7 @@ static int launch_wgrad(const sda_wgrad_args& a, hipStream_t st) {
   const int lds = a.out_e ? lds_max : NS * WG_::STAGE;
   static unsigned long long attr_done = 0;        // per device
   auto kern = wgrad_gemm_kernel<E, TILE_M, KS, TN, KM, NS>;
-  if (first_use_on_device(attr_done)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            lds_max) != hipSuccess) {
-      set_error("wgrad_gemm: cannot reserve %d bytes of LDS", lds_max);
-      return -3;
-    }
-  }
+  if (const int rc = reserve_lds_once(attr_done, kern, lds_max, "wgrad_gemm")) return rc;
   const long grid = (long)(a.Cin_p / TN) * (a.Cout_p / TILE_M) * a.nseg;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, a);
   return check_launch("wgrad_gemm");

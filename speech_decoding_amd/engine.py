@@ -11,6 +11,7 @@ from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
 import ast
+from collections import namedtuple
 import os
 
 import numpy as np
@@ -198,6 +199,9 @@ class _Backward:
         return out, st
 
 
+_Routes = namedtuple("_Routes", "conv2_glu_flat f2_wide f2_dgrad_gelu_flat")
+
+
 class EncoderEngine:
     def __init__(self, dims: EncoderDims, dtype: torch.dtype = torch.float32, group=None):
         L.load()                          # fail loudly if the HIP extension is missing
@@ -221,12 +225,13 @@ class EncoderEngine:
         self.flat_tiles_forward = True       # k = 3 convs on the 256-row flat-tile kernel (conv3_flat.hip) where it applies (fp32
                                              # storage too: that instantiation runs 128-row tiles only — 80 accumulator registers
                                              # per wave, no scratch)
-        self.fuse_glu_forward = True         # F.glu in conv2's epilogue (flat-tile kernel, D2p % 80 == 0): no [value | gate] buffer
+        self.fuse_glu_forward = True         # F.glu in conv2's epilogue (where conv2 routes to the flat-tile kernel): no [value | gate] buffer
         self.compose_subject_block = True    # SpatialAttention, the shared 1x1 conv and the per-subject 1x1 conv as ONE per-subject
                                              # matrix (needs a spare padding channel for the folded bias: C < Cp)
         self._side = {}
         self._const = {}                     # persistent operand buffers (composed SubjectBlock matrices)
         self._plan_key = None                # (device, dtype, glu_fused, composed) the cached pack plans were built for
+        self._route_key = None               # storage type the cached kernel routes were asked for
 
         # diagnostics: SDA_ENGINE_<switch>=<python literal> overrides one of the SWITCHES above (plain bool / int / float
         # attributes set in this constructor: never a property, a buffer table or the dims)
@@ -306,7 +311,7 @@ class EncoderEngine:
 
     @property
     def glu_fused(self) -> bool:
-        return bool(self.fuse_glu_forward and self.flat_forward and self.d.D2p % 80 == 0)
+        return bool(self.fuse_glu_forward and self.flat_forward and self._routes().conv2_glu_flat)
 
     @property
     def flat_forward(self) -> bool:
@@ -324,7 +329,19 @@ class EncoderEngine:
         e1.record(stream)
         self.probe.append((label, e0, e1))
 
-    # ------------------------------------------------------------------ operand packing plans
+    # ------------------------------------------------------------------ kernel routes and operand packing plans
+    def _routes(self):
+        """What depends on the kernel the library routes a conv to (ops.conv_kernel), asked once per storage type: conv2 with
+        F.glu in its epilogue runs on conv3_flat, conv_final2 with the row sums of squares on conv1_wide, conv_final2's data
+        gradient with conv_final1's GELU backward in its epilogue on conv1_flat."""
+        if self._route_key != self.dtype:
+            d, dt = self.d, self.dtype
+            self._route = _Routes(ops.conv_kernel(3, 2 * d.D2p, L.CONV_FLAT_TILES | L.EPI_GLU, dt) == L.CONV_KERNEL_FLAT3,
+                                  ops.conv_kernel(1, d.Fp, L.CONV_WIDE_TILES | L.EPI_ROW_SUMSQ, dt) == L.CONV_KERNEL_WIDE,
+                                  ops.conv_kernel(1, d.F1p, L.CONV_FLAT_TILES | L.EPI_GELU_BWD, dt) == L.CONV_KERNEL_FLAT1)
+            self._route_key = dt
+        return self._route
+
     def _plans(self, P, dev):
         key = (str(dev), self.dtype, self.glu_fused, self.composed)
         if self._plan_key == key:
@@ -527,8 +544,7 @@ class EncoderEngine:
         d, dt, ctx, dev = self.d, self.dtype, f.ctx, f.dev
         B, T, pk, need_grad = ctx.B, ctx.T, ctx.packed, f.need_grad
         u1, g1 = f.rows("u1", d.F1p), f.rows("g1", d.F1p)
-        # conv_final2 on conv1_wide.hip's 256-row tiles where its width allows (16-bit storage, Fp % 256 == 0)
-        f2_wide = dt != torch.float32 and d.Fp % 256 == 0
+        f2_wide = self._routes().f2_wide         # conv_final2 on conv1_wide.hip's 256-row tiles where storage type and width allow
         ops.conv_gemm(x, pk["f1w"], g1, B=B, T=T, KS=1, dil=0, bias=pk["f1b"], y_pre=u1 if need_grad else None,
                       gelu=True, alg_dims=(d.D2, d.F1))
         # Z is handed to the caller: a FRESH buffer per forward (the reference returns a new tensor each call), so
@@ -611,7 +627,7 @@ class EncoderEngine:
             ops.gelu_backward(bufs["u2"], dZt, du2, B, T)
         # the 1x1 data gradients on conv1_flat.hip's 256-row flat tiles
         du1 = b.tmp("du1", d.F1p)
-        if d.F1p % 160 == 0 or d.F1p % 128 == 0:
+        if self._routes().f2_dgrad_gelu_flat:
             # conv_final2's data gradient with conv_final1's GELU backward in its epilogue: du1 directly, plus per-unit column sums
             gst = torch.empty((ops.conv_stats_rows(B, T, 1, d.F1p, L.CONV_FLAT_TILES | L.EPI_GELU_BWD), 2, d.F1p),
                               dtype=torch.float32, device=dev)

@@ -608,8 +608,15 @@ def n_t_tiles(T: int) -> int:
 
 
 def conv_stats_rows(B: int, T: int, KS: int, Cout_p: int, flags: int = 0) -> int:
-    """Rows of the per-tile statistics buffer a conv_gemm launch with these parameters writes."""
+    """Rows of the per-tile statistics buffer a conv_gemm launch with these parameters writes (-1: it would be refused)."""
     return L.load().sda_conv_stats_rows(B, T, KS, Cout_p, flags)
+
+
+def conv_kernel(KS: int, Cout_p: int, flags: int, dtype) -> Optional[int]:
+    """The kernel conv_gemm routes a convolution to (L.CONV_KERNEL_TILE / _FLAT3 / _FLAT1 / _WIDE), asked of the library that
+    routes; None where it refuses these flags for this width or storage type (dtype: torch dtype or dtype code)."""
+    k = L.load().sda_conv_kernel(KS, Cout_p, flags, dtype if isinstance(dtype, int) else dt_code(dtype))
+    return None if k < 0 else k
 
 
 # the similarity matmul of 16-bit operands on sim_gemm.hip's 256 x 256 tiles (False: conv_gemm's split-K matrix mode with

@@ -223,7 +223,7 @@ def test_conv1_flat_gelu_backward_epilogue(ops, dtype, cin, cout, T, B):
     L = _L()
     g = torch.Generator().manual_seed(cin + T)
     Cip, Cop = L.pad_channels(cin), L.pad_channels(cout)
-    assert Cop % 160 == 0 or Cop % 128 == 0
+    assert ops.conv_kernel(1, Cop, L.CONV_FLAT_TILES | L.EPI_GELU_BWD, dtype) == L.CONV_KERNEL_FLAT1
     xb = rows_of(ops, q(torch.randn(B, cin, T, generator=g), dtype), dtype)
     wp = ops.pack_conv_weight(q(torch.randn(cout, cin, 1, generator=g) / math.sqrt(cin), dtype).to(DEV), Cop, Cip, dtype)
     ub = rows_of(ops, q(torch.randn(B, cout, T, generator=g), dtype), dtype)
@@ -241,7 +241,7 @@ def test_conv1_wide_tiles_row_sumsq(ops, dtype, cin, cout, T, B):
     L = _L()
     g = torch.Generator().manual_seed(cout + T)
     Cip, Cop = L.pad_channels(cin), L.pad_channels(cout)
-    assert Cop % 256 == 0
+    assert ops.conv_kernel(1, Cop, L.CONV_WIDE_TILES | L.EPI_ROW_SUMSQ, dtype) == L.CONV_KERNEL_WIDE
     xb = rows_of(ops, q(torch.randn(B, cin, T, generator=g), dtype), dtype)
     wp = ops.pack_conv_weight(q(torch.randn(cout, cin, 1, generator=g) / math.sqrt(cin), dtype).to(DEV), Cop, Cip, dtype)
     bias = ops.pack_vector(torch.randn(cout, generator=g).to(DEV), Cop)

@@ -62,6 +62,95 @@ def test_tile_rules_are_the_library_s(lib):
     assert [ops.wgrad_tile_m(c) for c in (320, 640, 256, 1024, 192)] == [160, 160, 128, 128, 64]
 
 
+# sda_conv_gemm's route, written out: per (kernel size, flags) one letter per Cout_p of ROUTE_WIDTHS — T = one tile per workgroup,
+# 3 = conv3_flat, 1 = conv1_flat, W = conv1_wide (16-bit storage; fp32 is refused), - = refused
+ROUTE_WIDTHS = (64, 128, 192, 256, 320, 640, 1024)
+ROUTES = {(3, "0"): "TTTTTTT", (3, "PAIR"): "TTTTTTT", (3, "FLAT"): "TTTT33T", (3, "FLAT|GELU_BWD"): "-------",
+          (3, "FLAT|ROW_SUMSQ"): "-------", (3, "FLAT|EPI_GLU"): "----33-", (3, "WIDE"): "TTTTTTT", (3, "WIDE|GELU_BWD"): "-------",
+          (3, "WIDE|ROW_SUMSQ"): "-------",
+          (1, "0"): "TTTTTTT", (1, "PAIR"): "TTTTTTT", (1, "FLAT"): "T1T1111", (1, "FLAT|GELU_BWD"): "T1T1111",
+          (1, "FLAT|ROW_SUMSQ"): "-1-1-11", (1, "FLAT|EPI_GLU"): "-------", (1, "WIDE"): "---WWWW", (1, "WIDE|GELU_BWD"): "---WWWW",
+          (1, "WIDE|ROW_SUMSQ"): "---W--W"}
+
+
+def route_rows(lib):
+    """(KS, Cout_p, flags, dtype code, expected kernel or None) for every row of ROUTES and every storage type"""
+    bits = {"0": 0, "PAIR": lib.CONV_PAIR_TILES, "FLAT": lib.CONV_FLAT_TILES, "WIDE": lib.CONV_WIDE_TILES, "GELU_BWD": lib.EPI_GELU_BWD,
+            "ROW_SUMSQ": lib.EPI_ROW_SUMSQ, "EPI_GLU": lib.EPI_GLU}
+    kern = {"T": lib.CONV_KERNEL_TILE, "3": lib.CONV_KERNEL_FLAT3, "1": lib.CONV_KERNEL_FLAT1, "W": lib.CONV_KERNEL_WIDE, "-": None}
+    for (KS, names), letters in ROUTES.items():
+        flags = sum(bits[n] for n in names.split("|"))
+        for Cout_p, letter in zip(ROUTE_WIDTHS, letters):
+            for dt in (lib.F32, lib.BF16, lib.F16):
+                yield KS, Cout_p, flags, dt, None if (letter == "W" and dt == lib.F32) else kern[letter]
+
+
+def test_conv_route_table(lib):
+    """sda_conv_kernel (and ops.conv_kernel over it) against the table above; a refusal leaves its reason in sda_last_error."""
+    from speech_decoding_amd import ops
+    L = lib.load()
+    assert len(ROUTES) == 2 * 9 and (lib.CONV_KERNEL_TILE, lib.CONV_KERNEL_FLAT3, lib.CONV_KERNEL_FLAT1, lib.CONV_KERNEL_WIDE) == (0, 1, 2, 3)
+    for KS, Cout_p, flags, dt, want in route_rows(lib):
+        got = L.sda_conv_kernel(KS, Cout_p, flags, dt)
+        assert got == (-1 if want is None else want), (KS, Cout_p, flags, dt)
+        assert ops.conv_kernel(KS, Cout_p, flags, dt) == want
+        assert ops.conv_kernel(KS, Cout_p, flags, {lib.F32: torch.float32, lib.BF16: torch.bfloat16, lib.F16: torch.float16}[dt]) == want
+        if want is None:
+            assert b"conv_gemm: SDA_" in L.sda_last_error()
+    assert L.sda_conv_kernel(1, 128, 0, 7) == -1 and b"dtype" in L.sda_last_error()
+
+
+def test_conv_stats_rows_are_the_routed_kernel_s(lib):
+    """sda_conv_stats_rows = the row count of the kernel the launch is routed to, for every accepted row of the table.  (3, 130)
+    tells the three counts apart: 6 tile rows, 4 flat units, 2 wide tiles."""
+    from speech_decoding_amd import ops
+    L = lib.load()
+    cdiv = lambda a, b: -(-a // b)
+    seen = set()
+    for KS, Cout_p, flags, dt, kernel in route_rows(lib):
+        if kernel is None:
+            continue
+        for B, T in [(3, 130), (2, 5), (1, 128)]:
+            want = {lib.CONV_KERNEL_TILE: B * cdiv(T, 128), lib.CONV_KERNEL_FLAT3: cdiv(B * (T + 16), 128),
+                    lib.CONV_KERNEL_FLAT1: cdiv(B * (T + 16), 128), lib.CONV_KERNEL_WIDE: cdiv(B * (T + 16), 256)}[kernel]
+            assert L.sda_conv_stats_rows(B, T, KS, Cout_p, flags) == want == ops.conv_stats_rows(B, T, KS, Cout_p, flags), (B, T, KS, Cout_p, flags)
+            seen.add((B, T, kernel, want))
+    assert {(3, 130, lib.CONV_KERNEL_TILE, 6), (3, 130, lib.CONV_KERNEL_FLAT1, 4), (3, 130, lib.CONV_KERNEL_WIDE, 2)} <= seen
+
+
+def test_conv_gemm_refuses_statistics_off_the_routed_kernel(lib):
+    """SDA_CONV_FLAT_TILES | SDA_EPI_GELU_BWD on a width conv1_flat serves, but operands that are not plain row layout (x_row0 = 32):
+    refused before any launch (made-up addresses, no device here), never handed to the tile kernel with its other row count."""
+    from speech_decoding_amd import ops
+    L = lib.load()
+    B, T, C = 3, 130, 128
+    kw = dict(B=B, T=T, Cin_p=C, Cout_p=C, KS=1, dil=0, x_pitch=C, w_pitch=C, x_rows_limit=lib.rows_alloc(B, T) + 32, dtype=lib.BF16,
+              flags=lib.CONV_FLAT_TILES | lib.EPI_GELU_BWD, stats=0x5000, bn_x=0x6000)
+    assert L.sda_conv_kernel(1, C, kw["flags"], lib.BF16) == lib.CONV_KERNEL_FLAT1
+    a = ops.conv_args(0x1000, 0x2000, 0x3000, x_row0=32, **kw)
+    assert L.sda_conv_gemm(ctypes.byref(a), None) != 0
+    err = L.sda_last_error().decode()
+    assert "SDA_CONV_FLAT_TILES" in err and "conv1_flat" in err, err
+
+
+def test_engine_asks_the_route(lib):
+    """The engine's three shape conditions, resolved once per storage type from ops.conv_kernel, against the expressions it
+    used to mirror, over the padded widths 64 ... 1280 (and conv_final1's 2 * D2 up to 2560)."""
+    from speech_decoding_amd.engine import EncoderDims, EncoderEngine
+    widths = set()
+    for i, D2 in enumerate(range(32, 1281, 32)):
+        for dt in (torch.float32, torch.bfloat16, torch.float16):
+            d = EncoderDims(208, 27, 270, D2, 64 * (i % 20 + 1), 32)
+            eng = EncoderEngine(d, dt)
+            r = eng._routes()
+            assert r is eng._routes()                                   # asked once
+            assert eng.glu_fused == r.conv2_glu_flat == (d.D2p % 80 == 0), (D2, dt)
+            assert r.f2_wide == (dt != torch.float32 and d.Fp % 256 == 0), (d.F, dt)
+            assert r.f2_dgrad_gelu_flat == (d.F1p % 160 == 0 or d.F1p % 128 == 0), (D2, dt)
+            widths |= {("D2p", d.D2p), ("F1p", d.F1p), ("Fp", d.Fp)}
+    assert widths >= {(n, w) for n in ("D2p", "F1p", "Fp") for w in range(64, 1281, 64)}
+
+
 @pytest.fixture(scope="module")
 def c_probe(lib, tmp_path_factory):
     """What the C compiler makes of sd_amd.h: {"sizeof T": n, "sda_x.field": (offset, size)} for every field of every struct

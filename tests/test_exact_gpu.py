@@ -190,7 +190,7 @@ def test_conv1_tile_flat_and_wide_kernels(ops, shape, regime, dtype):
         assert padding_is_zero(yb, s.B, s.cout, s.T)
         return
     kernels = [("tile", 0)]
-    if Cout_p % 160 == 0 or Cout_p % 128 == 0:
+    if ops.conv_kernel(1, Cout_p, L.CONV_FLAT_TILES, dtype) == L.CONV_KERNEL_FLAT1:
         kernels.append(("flat", L.CONV_FLAT_TILES))
     if wide:
         kernels.append(("wide", L.CONV_WIDE_TILES))

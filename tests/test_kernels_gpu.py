@@ -263,10 +263,12 @@ def test_conv1_flat_tiles_equal_tile_kernel(ops, dtype, cin, cout, T, B):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("cin,cout,T,B", [(1024, 640, 360, 4), (128, 256, 77, 3), (64, 320, 130, 6)])
+@pytest.mark.parametrize("cin,cout,T,B", [(1024, 640, 360, 4), (128, 256, 77, 3), (64, 320, 130, 6), (64, 192, 130, 3)])
 def test_conv1_flat_gelu_backward_epilogue(ops, dtype, cin, cout, T, B):
     """SDA_EPI_GELU_BWD: the data-gradient conv's epilogue multiplies by GELU'(u) and sums the columns = conv, store, then
-    sda_gelu_backward_colsum (bit-equal gradient; the column sums agree to summation order)."""
+    sda_gelu_backward_colsum (bit-equal gradient; the column sums agree to summation order).  `stats` is the leading
+    conv_stats_rows(...) rows of a buffer with four spare rows: every counted row is written, no spare one.  At 192 channels
+    SDA_CONV_FLAT_TILES routes to the tile-per-workgroup kernel (64-channel tiles), whose 6 rows are not conv1_flat's 4."""
     from speech_decoding_amd import lib as L
     g = torch.Generator().manual_seed(12)
     Cip, Cop = L.pad_channels(cin), L.pad_channels(cout)
@@ -277,10 +279,15 @@ def test_conv1_flat_gelu_backward_epilogue(ops, dtype, cin, cout, T, B):
     du_ref = ops.new_rows(B, T, Cop, dtype, DEV)
     cs_ref = ops.gelu_backward_colsum(ub, dg, du_ref, B, T, ops.reduce_scratch(Cop, DEV))
     du = ops.new_rows(B, T, Cop, dtype, DEV)
-    st = torch.full((ops.conv_stats_rows(B, T, 1, Cop, L.CONV_FLAT_TILES | L.EPI_GELU_BWD), 2, Cop), float("nan"), device=DEV)
+    nst = ops.conv_stats_rows(B, T, 1, Cop, L.CONV_FLAT_TILES | L.EPI_GELU_BWD)
+    flat = ops.conv_kernel(1, Cop, L.CONV_FLAT_TILES | L.EPI_GELU_BWD, dtype) == L.CONV_KERNEL_FLAT1
+    assert flat == (cout != 192) and nst == ((B * L.rows_tp(T) + 127) // 128 if flat else B * ops.n_t_tiles(T))
+    whole = torch.full((nst + 4, 2, Cop), float("nan"), device=DEV)
+    st = whole[:nst]
     ops.conv_gemm(xb, wp, du, B=B, T=T, KS=1, dil=0, flags=L.CONV_FLAT_TILES, gelu_bwd_u=ub, stats=st)
     assert torch.equal(du, du_ref)
     assert bool(torch.isfinite(st).all()) and float(st[:, 1].abs().max()) == 0.0
+    assert bool(torch.isnan(whole[nst:]).all())
     t = tol(dtype, B * T)
     np.testing.assert_allclose(st[:, 0].double().sum(0).cpu().numpy(), cs_ref.double().cpu().numpy(), rtol=1e-4, atol=t["atol"] * 1e-2 + 1e-4)
     # the same epilogue in the tile-per-workgroup kernel (statistics rows per (sample, 128-row tile))
