@@ -45,7 +45,9 @@ extern "C" {
                                   sda_gather_windows — training batches gathered from such tracks;
                                   sda_lagged_cov_f32 / sda_lagged_cov_slices / sda_lagged_cov_scratch_floats — the lag products of the
                                   time-lagged ridge baseline;
-                                  sda_conv_kernel — which kernel sda_conv_gemm routes a convolution to, asked instead of mirrored) */
+                                  sda_conv_kernel — which kernel sda_conv_gemm routes a convolution to, asked instead of mirrored;
+                                  sda_clip_label_counts / sda_clip_logits_stats_masked / sda_clip_grad_labels / sda_clip_grad_y_labels /
+                                  sda_clip_ranks_labels — the loss tail with speech labels) */
 #define SDA_ROW_PAD 16
 #define SDA_CH_ALIGN 64
 
@@ -453,6 +455,33 @@ int sda_clip_dz(const void* G, long g_pitch, const void* Y, const void* Z, void*
                 const float* out_scale, int Bm, int Bn, long row_elems, int dtype, void* stream);
 /* cnt[i] = #{local j : logits[i][j] beats diag[i]} (ties: lower global index wins) — Classifier ranks */
 int sda_clip_ranks(const float* logits, const float* diag, int32_t* cnt, int Bm, int Bn, int col0, void* stream);
+/* The loss tail with speech labels (csrc/clip_labels.hip): samples of the global batch that carry the same speech segment are
+ * matches of one another, not negatives.  labels: device int32 [Bg = Bm], one per global sample (row i: labels[i], local column
+ * j: labels[col0 + j]); same_ij = (labels[i] == labels[j]), n_i = sum_j same_ij (sda_clip_label_counts: counts[i], exact).
+ * Every entry point is its unlabelled sibling's twin in shapes, layouts, scaling and the order of its sums, and needs
+ * 0 <= col0, col0 + Bn <= Bm.  mode:
+ *   SDA_CLIP_DUP_POSITIVE  targets T_ij = same_ij / n_i: D_ij = p_row + p_col - 2 T_ij on the statistics of
+ *                          sda_clip_logits_stats; scalars[0] sums (row_lse[col0 + j] - pbar_j) + (col_lse[j] - pbar_j) with
+ *                          pbar_j = (1 / n_j) sum_i same_{i, col0 + j} logits_ij.
+ *   SDA_CLIP_DUP_MASK      entries with same_ij, i != j leave both soft-max denominators (sda_clip_logits_stats_masked: they are
+ *                          skipped in the row (max, sum) and in the column lse; the stored logits stay unmasked) and have
+ *                          D_ij = 0; elsewhere D_ij = p'_row + p'_col - 2 delta_ij and the loss terms are the unlabelled ones.
+ * sda_clip_ranks_labels counts only columns of another label: a repeat of the row's own speech is never a wrong answer. */
+enum { SDA_CLIP_DUP_POSITIVE = 0, SDA_CLIP_DUP_MASK = 1 };
+int sda_clip_label_counts(const int32_t* labels, int32_t* counts, int Bg, void* stream);
+int sda_clip_logits_stats_masked(const float* S, long s_pitch, const float* ysq, const float* zsq, const float* temp,
+                                 const int32_t* labels, float* logits, float* row_max, float* row_sum, float* col_lse,
+                                 float* diag, float* row_lse, int Bm, int Bn, int col0, void* stream);
+int sda_clip_grad_labels(const float* logits, const float* row_lse, const float* col_lse, const float* ysq,
+                         const float* zsq, const float* temp, const int32_t* labels, const int32_t* counts, int mode,
+                         float inv_norm, int col0, void* G, long g_pitch, float* rscale, float* cscale, float* colpart,
+                         float* scalars, int Bm, int Bn, int dtype, void* stream);
+int sda_clip_grad_y_labels(const float* logits, const float* row_lse, const float* col_lse, const float* zsq,
+                           const float* zsq_all, int nz, const int32_t* labels, const int32_t* counts, int mode, int col0,
+                           void* Gy, long gy_pitch, int seg, int seg_pitch, float* part, int Bm, int Bn, int dtype,
+                           void* stream);
+int sda_clip_ranks_labels(const float* logits, const float* diag, const int32_t* labels, int32_t* cnt, int Bm, int Bn,
+                          int col0, void* stream);
 /* Decoding against a candidate bank (csrc/retrieval.hip): top-k selection over the raw fp32 dot products of n query rows
  * against M candidates, one pass over the matrix.  score[i][j] = S[i][j] / max(sqrt(qsq[i]) * sqrt(csq[j]), 1e-8) (the
  * similarity of models.py:223-232; a zero row scores 0), ordered by score descending, on equal scores the lower j first

@@ -4,7 +4,7 @@ the two embedding gradients.  `loss.py` owns the buffers, the gathers and the au
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Optional
 
 import torch
@@ -33,15 +33,22 @@ class ClipCtx:
     zsq: Optional[torch.Tensor] = None
     temp: Optional[torch.Tensor] = None
     inv_norm: float = 0.0
+    # speech labels of the global batch and their class sizes (None: the unlabelled loss), and what a repeat counts as
+    labels: Optional[torch.Tensor] = None
+    counts: Optional[torch.Tensor] = None
+    duplicates: str = "positive"
 
 
 def clip_forward(Yt: torch.Tensor, Zt: torch.Tensor, temp: torch.Tensor, *, Bm: int, Bn: int, T: int, col0: int = 0,
                  reduction: str = "mean", B_global: Optional[int] = None, dist_group=None, want_grad: bool = True,
-                 ysq: Optional[torch.Tensor] = None):
+                 ysq: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, duplicates: str = "positive"):
     """CLIP loss (loss.py:58-79) on RL embeddings: Yt holds the Bm (global) speech rows, Zt the Bn local
     brain rows.  Returns (loss_local_share, logits, ranks_count, ctx).  With `dist_group`, row statistics
-    and the diagonal are merged across ranks so that the negatives span the global batch."""
-    st = clip_block_stats(Yt, Zt, temp, Bm=Bm, Bn=Bn, T=T, col0=col0, ysq=ysq)
+    and the diagonal are merged across ranks so that the negatives span the global batch.
+    `labels` (device int32 [Bm], one per global sample): samples with one label carry the same speech and are matches of one
+    another: extra positives (duplicates="positive") or left out of the soft-max denominators ("mask").  None: the unlabelled
+    loss, launch for launch."""
+    st = clip_block_stats(Yt, Zt, temp, Bm=Bm, Bn=Bn, T=T, col0=col0, ysq=ysq, labels=labels, duplicates=duplicates)
     if dist_group is None:                       # one process: the block IS the whole matrix, its row lse came with the logits
         row_lse, diag = st.row_lse, st.diag
     else:
@@ -68,11 +75,17 @@ class ClipBlockStats:
     col_lse: torch.Tensor
     diag: torch.Tensor
     row_lse: torch.Tensor          # lse of each row over this block's columns only
+    labels: Optional[torch.Tensor] = None
+    duplicates: str = "positive"
 
 
-def clip_block_stats(Yt, Zt, temp, *, Bm: int, Bn: int, T: int, col0: int = 0, ysq=None) -> ClipBlockStats:
+def clip_block_stats(Yt, Zt, temp, *, Bm: int, Bn: int, T: int, col0: int = 0, ysq=None, labels=None,
+                     duplicates: str = "positive") -> ClipBlockStats:
     """First half of clip_forward: norms, the (Bm x Bn) logits block of this rank's brain columns, per-row (max, sum exp)
-    over the block, per-column lse over all rows, the positives' logits.  Rank-local: no collective."""
+    over the block, per-column lse over all rows, the positives' logits.  Rank-local: no collective.  With labels and
+    duplicates="mask" the statistics leave out the repeats of a sample's own speech; "positive" keeps the unlabelled ones."""
+    if labels is not None:
+        ops.clip_dup_code(duplicates)             # refused before the first launch
     Fp = Zt.shape[1]
     row_elems = L.rows_tp(T) * Fp
     if ysq is None:                              # (under DP the caller gathers the per-rank norms instead)
@@ -81,23 +94,39 @@ def clip_block_stats(Yt, Zt, temp, *, Bm: int, Bn: int, T: int, col0: int = 0, y
     if zsq is None:
         zsq = ops.rows_sumsq(Zt, Bn, row_elems, row_elems)
     S = ops.matmul_nt_splitk(Yt, Zt, Bm, Bn, row_elems, row_elems)
-    logits, row_max, row_sum, col_lse, diag, row_lse = ops.clip_logits_stats(S, ysq, zsq, temp, Bm, Bn, col0)
-    return ClipBlockStats(Yt, Zt, temp, Bm, Bn, col0, row_elems, ysq, zsq, logits, row_max, row_sum, col_lse, diag, row_lse)
+    if labels is not None and duplicates == "mask":
+        logits, row_max, row_sum, col_lse, diag, row_lse = ops.clip_logits_stats_masked(S, ysq, zsq, temp, labels, Bm, Bn, col0)
+    else:
+        logits, row_max, row_sum, col_lse, diag, row_lse = ops.clip_logits_stats(S, ysq, zsq, temp, Bm, Bn, col0)
+    return ClipBlockStats(Yt, Zt, temp, Bm, Bn, col0, row_elems, ysq, zsq, logits, row_max, row_sum, col_lse, diag, row_lse,
+                          labels, duplicates)
 
 
-def clip_block_finish(st: ClipBlockStats, row_lse, diag, *, reduction: str = "mean", B_global: Optional[int] = None):
+def clip_block_finish(st: ClipBlockStats, row_lse, diag, *, reduction: str = "mean", B_global: Optional[int] = None,
+                      labels: Optional[torch.Tensor] = None, duplicates: Optional[str] = None):
     """Second half, given the row lse over the columns of ALL ranks and the positives' logits (after the merge): this rank's
-    share of the loss and of d loss / d temp, the gradient coefficient matrix, the retrieval rank counts."""
+    share of the loss and of d loss / d temp, the gradient coefficient matrix, the retrieval rank counts.  `labels` /
+    `duplicates`: default to those the statistics were taken with (they must be the same in mask mode)."""
+    if labels is not None or duplicates is not None:
+        st = replace(st, labels=st.labels if labels is None else labels, duplicates=duplicates or st.duplicates)
     Yt, Zt, temp, Bm, Bn, col0, row_elems = st.Yt, st.Zt, st.temp, st.Bm, st.Bn, st.col0, st.row_elems
     logits, col_lse, ysq, zsq = st.logits, st.col_lse, st.ysq, st.zsq
     Bg = B_global if B_global is not None else Bm
     inv_norm = 1.0 / (2.0 * Bg) if reduction == "mean" else 0.5
     # G is an MFMA operand (16-bit in the 16-bit modes): it holds the O(1) part of dL/dlogits * exp(temp) / (|Y||Z|), the
     # rest — 1e-8 at the 8-GPU shapes, far outside fp16 — comes back as a per-column fp32 factor in the dZ GEMM's epilogue
-    G, rscale, cscale, scalars = ops.clip_grad(logits, row_lse, col_lse, ysq, zsq, temp, inv_norm, col0, Yt.dtype)
-    cnt = ops.clip_ranks(logits, diag, col0)
+    labels, counts = st.labels, None
+    if labels is None:
+        G, rscale, cscale, scalars = ops.clip_grad(logits, row_lse, col_lse, ysq, zsq, temp, inv_norm, col0, Yt.dtype)
+        cnt = ops.clip_ranks(logits, diag, col0)
+    else:
+        counts = ops.clip_label_counts(labels)     # the one extra launch; the others replace their siblings one for one
+        G, rscale, cscale, scalars = ops.clip_grad_labels(logits, row_lse, col_lse, ysq, zsq, temp, labels, counts, st.duplicates,
+                                                          inv_norm, col0, Yt.dtype)
+        cnt = ops.clip_ranks_labels(logits, diag, labels, col0)
     ctx = ClipCtx(Bm=Bm, Bn=Bn, col0=col0, G=G, rscale=rscale, Yt=Yt, Zt=Zt, row_elems=row_elems, dtemp=scalars[1:2],
-                  cscale=cscale, logits=logits, row_lse=row_lse, col_lse=col_lse, ysq=ysq, zsq=zsq, temp=temp, inv_norm=inv_norm)
+                  cscale=cscale, logits=logits, row_lse=row_lse, col_lse=col_lse, ysq=ysq, zsq=zsq, temp=temp, inv_norm=inv_norm,
+                  labels=labels, counts=counts, duplicates=st.duplicates)
     return scalars[0:1], logits, cnt, ctx
 
 
@@ -106,9 +135,23 @@ def clip_backward(ctx: ClipCtx, dZt: torch.Tensor, dloss: Optional[torch.Tensor]
     return ops.clip_dz(ctx.G, ctx.Yt, ctx.Zt, dZt, ctx.rscale, ctx.cscale, Bm=ctx.Bm, Bn=ctx.Bn, row_elems=ctx.row_elems, out_scale=dloss)
 
 
-def clip_backward_y(ctx: ClipCtx, dYt: torch.Tensor, dloss: Optional[torch.Tensor] = None) -> torch.Tensor:
+def clip_grad_y_coeffs(ctx: ClipCtx, zsq_all: torch.Tensor, dtype, **layout):
+    """(Gy, part) of the block behind `ctx`: the labelled twin when the forward had labels."""
+    if ctx.labels is None:
+        return ops.clip_grad_y(ctx.logits, ctx.row_lse, ctx.col_lse, ctx.zsq, zsq_all, ctx.col0, dtype, **layout)
+    return ops.clip_grad_y_labels(ctx.logits, ctx.row_lse, ctx.col_lse, ctx.zsq, zsq_all, ctx.labels, ctx.counts, ctx.duplicates,
+                                  ctx.col0, dtype, **layout)
+
+
+def clip_backward_y(ctx: ClipCtx, dYt: torch.Tensor, dloss: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+                    duplicates: Optional[str] = None) -> torch.Tensor:
     """dY = dloss * (diag(c_y) Gy^T Z - diag(r_y) Y) on one GPU (the block is the whole matrix): the dZ product with the roles of
-    the two embeddings exchanged, on the same GEMM family (no new GEMM kernel)."""
-    Gy, part = ops.clip_grad_y(ctx.logits, ctx.row_lse, ctx.col_lse, ctx.zsq, ctx.zsq, ctx.col0, ctx.Zt.dtype)
+    the two embeddings exchanged, on the same GEMM family (no new GEMM kernel).  `labels` / `duplicates`: default to the
+    forward's, which `ctx` carries with their class sizes."""
+    if labels is not None and labels is not ctx.labels:
+        ctx = replace(ctx, labels=labels, counts=ops.clip_label_counts(labels))
+    if duplicates is not None:
+        ctx = replace(ctx, duplicates=duplicates)
+    Gy, part = clip_grad_y_coeffs(ctx, ctx.zsq, ctx.Zt.dtype)
     rscale_y, cscale_y = ops.clip_grad_y_finish(part, ctx.ysq, ctx.zsq, ctx.temp, ctx.inv_norm, 0, ctx.Bm)
     return ops.clip_dz(Gy, ctx.Zt, ctx.Yt, dYt, rscale_y, cscale_y, Bm=ctx.Bn, Bn=ctx.Bm, row_elems=ctx.row_elems, out_scale=dloss)

@@ -5,21 +5,6 @@
 
 namespace sda {
 
-__device__ inline float block_sum(float v, float* sh) {     // 256 threads; result broadcast
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return sh[0] + sh[1] + sh[2] + sh[3];
-}
-__device__ inline float block_max(float v, float* sh) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return max_nan(max_nan(sh[0], sh[1]), max_nan(sh[2], sh[3]));
-}
-
 // SpatialAttention weights, forward.  a[o][c] = sum_m Re z[o][m] cos[m][c] + Im z[o][m] sin[m][c].
 // Stage 1: block (row group of SA_R rows, m-chunk of SA_MC) accumulates partial sums for all sensors; every
 // table element it loads feeds SA_R rows (the tables are the traffic: 2 x K2 x C floats).  Stage 2: one block
@@ -321,6 +306,10 @@ __global__ void clip_scalars_kernel(const float* __restrict__ colpart, float inv
   for (int k = 0; k < 64; ++k) { l += pl[k]; dt += pd[k]; }
   scalars[0] = (float)(l * (double)inv_norm);
   scalars[1] = (float)dt;
+}
+
+void launch_clip_scalars(const float* colpart, float inv_norm, float* scalars, int Bn, hipStream_t stream) {
+  hipLaunchKernelGGL(clip_scalars_kernel, dim3(1), dim3(64), 0, stream, colpart, inv_norm, scalars, Bn);
 }
 
 // block per row i: number of local columns whose logit beats the row's positive (ties: lower index wins)

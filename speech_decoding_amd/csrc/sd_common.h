@@ -308,6 +308,21 @@ __device__ inline float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = max_nan(v, __shfl_xor(v, o));
   return v;
 }
+// Ordered reductions of a 256-thread block over sh[4] (sa_loss.hip, clip_labels.hip): the four wave results in wave order.
+__device__ inline float block_sum(float v, float* sh) {     // 256 threads; result broadcast
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return sh[0] + sh[1] + sh[2] + sh[3];
+}
+__device__ inline float block_max(float v, float* sh) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return max_nan(max_nan(sh[0], sh[1]), max_nan(sh[2], sh[3]));
+}
 
 // LDS-DMA (global_load_lds_dwordx4) issued through inline asm.  hipcc treats the builtin form as an LDS
 // write that may alias every later ds_read of the same array and drains it with s_waitcnt vmcnt(0) before the
@@ -353,6 +368,9 @@ template <typename K> int reserve_lds_once(unsigned long long& done, K* kern, in
 // CUs a persistent grid may count on: the current device's CU count, or the limit the caller set for launches that go to
 // a CU-masked stream (sda_set_cu_limit; thread-local, 0 = none)
 int launch_cus();
+// sa_loss.hip: scalars[0] = inv_norm * sum_j colpart[2 j], scalars[1] = sum_j colpart[2 j + 1] (fp64, fixed order), for the
+// loss tails of other files that fill colpart
+void launch_clip_scalars(const float* colpart, float inv_norm, float* scalars, int Bn, hipStream_t stream);
 
 }  // namespace sda
 

@@ -106,23 +106,39 @@ class _ResidentEmbeddings:
     _Yt = None                # row-layout table in the compute dtype (set by pack_embeddings only)
     drawn_as: str             # "rec" / "subjects"; draw_for(ii) makes one such draw from the feed's generator per segment of ii
 
-    def batches(self, sampler, index_map=None) -> Iterator[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+    def batches(self, sampler, index_map=None, with_ids: bool = False) -> Iterator[Tuple[torch.Tensor, ...]]:
         """One (X, Y, subject_idxs) per batch of `sampler`.  With a ShardedRandomSampler of more than one rank the draw (the
         recording of a segment, the subject of a chunk) is made for EVERY item of the global batch on every rank from the same
         generator state and the rank keeps its slice — the union over the ranks is exactly the batch a single process would have
         drawn, and no two ranks share a draw.  `index_map`: optional array mapping sampler indices to segment indices (a train
-        split)."""
+        split).  `with_ids`: yield the reference's 4-tuple (X, Y, subject_idxs, chunkIDs) instead (train.py:179-183), chunkIDs =
+        speech_ids() of the batch's segments as a host int64 tensor — what CLIPLoss.forward takes as `labels`."""
+        def item(ii, **drawn):
+            out = self.batch(ii, **drawn)
+            return (*out, torch.from_numpy(self.speech_ids(ii))) if with_ids else out
+
         if hasattr(sampler, "global_batches") and getattr(sampler, "world", 1) > 1:
             per = sampler.batch_size // sampler.world
             lo = sampler.rank * per
             for gidx in sampler.global_batches():
                 g = gidx.numpy() if index_map is None else np.asarray(index_map)[gidx.numpy()]
                 drawn = self.draw_for(g)
-                yield self.batch(g[lo: lo + per], **{self.drawn_as: drawn[lo: lo + per]})
+                yield item(g[lo: lo + per], **{self.drawn_as: drawn[lo: lo + per]})
             return
         for idx in sampler:
             i = idx.numpy() if isinstance(idx, torch.Tensor) else np.asarray(idx)
-            yield self.batch(i if index_map is None else np.asarray(index_map)[i])
+            yield item(i if index_map is None else np.asarray(index_map)[i])
+
+    def speech_ids(self, idx) -> np.ndarray:
+        """One int64 id per segment of `idx` that is equal for two segments exactly when they carry the same speech: the
+        segment (chunk) index itself where Y holds materialised segments; for a WindowBank-backed feed the window's first row in
+        the bank's table, so two candidates cut from the same track at the same start share an id."""
+        ii = np.asarray(torch.as_tensor(idx, dtype=torch.int64).numpy(), dtype=np.int64).reshape(-1)
+        bank = self._bank()
+        if bank is None:
+            return ii.copy()
+        self._check_segments(ii)
+        return bank.starts_host[ii].astype(np.int64)
 
     def _bank(self):
         """The WindowBank behind Y, or None when Y holds materialised segments."""

@@ -15,6 +15,7 @@ from __future__ import annotations
 import weakref
 from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -22,7 +23,7 @@ from . import clip
 from . import lib as L
 from . import ops
 
-_rank_cache = []          # [(weakref(Y), weakref(Z), Y._version, Z._version, ranks)] from the last CLIPLoss forward
+_rank_cache = []          # [(weakref(Y), weakref(Z), Y._version, Z._version, ranks, labels key)] from the last CLIPLoss forward
 
 
 class RingSlot:
@@ -111,19 +112,87 @@ class LossState:
 _DEFAULT_STATE = LossState()      # for the module-level helpers called without a CLIPLoss instance
 
 
-def _cache_ranks(Y, Z, cnt):
+def _cache_ranks(Y, Z, cnt, labels_key=None):
     _rank_cache.clear()
-    _rank_cache.append((weakref.ref(Y), weakref.ref(Z), Y._version, Z._version, cnt))
+    _rank_cache.append((weakref.ref(Y), weakref.ref(Z), Y._version, Z._version, cnt, labels_key))
 
 
-def _cached_ranks(Y, Z):
+def _cached_ranks(Y, Z, labels_key=None):
     """Ranks of the last CLIPLoss forward — valid for the SAME two tensor objects while neither has been written in place
     since (torch's version counters, as ops.ROW_NORMS checks them): an edit of Z between loss_func(Y, Z) and
-    classifier(Z, Y) sends the classifier back to computing its own ranks."""
-    for wy, wz, vy, vz, cnt in _rank_cache:
-        if wy() is Y and wz() is Z and Y._version == vy and Z._version == vz:
+    classifier(Z, Y) sends the classifier back to computing its own ranks.  Ranks counted with speech labels serve a query
+    with the same labels only, unlabelled ranks an unlabelled query only."""
+    for wy, wz, vy, vz, cnt, key in _rank_cache:
+        if wy() is Y and wz() is Z and Y._version == vy and Z._version == vz and _same_labels_key(key, labels_key):
             return cnt
     return None
+
+
+class SpeechLabels(NamedTuple):
+    """The local samples' speech ids as the kernels take them, and what identifies their values without a device read."""
+    dev: torch.Tensor            # int32 [B] on the device
+    host: Optional[np.ndarray]   # the same values on the host (None for a device tensor handed in as int32)
+    key: object                  # bytes of the values, or ("tensor", weakref, version) of an int32 device tensor
+
+
+def _same_labels_key(a, b) -> bool:
+    if a is None or b is None:
+        return a is None and b is None
+    if isinstance(a, bytes) or isinstance(b, bytes):
+        return isinstance(a, bytes) and isinstance(b, bytes) and a == b
+    return a[1]() is not None and a[1]() is b[1]() and a[2] == b[2]
+
+
+def speech_labels(labels, B: int, device) -> Optional[SpeechLabels]:
+    """Check and upload the speech ids of the B local samples: a host sequence, a numpy array or a torch int32 / int64 tensor of
+    length B whose values fit int32.  A wrong length, a non-integer dtype or a value outside int32 raises ValueError before
+    anything is launched.  Host data and int64 tensors are checked on the host (an int64 device tensor costs one copy back:
+    hand in int32 to avoid it); an int32 device tensor is taken as it is."""
+    if labels is None:
+        return None
+    if isinstance(labels, SpeechLabels):
+        if labels.dev.numel() != B:
+            raise ValueError(f"labels: expected {B} speech ids (one per local sample), got {labels.dev.numel()}")
+        return labels
+    if isinstance(labels, torch.Tensor):
+        if labels.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"labels: expected an int32 or int64 tensor, got {labels.dtype}")
+        if labels.dim() != 1 or labels.numel() != B:
+            raise ValueError(f"labels: expected {B} speech ids (one per local sample), got shape {tuple(labels.shape)}")
+        if labels.dtype == torch.int32 and labels.is_cuda:
+            return SpeechLabels(labels.detach().contiguous(), None, ("tensor", weakref.ref(labels), labels._version))
+        labels = labels.detach().cpu().numpy()
+    a = np.asarray(labels)
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"labels: expected integer speech ids, got dtype {a.dtype}")
+    if a.ndim != 1 or a.size != B:
+        raise ValueError(f"labels: expected {B} speech ids (one per local sample), got shape {a.shape}")
+    if int(a.min()) < -2 ** 31 or int(a.max()) > 2 ** 31 - 1:
+        raise ValueError("labels: speech ids must fit int32")
+    a32 = np.ascontiguousarray(a.astype(np.int32))
+    return SpeechLabels(ops.upload_small(a32, device), a32, a32.tobytes())
+
+
+def gather_labels(lab: SpeechLabels, B: int, group) -> torch.Tensor:
+    """The labels of the global batch in rank order (device int32 [B_global]): one small all-gather on the side group that
+    gathers the speech rows.  In an emulated world the stand-in rows get labels that match nothing: the local ids are renumbered
+    from 0 (in the order of their values) and every stand-in row gets an id of its own behind them."""
+    if group is None:
+        return lab.dev
+    import torch.distributed as dist
+    from .distributed import emulated_world, side_group
+    world = dist.get_world_size(group)
+    local = lab.dev
+    held = emulated_world() if world == 1 and emulated_world() > 1 else world
+    if held != world:
+        host = lab.host if lab.host is not None else lab.dev.cpu().numpy()
+        _, dense = np.unique(host, return_inverse=True)
+        local = ops.upload_small(np.ascontiguousarray(dense.astype(np.int32)), lab.dev.device)
+    out = torch.empty(B * held, dtype=torch.int32, device=local.device)
+    dist.all_gather_into_tensor(out[: B * world], local, group=side_group("gather", group))
+    if held != world:
+        out[B:] = torch.arange(B, B * held, dtype=torch.int32, device=local.device)
+    return out
 
 
 _rows_base = ops.rows_base      # its name while it lived here: kept for code outside this tree that imported it; use ops.rows_base
@@ -277,9 +346,10 @@ _RECYCLED = ("CLIPLoss.backward: the packed {what} rows of this forward were rec
 
 class _ClipFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, module: "CLIPLoss", Y, Z, temp):
+    def forward(ctx, module: "CLIPLoss", Y, Z, temp, labels=None):
         import torch.distributed as dist
         B, F, T = Z.shape
+        lab = speech_labels(labels, B, Z.device)    # refused here, before the first launch, when they are malformed
         dtype = Z.dtype if Z.dtype in ops.COMPUTE_DTYPES else torch.float32
         Zt = as_rows(Z, B, F, T, dtype, "y (brain embeddings)")
         group = _dist_group() if module.global_negatives else None
@@ -303,8 +373,10 @@ class _ClipFn(torch.autograd.Function):
         if yg is None:
             Yt_local, slot = _pack_ring(state, Y, B, F, T, dtype, "x (speech embeddings)", "loss.Y")
             yg = gather_speech_rows(Yt_local, B, T, group, state=state, slot=slot)
+        lab_all = None if lab is None else gather_labels(lab, B, group)
         loss, logits, cnt, cctx = clip.clip_forward(yg.rows, Zt, temp.detach(), Bm=yg.n, Bn=B, T=T, col0=yg.col0,
-                                                    reduction=module.reduction, B_global=yg.n, dist_group=group, ysq=yg.sq)
+                                                    reduction=module.reduction, B_global=yg.n, dist_group=group, ysq=yg.sq,
+                                                    labels=lab_all, duplicates=module.duplicates)
         ctx.z_gather = None
         if want_y and group is not None:
             # the speech-side gradient contracts over the brain rows of ALL ranks: gather them (and their norms) now, behind
@@ -320,7 +392,7 @@ class _ClipFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)            # no zero-filled gradient for the (non-differentiable) logits output
         ctx.z_requires_grad = Z.requires_grad
         ctx.y_requires_grad, ctx.y_rows, ctx.y_dtype = want_y, y_rows, Y.dtype
-        _cache_ranks(Y, Z, cnt[yg.col0: yg.col0 + B])
+        _cache_ranks(Y, Z, cnt[yg.col0: yg.col0 + B], None if lab is None else lab.key)
         ctx.mark_non_differentiable(logits)
         return loss.reshape(()), logits
 
@@ -330,7 +402,7 @@ class _ClipFn(torch.autograd.Function):
         B, F, T = ctx.shape
         dZ = dY = None
         if dloss is None:                           # (the loss itself took no part in what was differentiated)
-            return None, None, None, None
+            return None, None, None, None, None
         scale = dloss.to(torch.float32)
         if (ctx.z_requires_grad or ctx.y_requires_grad) and ctx.y_slot is not None and not ctx.y_slot.valid():
             raise L.SdaError(_RECYCLED.format(what="speech"))
@@ -344,7 +416,7 @@ class _ClipFn(torch.autograd.Function):
             dYt = _clip_dy(ctx, scale.reshape(1).contiguous())
             dY = ops.rows_view(dYt, B, F, T) if ctx.y_rows else ops.unpack_rows(dYt, B, F, T, ctx.y_dtype)
         dtemp = ops.scalar_mul(c.dtemp, scale.reshape(1))
-        return None, dY, dZ, dtemp
+        return None, dY, dZ, dtemp, None
 
 
 def _clip_dy(ctx, scale: torch.Tensor) -> torch.Tensor:
@@ -366,8 +438,7 @@ def _clip_dy(ctx, scale: torch.Tensor) -> torch.Tensor:
     if not zg.slot.valid():
         raise L.SdaError(_RECYCLED.format(what="brain"))
     Bg, sp = c.Bm, L.pad_channels(B)
-    Gy, part = ops.clip_grad_y(c.logits, c.row_lse, c.col_lse, c.zsq, zg.sq, c.col0, ctx.dtype, seg=B, seg_pitch=sp,
-                               groups=world)
+    Gy, part = clip.clip_grad_y_coeffs(c, zg.sq, ctx.dtype, seg=B, seg_pitch=sp, groups=world)
     Gall = torch.empty((Bg + 1, world * sp), dtype=ctx.dtype, device=Gy.device)
     ops.fill_zero_(Gall[Bg])                        # the zero row behind the contraction
     pall = torch.empty((world * part.shape[0], Bg), dtype=torch.float32, device=Gy.device)
@@ -388,6 +459,11 @@ class CLIPLoss(nn.Module):
         self.reduction = str(args.reduction)
         if self.reduction not in ("mean", "sum"):
             raise ValueError("reduction must be 'mean' or 'sum'")
+        # what a repeated speech segment in a batch counts as when forward() is given labels: a further positive of its
+        # partners ("positive") or no negative of them ("mask")
+        get = getattr(args, "get", None)
+        self.duplicates = str(get("clip_duplicates", "positive") if get else getattr(args, "clip_duplicates", "positive"))
+        ops.clip_dup_code(self.duplicates)          # any other value: ValueError
         self.temp = nn.Parameter(torch.tensor([float(args.init_temperature)]))
         self.global_negatives = True
         self.last_logits: Optional[torch.Tensor] = None
@@ -405,18 +481,23 @@ class CLIPLoss(nn.Module):
         """Drop the persistent packed-speech buffers (e.g. between a training and an evaluation phase)."""
         self._state.clear()
 
-    def forward(self, x, y, fast=True, return_logits=False):
+    def forward(self, x, y, fast=True, return_logits=False, labels=None):
+        """`labels`: the speech id of each local sample (a host sequence, a numpy array or an int32 / int64 tensor of length B):
+        samples of the global batch with one id carry the same speech segment and are treated as `self.duplicates` says.
+        None: every sample is its own class — the reference's loss."""
         batch_size = x.size(0)
         assert batch_size > 1, "Batch size must be greater than 1."               # loss.py:40
+        if labels is not None:
+            labels = speech_labels(labels, batch_size, y.device)
         if not fast:
             # loss.py:46-50: logits[i][j] = cos(y_i, x_j) — the fast way's matrix TRANSPOSED and without the learned
             # temperature (which then receives no gradient).  The symmetric loss is the same function of it, so the same
             # kernels run with a zero log-temperature; only the returned logits are turned.
             zero = torch.zeros(1, dtype=torch.float32, device=self.temp.device)
-            loss, logits = _ClipFn.apply(self, x, y, zero)
+            loss, logits = _ClipFn.apply(self, x, y, zero, labels)
             self.last_logits = logits
             return (logits.t(), loss) if return_logits else loss
-        loss, logits = _ClipFn.apply(self, x, y, self.temp)
+        loss, logits = _ClipFn.apply(self, x, y, self.temp, labels)
         self.last_logits = logits
         if return_logits:
             return logits, loss
@@ -424,21 +505,24 @@ class CLIPLoss(nn.Module):
 
 
 @torch.no_grad()
-def retrieval_ranks(Y: torch.Tensor, Z: torch.Tensor, global_candidates: bool = True) -> torch.Tensor:
+def retrieval_ranks(Y: torch.Tensor, Z: torch.Tensor, global_candidates: bool = True, labels=None) -> torch.Tensor:
     """Rank of each speech row's own brain column (0 = top-1).  Reuses the ranks computed by the last
-    CLIPLoss forward on the same tensors; otherwise runs the similarity GEMM + rank kernel."""
-    hit = _cached_ranks(Y, Z)
+    CLIPLoss forward on the same tensors; otherwise runs the similarity GEMM + rank kernel.  With `labels` (the local samples'
+    speech ids, as CLIPLoss.forward takes them) a column that carries the row's own speech never counts against it."""
+    B, F, T = Z.shape
+    lab = speech_labels(labels, B, Z.device)
+    hit = _cached_ranks(Y, Z, None if lab is None else lab.key)
     if hit is not None:
         return hit
-    B, F, T = Z.shape
     dtype = Z.dtype if Z.dtype in ops.COMPUTE_DTYPES else torch.float32
     Zt = as_rows(Z, B, F, T, dtype, "Z")
     Yt = as_rows(Y, B, F, T, dtype, "Y")
     temp = torch.zeros(1, dtype=torch.float32, device=Zt.device)
     group = _dist_group() if global_candidates else None     # under data parallelism: the GLOBAL batch
     yg = gather_speech_rows(Yt, B, T, group)
+    lab_all = None if lab is None else gather_labels(lab, B, group)
     _, _, cnt, _ = clip.clip_forward(yg.rows, Zt, temp, Bm=yg.n, Bn=B, T=T, col0=yg.col0, B_global=yg.n, dist_group=group,
-                                     ysq=yg.sq)
+                                     ysq=yg.sq, labels=lab_all)
     if group is not None:
         import torch.distributed as dist
         dist.all_reduce(cnt, group=group)

@@ -477,12 +477,14 @@ class Classifier(nn.Module):
         self.global_candidates = True       # under torch.distributed: rank against the global batch
 
     @torch.no_grad()
-    def ranks(self, Z: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+    def ranks(self, Z: torch.Tensor, Y: torch.Tensor, labels=None) -> torch.Tensor:
         """Rank of every speech row's own brain column (0 = top-1) as a DEVICE tensor: what forward() reduces to the two
-        accuracies, without the host read-back (a training loop can collect these and read them once per epoch)."""
+        accuracies, without the host read-back (a training loop can collect these and read them once per epoch).
+        `labels`: the local samples' speech ids (as CLIPLoss.forward takes them); a brain column that heard the row's own
+        speech segment then never counts as a wrong answer."""
         if Z.size(0) < 10:
             raise RuntimeError("selected index k out of range")      # torch.topk(…, 10) on fewer than 10 columns
-        return _loss.retrieval_ranks(Y, Z, self.global_candidates)
+        return _loss.retrieval_ranks(Y, Z, self.global_candidates, labels=labels)
 
     @torch.no_grad()
     def decode(self, Z: torch.Tensor, bank, k: int = 10, labels=None):
@@ -504,6 +506,6 @@ class Classifier(nn.Module):
         return retrieve_classes(Z, bank, classes, **kw)
 
     @torch.no_grad()
-    def forward(self, Z: torch.Tensor, Y: torch.Tensor, test: bool = False):
-        cnt = self.ranks(Z, Y).cpu().numpy()
+    def forward(self, Z: torch.Tensor, Y: torch.Tensor, test: bool = False, labels=None):
+        cnt = self.ranks(Z, Y, labels=labels).cpu().numpy()
         return float((cnt == 0).mean()), np.mean(cnt < 10)

@@ -1035,6 +1035,87 @@ def clip_ranks(logits, diag, col0):
     return cnt
 
 
+CLIP_DUPLICATES = {"positive": L.CLIP_DUP_POSITIVE, "mask": L.CLIP_DUP_MASK}
+
+
+def clip_dup_code(duplicates: str) -> int:
+    if duplicates not in CLIP_DUPLICATES:
+        raise ValueError(f"duplicates must be one of {sorted(CLIP_DUPLICATES)}, got {duplicates!r}")
+    return CLIP_DUPLICATES[duplicates]
+
+
+def _need_labels(who: str, labels, n: int, *more):
+    for name, t in (("labels", labels), *more):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n):
+            raise L.SdaError(f"{who}: {name} must be a contiguous device int32 tensor of {n} values (one per global sample)")
+
+
+def clip_label_counts(labels: torch.Tensor) -> torch.Tensor:
+    """n_i = the number of samples of the global batch that carry sample i's speech label (itself included), int32 [Bg]."""
+    _need_labels("clip_label_counts", labels, labels.numel() if isinstance(labels, torch.Tensor) else 0)
+    counts = torch.empty_like(labels)
+    L.check(L.load().sda_clip_label_counts(_p(labels), _p(counts), labels.numel(), _st()), "clip_label_counts")
+    return counts
+
+
+def clip_logits_stats_masked(S, ysq, zsq, temp, labels, Bm, Bn, col0):
+    """clip_logits_stats with the repeats of a sample's own speech left out of both soft-max denominators (duplicates="mask")."""
+    _need_labels("clip_logits_stats_masked", labels, Bm)
+    dev = S.device
+    logits = torch.empty((Bm, Bn), dtype=torch.float32, device=dev)
+    st3 = torch.empty((3, Bm), dtype=torch.float32, device=dev)          # one buffer: what the all-gather of the row statistics sends
+    row_max, row_sum, diag = st3[0], st3[1], st3[2]
+    col_lse = torch.empty(Bn, dtype=torch.float32, device=dev)
+    row_lse = torch.empty(Bm, dtype=torch.float32, device=dev)
+    L.check(L.load().sda_clip_logits_stats_masked(_p(S), S.shape[1], _p(ysq), _p(zsq), _p(temp), _p(labels), _p(logits), _p(row_max),
+                                                  _p(row_sum), _p(col_lse), _p(diag), _p(row_lse), Bm, Bn, col0, _st()),
+            "clip_logits_stats_masked")
+    return logits, row_max, row_sum, col_lse, diag, row_lse
+
+
+def clip_grad_labels(logits, row_lse, col_lse, ysq, zsq, temp, labels, counts, duplicates, inv_norm, col0, dtype):
+    """clip_grad with the labelled coefficient D (sda_clip_grad_labels): the same four results in the same layouts."""
+    Bm, Bn = logits.shape
+    mode = clip_dup_code(duplicates)
+    _need_labels("clip_grad_labels", labels, Bm, ("counts", counts))
+    dev = logits.device
+    G = torch.empty((Bm + 1, L.pad_channels(Bn)), dtype=dtype, device=dev)      # zero row and pad columns written by the kernel
+    rscale = torch.empty(Bn, dtype=torch.float32, device=dev)
+    cscale = torch.empty(Bn, dtype=torch.float32, device=dev)
+    colpart = torch.empty(2 * Bn, dtype=torch.float32, device=dev)
+    scalars = torch.empty(2, dtype=torch.float32, device=dev)
+    L.check(L.load().sda_clip_grad_labels(_p(logits), _p(row_lse), _p(col_lse), _p(ysq), _p(zsq), _p(temp), _p(labels), _p(counts), mode,
+                                          float(inv_norm), col0, _p(G), G.shape[1], _p(rscale), _p(cscale), _p(colpart), _p(scalars),
+                                          Bm, Bn, dt_code(dtype), _st()), "clip_grad_labels")
+    return G, rscale, cscale, scalars
+
+
+def clip_grad_y_labels(logits, row_lse, col_lse, zsq, zsq_all, labels, counts, duplicates, col0, dtype, *, seg=None, seg_pitch=None,
+                       groups=1):
+    """clip_grad_y with the labelled coefficient D (sda_clip_grad_y_labels): Gy and the partials in the same layouts."""
+    Bm, Bn = logits.shape
+    mode = clip_dup_code(duplicates)
+    _need_labels("clip_grad_y_labels", labels, Bm, ("counts", counts))
+    seg = Bm if seg is None else seg
+    seg_pitch = L.pad_channels(seg) if seg_pitch is None else seg_pitch
+    dev = logits.device
+    Gy = torch.empty((Bn + 1, groups * seg_pitch), dtype=dtype, device=dev)     # every element is written by the kernel
+    part = torch.empty(((Bn + 63) // 64, Bm), dtype=torch.float32, device=dev)
+    L.check(L.load().sda_clip_grad_y_labels(_p(logits), _p(row_lse), _p(col_lse), _p(zsq), _p(zsq_all), zsq_all.numel(), _p(labels),
+                                            _p(counts), mode, col0, _p(Gy), Gy.shape[1], seg, seg_pitch, _p(part), Bm, Bn,
+                                            dt_code(dtype), _st()), "clip_grad_y_labels")
+    return Gy, part
+
+
+def clip_ranks_labels(logits, diag, labels, col0):
+    """clip_ranks where the columns that carry the row's own speech label are never counted as beating its positive."""
+    Bm, Bn = logits.shape
+    _need_labels("clip_ranks_labels", labels, Bm)
+    cnt = torch.empty(Bm, dtype=torch.int32, device=logits.device)
+    L.check(L.load().sda_clip_ranks_labels(_p(logits), _p(diag), _p(labels), _p(cnt), Bm, Bn, col0, _st()), "clip_ranks_labels")
+    return cnt
+
+
 def retrieval_scores_floats(n: int, M: int, chunk_cols: int) -> int:
     """Floats of the chunk-major score matrix sda_retrieval_select reads for n query rows against M candidates."""
     r = L.load().sda_retrieval_scores_floats(n, M, chunk_cols)

@@ -27,6 +27,9 @@ Layout: `build_data` makes the synthetic data of a `data=` kind (the feed, or No
 epoch seed and test shard are written there once), `make_backward_and_step` the update, `run` the loop around them.
 `max_grad_norm=1.0` clips the gradients by their global norm and `fp16_guard=device` moves fp16's overflow guard off the host;
 either one runs the step through `make_guarded_step` (GuardedAdam: norm, guard, clipping and Adam on the device, no read-back).
+`clip_duplicates=positive|mask` (default `ignore`: the reference's loss) hands the feed's speech ids to the loss and the
+accuracies: the sampler draws with replacement, so a batch can hold one speech segment twice under two brain recordings, and the
+repeat then counts as a further positive (or as no negative) instead of a wrong answer.
 """
 from __future__ import annotations
 
@@ -46,6 +49,7 @@ from speech_decoding.utils.loss import CLIPLoss, MSELoss           # noqa: E402 
 from speech_decoding_amd import data as D                          # noqa: E402  (feeds are looked up in the module when run() is called)
 from speech_decoding_amd import load_config                        # noqa: E402
 from speech_decoding_amd.distributed import allreduce_gradients, broadcast_parameters, shard_range  # noqa: E402
+from speech_decoding_amd.loss import speech_labels                 # noqa: E402
 from speech_decoding_amd.models import resolve_dtype               # noqa: E402
 
 
@@ -82,10 +86,11 @@ class SyntheticSegments:
         return self.X[i], self.Y[i], self.subj[i]
 
 
-def build_data(args, data_kind: str, device, rank: int, world: int):
+def build_data(args, data_kind: str, device, rank: int, world: int, with_ids: bool = False):
     """The synthetic data of a `data=` kind -> (feed, train_batches, test_batch).  `feed` is None for the pool; otherwise the
     callables hand out THIS rank's shard of every batch, and feed.pack_embeddings is the caller's to call once the encoder's
-    compute dtype is known.
+    compute dtype is known.  `with_ids`: a feed's batches are the 4-tuples (X, Y, subject_idxs, chunkIDs) with the segments'
+    speech ids (the pool draws without repeats and has none to give).
 
     data=pool (default): a resident pool of ready-made segments, every rank slicing its shard out of the global batch;
     data=resident: the reference's own input path on the GPU — recordings resident in HBM, RandomSampler(replacement=True)
@@ -128,11 +133,12 @@ def build_data(args, data_kind: str, device, rank: int, world: int):
         sampler = D.ShardedRandomSampler(len(train_idx), batch_size, updates, rank, world, seed=4321 + epoch_no[0])
         epoch_no[0] += 1
         # (under data parallelism the draws for the whole global batch are made on every rank alike and sliced)
-        yield from feed.batches(sampler, index_map=train_idx)
+        yield from feed.batches(sampler, index_map=train_idx, with_ids=with_ids)
 
     def test_batch():
         lo, hi = shard_range(len(test_idx), rank, world)
-        return feed.batch(test_idx[lo:hi])
+        out = feed.batch(test_idx[lo:hi])
+        return (*out, torch.from_numpy(feed.speech_ids(test_idx[lo:hi]))) if with_ids else out
     return feed, train_batches, test_batch
 
 
@@ -200,6 +206,12 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
     import torch.distributed as dist
     data_kind = str(args.get("data", "pool"))
     guarded, max_grad_norm = guard_mode(args)          # (an unknown fp16_guard is refused before anything touches the device)
+    duplicates = str(args.get("clip_duplicates", "ignore"))
+    if duplicates not in ("ignore", "positive", "mask"):
+        raise ValueError(f"clip_duplicates={duplicates}: expected ignore, positive or mask")
+    if duplicates != "ignore" and str(args.get("loss", "clip")).lower() == "mse":
+        raise ValueError(f"clip_duplicates={duplicates} is an option of the CLIP loss; loss=mse has no negatives to correct")
+    use_ids = duplicates != "ignore"
     if train_batches is None and data_kind == "continuous" and args.dataset != "Brennan2018":
         raise ValueError("data=continuous is Brennan2018's input path (one stimulus, every subject): use dataset=Brennan2018")
     if train_batches is None and data_kind == "tracks" and args.dataset != "Gwilliams2022":
@@ -229,14 +241,18 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
 
     feed = None          # a resident feed hands out this rank's shard; batches of the pool, or the caller's, are whole and sliced here
     if train_batches is None:
-        feed, train_batches, test_batch = build_data(args, data_kind, device, rank, world)
+        feed, train_batches, test_batch = build_data(args, data_kind, device, rank, world, with_ids=use_ids)
 
     def local_shard(batch):
-        X, Y, subject_idxs = batch
+        """(X, Y, subject_idxs, labels): labels = the batch's speech ids as the loss takes them (checked and uploaded once for
+        the loss and the accuracies), or None — clip_duplicates=ignore, or a batch that comes without ids."""
+        X, Y, subject_idxs = batch[:3]
+        ids = batch[3] if use_ids and len(batch) == 4 else None
         if world > 1 and feed is None:
             lo, hi = shard_range(X.shape[0], rank, world)
             X, Y, subject_idxs = X[lo:hi], Y[lo:hi], subject_idxs[lo:hi]
-        return X, Y, subject_idxs
+            ids = None if ids is None else ids[lo:hi]
+        return X, Y, subject_idxs, None if ids is None else speech_labels(ids, X.shape[0], device)
 
     brain_encoder = BrainEncoder(args).to(device)
     if feed is not None:
@@ -246,7 +262,9 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
     if loss_kind not in ("clip", "mse"):
         raise ValueError(f"loss={loss_kind}: expected clip or mse")
     clip = loss_kind == "clip"
-    loss_func = (CLIPLoss(args) if clip else MSELoss()).to(device)
+    # (`ignore` is this script's word for "no labels"; the loss itself knows the two ways of using them)
+    loss_args = args if use_ids or "clip_duplicates" not in args else type(args)({**args, "clip_duplicates": "positive"})
+    loss_func = (CLIPLoss(loss_args) if clip else MSELoss()).to(device)
     loss_func.train()
     broadcast_parameters(brain_encoder)
     # MSELoss has no parameters of its own: Adam steps the encoder alone
@@ -290,18 +308,18 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
         ahead = next(batches, None)
         first = True
         while ahead is not None:
-            X, Y, subject_idxs = ahead
+            X, Y, subject_idxs, labels = ahead
             ahead = next(batches, None)
             if first and clip:
                 loss_func.prefetch(Y, brain_encoder.compute_dtype)
                 first = False
             Z = brain_encoder(X, subject_idxs)
-            loss = loss_func(Y, Z)
+            loss = loss_func(Y, Z) if labels is None else loss_func(Y, Z, labels=labels)
             # The reference reads loss.item() and the two accuracies back on the host here, every batch (train.py:194-198):
             # a host<->GPU synchronisation in the middle of the step.  The same numbers are kept on the device and read
             # once per epoch, below: the host keeps enqueueing while the GPU works (8 vs 16 ms per step at batch 256).
             with torch.no_grad():
-                ranks = classifier.ranks(Z, Y)                   # Classifier.forward's ranks, kept on the device
+                ranks = classifier.ranks(Z, Y, labels=labels)    # Classifier.forward's ranks, kept on the device
             tr_loss.append(loss.detach())
             tr_ranks.append(ranks)
             if ahead is not None and clip:
@@ -317,10 +335,10 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
         brain_encoder.eval()
         te_loss, te_top1, te_top10 = [], [], []
         with torch.no_grad():
-            X, Y, subject_idxs = local_shard(test_batch())
+            X, Y, subject_idxs, labels = local_shard(test_batch())
             Z = brain_encoder(X, subject_idxs)
-            te_loss.append(loss_func(Y, Z).item())
-            t1, t10 = classifier(Z, Y, test=True)
+            te_loss.append((loss_func(Y, Z) if labels is None else loss_func(Y, Z, labels=labels)).item())
+            t1, t10 = classifier(Z, Y, test=True, labels=labels)
             te_top1.append(t1)
             te_top10.append(t10)
 
