@@ -177,9 +177,11 @@ def matmul_nt_ref(A, Bm):
 # the conv forward cases and their emulation with mutants
 # ---------------------------------------------------------------------------------------------------------------
 ConvShape = namedtuple("ConvShape", "cin cout dil T B")
-# T below / above one 128-row tile (40, 129, 130), T = 1, dil = 16 = the row padding, T < dil; B * (T + 16) rows put a 256-row
-# flat tile across two (or all) samples and leave the last tile partial; Cout_p on the 64- (48, 64), 160- (320, 640, 160) and
-# 128-channel (128) tiles; Cin 40 and 96 are no multiples of 64.  cin == cout: the residual is the conv's own input.
+# T below / above one 128-row tile (40, 129, 130), T = 1, dil = 16 = the row padding, T < dil; B * (T + 16) rows put the flat
+# kernel's 128-row tiles across two (or all) samples and leave the last tile partial — with no CU limit a shape this small is
+# planned one unit per workgroup, so the flat kernel's 256-row tile does not run here: tests/persistent_cases.py has the
+# (shape, CU limit) pairs that run it; Cout_p on the 64- (48, 64), 160- (320, 640, 160) and 128-channel (128) tiles; Cin 40 and
+# 96 are no multiples of 64.  cin == cout: the residual is the conv's own input.
 CONV3_SHAPES = [ConvShape(40, 48, 1, 40, 3), ConvShape(320, 320, 16, 130, 2), ConvShape(64, 640, 4, 129, 3),
                 ConvShape(96, 128, 2, 1, 5), ConvShape(64, 64, 16, 9, 4), ConvShape(64, 160, 16, 5, 7)]
 EPILOGUES = ["bare", "bias", "bias_res"]

@@ -7,6 +7,7 @@ each fail them."""
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as TF
 
 pytestmark = pytest.mark.gpu
 
@@ -65,9 +66,12 @@ def padding_is_zero(buf, B, C, T):
 @pytest.mark.parametrize("regime", X.REGIMES)
 @pytest.mark.parametrize("i", range(len(X.CONV3_SHAPES)), ids=lambda i: "x".join(map(str, X.CONV3_SHAPES[i])))
 def test_conv3_forward_every_tiling_and_epilogue(ops, i, regime, dtype):
-    """one tile / two tiles per workgroup, 256-row flat tiles (two workgroups or one per CU; widths without a flat tiling take the
+    """one tile / two tiles per workgroup, the flat kernel (two workgroups or one per CU; widths without a flat tiling take the
     tile kernel again), each bare, with bias, with bias + residual: the stored values are the rounded exact ones, padding stays
-    zero, and in the exact regime the statistics' sum plane holds the exact column sums."""
+    zero, and in the exact regime the statistics' sum plane holds the exact column sums.
+    With no CU limit these shapes (at most 3 units x 2 channel tiles against 512 workgroup slots) give the flat kernel a plan of
+    one unit per workgroup: it runs its 128-row tiles only.  Its 256-row tile, and runs of several tiles per workgroup, meet the
+    same references in tests/test_persistent_runs_gpu.py."""
     from speech_decoding_amd import lib as L
     case = X.conv3_case(i, regime, dtype)
     s = case.shape
@@ -96,6 +100,10 @@ def test_conv3_forward_every_tiling_and_epilogue(ops, i, regime, dtype):
 @pytest.mark.parametrize("dtype", X.DTYPES, ids=name)
 @pytest.mark.parametrize("regime", X.REGIMES)
 def test_conv3_flat_glu_epilogue_keeps_the_exact_gate(ops, regime, dtype):
+    check_glu_gate(ops, regime, dtype)
+
+
+def check_glu_gate(ops, regime, dtype):
     """SDA_EPI_GLU (weights and bias packed 80 values + 80 gates per tile): the gate written to y_pre is the conv's gate half"""
     from speech_decoding_amd import lib as L
     case = X.glu_case(regime, dtype)
@@ -128,7 +136,10 @@ def test_conv3_flat_staggered_tile_order_gives_the_same_bits(ops, B, T, dtype):
     spread the same sums over a run's rows differently by design (and the same for fp32, where the rows themselves must be
     equal).  What both orders share is the sum over a workgroup's run of units, and the operands are integers small enough that
     every partial sum (and sum of squares) of a tile is exact in fp32, whatever the order: the per-run sums, taken in float64,
-    are compared with torch.equal, and so are the raw rows for fp32."""
+    are compared with torch.equal, and so are the raw rows for fp32.
+    Both orders could be wrong alike, so the plain order's output must also equal a reference that uses no project kernel: the
+    operands are integers in [-1, 1] (bias in [-3, 3]), so three shifted float64 matmuls plus bias and residual are exact, and
+    the stored value is their one rounding to the storage type."""
     from speech_decoding_amd import lib as L
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     if cus != 256:
@@ -143,7 +154,8 @@ def test_conv3_flat_staggered_tile_order_gives_the_same_bits(ops, B, T, dtype):
     w = torch.randint(-1, 2, (C, C, 3), device=DEV, generator=g).float()
     xb = ops.pack_rows(x, ops.new_rows(B, T, C, dtype, DEV))
     wp = ops.pack_conv_weight(w, C, C, dtype)
-    bias = ops.pack_vector(torch.randint(-3, 4, (C,), device=DEV, generator=g).float(), C)
+    bias_v = torch.randint(-3, 4, (C,), device=DEV, generator=g)
+    bias = ops.pack_vector(bias_v.float(), C)
     got = []
     for flags in (L.CONV_FLAT_TILES, L.CONV_FLAT_TILES | L.CONV_FLAT_STAGGER):
         yb = ops.new_rows(B, T, C, dtype, DEV)
@@ -151,6 +163,12 @@ def test_conv3_flat_staggered_tile_order_gives_the_same_bits(ops, B, T, dtype):
         ops.conv_gemm(xb, wp, yb, B=B, T=T, KS=3, dil=dil, bias=bias, res=xb, stats=stats, flags=flags)
         got.append((yb, stats))
     (y0, s0), (y1, s1) = got
+    # the reference, in plain torch on the device: three shifted float64 matmuls (integers: exact), bias and residual, one rounding
+    xd = TF.pad(x.double(), (dil, dil))
+    want = sum(torch.matmul(w[:, :, k].double(), xd[:, :, k * dil: k * dil + T]) for k in range(3))
+    want = (want + bias_v.double()[None, :, None] + x.double()).float().to(dtype)
+    if not torch.equal(ops.unpack_rows(y0, B, C, T), want.float()):         # (the failing index names the tile or run boundary)
+        X.assert_same(ops.unpack_rows(y0, B, C, T), want, f"conv3_flat {B} x {C} x {T} {name(dtype)} against three shifted matmuls")
     assert torch.equal(ops.unpack_rows(y0, B, C, T), ops.unpack_rows(y1, B, C, T))
     assert torch.equal(y0, y1)                                           # padding included
     assert float(y0.float().abs().max()) ** 2 * 256 < 2 ** 24            # a tile's sums are exact in fp32
@@ -222,6 +240,11 @@ def test_conv1_tile_flat_and_wide_kernels(ops, shape, regime, dtype):
 @pytest.mark.parametrize("regime", X.REGIMES)
 @pytest.mark.parametrize("i", range(len(X.DGRAD_SHAPES)), ids=lambda i: "x".join(map(str, X.DGRAD_SHAPES[i])))
 def test_data_gradient_on_mode1_weights(ops, i, regime, dtype):
+    from speech_decoding_amd import lib as L
+    check_data_gradient(ops, i, regime, dtype, (0, L.CONV_SINGLE_TILE, L.CONV_PAIR_TILES, L.CONV_FLAT_TILES))
+
+
+def check_data_gradient(ops, i, regime, dtype, tilings):
     """dx through conv_gemm on weights packed with mode 1, plain and in the GLU channel layout (the halves split at half_p)"""
     from speech_decoding_amd import lib as L
     case = X.dgrad_case(i, regime, dtype)
@@ -237,7 +260,7 @@ def test_data_gradient_on_mode1_weights(ops, i, regime, dtype):
         dy[:, half_p: half_p + s.cout - half] = case.dy[:, half:]
     dyb = rows(ops, dy, dtype, Cp=Cout_p)
     wt = weight(ops, case.w, Cout_p, Cin_p, dtype, mode=1, glu_half=half, glu_half_p=half_p)
-    for flags in (0, L.CONV_SINGLE_TILE, L.CONV_PAIR_TILES, L.CONV_FLAT_TILES):
+    for flags in tilings:
         dxb = ops.conv_gemm(dyb, wt, ops.new_rows(s.B, s.T, Cin_p, dtype, DEV), B=s.B, T=s.T, KS=s.KS, dil=s.dil, flags=flags)
         what = f"dgrad {tuple(s)} {regime} {name(dtype)} flags {flags}"
         X.assert_same(unrows(ops, dxb, s.B, s.cin, s.T), X.store(case.ref, dtype), what)

@@ -265,6 +265,10 @@ def test_conv1_flat_tiles_equal_tile_kernel(ops, dtype, cin, cout, T, B):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("cin,cout,T,B", [(1024, 640, 360, 4), (128, 256, 77, 3), (64, 320, 130, 6), (64, 192, 130, 3)])
 def test_conv1_flat_gelu_backward_epilogue(ops, dtype, cin, cout, T, B):
+    check_conv1_flat_gelu_backward_epilogue(ops, dtype, cin, cout, T, B)
+
+
+def check_conv1_flat_gelu_backward_epilogue(ops, dtype, cin, cout, T, B):
     """SDA_EPI_GELU_BWD: the data-gradient conv's epilogue multiplies by GELU'(u) and sums the columns = conv, store, then
     sda_gelu_backward_colsum (bit-equal gradient; the column sums agree to summation order).  `stats` is the leading
     conv_stats_rows(...) rows of a buffer with four spare rows: every counted row is written, no spare one.  At 192 channels
@@ -358,6 +362,10 @@ def test_conv1_wide_tiles_equal_tile_kernel(ops, dtype, cin, cout, T, B):
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("cin,cout,T,B", [(1024, 640, 360, 4), (128, 256, 77, 3), (64, 320, 130, 6), (256, 512, 360, 20)])
 def test_conv1_wide_gelu_backward_epilogue(ops, dtype, cin, cout, T, B):
+    check_conv1_wide_gelu_backward_epilogue(ops, dtype, cin, cout, T, B)
+
+
+def check_conv1_wide_gelu_backward_epilogue(ops, dtype, cin, cout, T, B):
     from speech_decoding_amd import lib as L
     g = torch.Generator().manual_seed(22)
     Cip, Cop = L.pad_channels(cin), L.pad_channels(cout)
@@ -439,6 +447,10 @@ def test_conv3_dgrad_and_wgrad(ops, dtype, cin, cout, dil, T, glu):
 @pytest.mark.parametrize("tiling", [4096, 8192, 16384])
 @pytest.mark.parametrize("cin,cout,dil,T", [(48, 40, 2, 70), (640, 320, 2, 300), (320, 320, 8, 360)])
 def test_conv3_bn_backward_statistics_epilogue(ops, dtype, cin, cout, dil, T, tiling):
+    check_conv3_bn_backward_statistics_epilogue(ops, dtype, cin, cout, dil, T, tiling)
+
+
+def check_conv3_bn_backward_statistics_epilogue(ops, dtype, cin, cout, dil, T, tiling):
     """conv_gemm(bn_x=...) writes its output AND the BatchNorm+GELU backward sums of the layer that output is
     the gradient of; they must equal the stand-alone reduction pass over the stored output."""
     from speech_decoding_amd import lib as L
