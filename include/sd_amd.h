@@ -47,7 +47,8 @@ extern "C" {
                                   time-lagged ridge baseline;
                                   sda_conv_kernel — which kernel sda_conv_gemm routes a convolution to, asked instead of mirrored;
                                   sda_clip_label_counts / sda_clip_logits_stats_masked / sda_clip_grad_labels / sda_clip_grad_y_labels /
-                                  sda_clip_ranks_labels — the loss tail with speech labels) */
+                                  sda_clip_ranks_labels — the loss tail with speech labels;
+                                  sda_sigmoid_pairs / sda_sigmoid_finish / sda_sigmoid_grad_y — the pairwise sigmoid loss tail) */
 #define SDA_ROW_PAD 16
 #define SDA_CH_ALIGN 64
 
@@ -482,6 +483,31 @@ int sda_clip_grad_y_labels(const float* logits, const float* row_lse, const floa
                            void* stream);
 int sda_clip_ranks_labels(const float* logits, const float* diag, const int32_t* labels, int32_t* cnt, int Bm, int Bn,
                           int col0, void* stream);
+/* The pairwise sigmoid loss tail (csrc/sigmoid_loss.hip) on the same raw similarity block S (rows = the Bm global speech samples,
+ * columns = this block's Bn brain samples from global index col0; 0 <= col0, col0 + Bn <= Bm):
+ *     a_ij = S_ij exp(temp) / (|Y_i| |Z_j|)   (the expression, and the bits, of sda_clip_logits_stats' logits),  l_ij = a_ij + bias,
+ *     z_ij = +1 where i == col0 + j, else -1;  loss = inv_norm * sum_ij softplus(-z_ij l_ij);  D_ij = -z_ij sigma(-z_ij l_ij).
+ * labels (device int32 [Bm], or NULL: then mode is ignored): a pair of two samples with one label has z = +1
+ * (SDA_CLIP_DUP_POSITIVE) or is dropped (SDA_CLIP_DUP_MASK: no loss term, D_ij = 0 exactly).  inv_norm = 1 / B_global for
+ * reduction="mean", 1 for "sum".  softplus and sigma are the stable forms: past |l| = 104 the term is |l| or 0 and D is -+1 or 0.
+ * sda_sigmoid_pairs, one pass over the block: a fp32 [Bm][Bn]; diag as sda_clip_logits_stats writes it (every row; 0 where the
+ * positive lives in another block); G[i][j] = D_ij ymax / |Y_i| as `dtype`, [Bm + 1][g_pitch] with row Bm and the columns >= Bn
+ * written as zeros (sda_clip_grad's G); part fp32 [ceil(Bm / 64)][Bn][3] = (sum softplus, sum D a, sum D) of column j over
+ * each group of 64 rows.
+ * sda_sigmoid_finish (nparts = ceil(Bm / 64)) sums them in group order: rscale[j] = inv_norm * sum_i D_ij a_ij / |Z_j|^2,
+ * cscale[j] = inv_norm * exp(temp) / (ymax |Z_j|) — so that sda_clip_dz gives dZ_j = cscale_j sum_i G_ij Y_i - rscale_j Z_j —
+ * and scalars[3] = this block's shares of (loss, d loss / d temp, d loss / d bias), summed over the columns in fp64.
+ * sda_sigmoid_grad_y is sda_clip_grad_y's twin (same Gy layout with seg / seg_pitch, zero row Bn, part [ceil(Bn / 64)][Bm] =
+ * sums of D_ij a_ij): Gy[j][i] = D_ij zmax / |Z_j|, D from a, bias and the labels as above; its outputs go to
+ * sda_clip_grad_y_finish and sda_clip_dz.  No atomics: every sum's order is fixed by the shape. */
+int sda_sigmoid_pairs(const float* S, long s_pitch, const float* ysq, const float* zsq, const float* temp,
+                      const float* bias, const int32_t* labels, int mode, int col0, float* a, float* diag, void* G,
+                      long g_pitch, float* part, int Bm, int Bn, int dtype, void* stream);
+int sda_sigmoid_finish(const float* part, int nparts, const float* ysq, const float* zsq, const float* temp,
+                       float inv_norm, float* rscale, float* cscale, float* scalars, int Bm, int Bn, void* stream);
+int sda_sigmoid_grad_y(const float* a, const float* bias, const float* zsq, const float* zsq_all, int nz,
+                       const int32_t* labels, int mode, int col0, void* Gy, long gy_pitch, int seg, int seg_pitch,
+                       float* part, int Bm, int Bn, int dtype, void* stream);
 /* Decoding against a candidate bank (csrc/retrieval.hip): top-k selection over the raw fp32 dot products of n query rows
  * against M candidates, one pass over the matrix.  score[i][j] = S[i][j] / max(sqrt(qsq[i]) * sqrt(csq[j]), 1e-8) (the
  * similarity of models.py:223-232; a zero row scores 0), ordered by score descending, on equal scores the lower j first

@@ -37,6 +37,10 @@ class ClipCtx:
     labels: Optional[torch.Tensor] = None
     counts: Optional[torch.Tensor] = None
     duplicates: str = "positive"
+    # the pairwise sigmoid loss (sigmoid_forward): its bias and this block's share of d loss / d bias; `logits` then holds the
+    # scaled cosines a (the logits less the bias) and there are no lse
+    bias: Optional[torch.Tensor] = None
+    dbias: Optional[torch.Tensor] = None
 
 
 def clip_forward(Yt: torch.Tensor, Zt: torch.Tensor, temp: torch.Tensor, *, Bm: int, Bn: int, T: int, col0: int = 0,
@@ -136,7 +140,10 @@ def clip_backward(ctx: ClipCtx, dZt: torch.Tensor, dloss: Optional[torch.Tensor]
 
 
 def clip_grad_y_coeffs(ctx: ClipCtx, zsq_all: torch.Tensor, dtype, **layout):
-    """(Gy, part) of the block behind `ctx`: the labelled twin when the forward had labels."""
+    """(Gy, part) of the block behind `ctx`: the labelled twin when the forward had labels, the sigmoid loss's twin behind
+    sigmoid_forward."""
+    if ctx.bias is not None:
+        return ops.sigmoid_grad_y(ctx.logits, ctx.bias, ctx.zsq, zsq_all, ctx.col0, dtype, ctx.labels, ctx.duplicates, **layout)
     if ctx.labels is None:
         return ops.clip_grad_y(ctx.logits, ctx.row_lse, ctx.col_lse, ctx.zsq, zsq_all, ctx.col0, dtype, **layout)
     return ops.clip_grad_y_labels(ctx.logits, ctx.row_lse, ctx.col_lse, ctx.zsq, zsq_all, ctx.labels, ctx.counts, ctx.duplicates,
@@ -149,9 +156,38 @@ def clip_backward_y(ctx: ClipCtx, dYt: torch.Tensor, dloss: Optional[torch.Tenso
     the two embeddings exchanged, on the same GEMM family (no new GEMM kernel).  `labels` / `duplicates`: default to the
     forward's, which `ctx` carries with their class sizes."""
     if labels is not None and labels is not ctx.labels:
-        ctx = replace(ctx, labels=labels, counts=ops.clip_label_counts(labels))
+        ctx = replace(ctx, labels=labels, counts=None if ctx.bias is not None else ops.clip_label_counts(labels))
     if duplicates is not None:
         ctx = replace(ctx, duplicates=duplicates)
     Gy, part = clip_grad_y_coeffs(ctx, ctx.zsq, ctx.Zt.dtype)
     rscale_y, cscale_y = ops.clip_grad_y_finish(part, ctx.ysq, ctx.zsq, ctx.temp, ctx.inv_norm, 0, ctx.Bm)
     return ops.clip_dz(Gy, ctx.Zt, ctx.Yt, dYt, rscale_y, cscale_y, Bm=ctx.Bn, Bn=ctx.Bm, row_elems=ctx.row_elems, out_scale=dloss)
+
+
+def sigmoid_forward(Yt: torch.Tensor, Zt: torch.Tensor, temp: torch.Tensor, bias: torch.Tensor, *, Bm: int, Bn: int, T: int,
+                    col0: int = 0, reduction: str = "mean", B_global: Optional[int] = None, ysq: Optional[torch.Tensor] = None,
+                    labels: Optional[torch.Tensor] = None, duplicates: str = "positive"):
+    """The pairwise sigmoid loss on RL embeddings: Yt holds the Bm (global) speech rows, Zt the Bn local brain rows from global
+    sample col0.  Every pair is its own binary decision, so the block is complete on its own: there is no merge across ranks
+    and the loss is the sum of the blocks' shares.  Returns (loss_local_share, a, ranks_count, ctx) — a = the scaled cosines,
+    the logits less the bias; ctx serves clip_backward and clip_backward_y as the CLIP loss's does.
+    The tail is three launches (pairs, finish, ranks) against the CLIP loss's five."""
+    ops.clip_dup_code(duplicates)                 # refused before the first launch
+    Fp = Zt.shape[1]
+    row_elems = L.rows_tp(T) * Fp
+    if ysq is None:
+        ysq = ops.rows_sumsq(Yt, Bm, row_elems, row_elems)
+    zsq = ops.ROW_NORMS.get(Zt, Bn)
+    if zsq is None:
+        zsq = ops.rows_sumsq(Zt, Bn, row_elems, row_elems)
+    S = ops.matmul_nt_splitk(Yt, Zt, Bm, Bn, row_elems, row_elems)
+    Bg = B_global if B_global is not None else Bm
+    inv_norm = 1.0 / Bg if reduction == "mean" else 1.0
+    a, diag, G, part = ops.sigmoid_pairs(S, ysq, zsq, temp, bias, Bm, Bn, col0, Yt.dtype, labels, duplicates)
+    rscale, cscale, scalars = ops.sigmoid_finish(part, ysq, zsq, temp, inv_norm)
+    # the bias moves every entry of a row alike: the order within a row, and so the ranks, are those of a
+    cnt = ops.clip_ranks(a, diag, col0) if labels is None else ops.clip_ranks_labels(a, diag, labels, col0)
+    ctx = ClipCtx(Bm=Bm, Bn=Bn, col0=col0, G=G, rscale=rscale, Yt=Yt, Zt=Zt, row_elems=row_elems, dtemp=scalars[1:2], cscale=cscale,
+                  logits=a, ysq=ysq, zsq=zsq, temp=temp, inv_norm=inv_norm, labels=labels, duplicates=duplicates, bias=bias,
+                  dbias=scalars[2:3])
+    return scalars[0:1], a, cnt, ctx

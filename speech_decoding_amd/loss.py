@@ -7,6 +7,9 @@ all run in libsdamd.so.  Under torch.distributed (one process per GPU) the speec
 so the negatives span the GLOBAL batch; each rank owns the columns of its local brain embeddings.  Gradients reach x, y and
 temp, as in the reference; x's is computed only when x requires one.
 
+`SigmoidLoss` is the pairwise sigmoid contrastive loss on the same operands, buffers and gradient kernels (sda_sigmoid_*): every
+(speech, brain) pair is its own binary decision, with a learned temperature and bias; nothing in the reference corresponds to it.
+
 Also `MSELoss` (loss.py:15-25), the reference's regression objective, on the sda_mse_* kernels, and its two clamped helpers
 `torch_exp` / `torch_log` (loss.py:8-13, plain torch).
 """
@@ -501,6 +504,131 @@ class CLIPLoss(nn.Module):
         self.last_logits = logits
         if return_logits:
             return logits, loss
+        return loss
+
+
+class _SigmoidFn(torch.autograd.Function):
+    """SigmoidLoss's node: _ClipFn's operands, buffers and gradient forms around clip.sigmoid_forward.  A rank's block of pairs is
+    complete on its own, so under data parallelism the forward runs the speech all-gather and the one all-reduce of the loss
+    share — no merge of row statistics."""
+
+    @staticmethod
+    def forward(ctx, module: "SigmoidLoss", Y, Z, temp, bias, labels=None):
+        import torch.distributed as dist
+        B, F, T = Z.shape
+        lab = speech_labels(labels, B, Z.device)    # refused here, before the first launch, when they are malformed
+        dtype = Z.dtype if Z.dtype in ops.COMPUTE_DTYPES else torch.float32
+        Zt = as_rows(Z, B, F, T, dtype, "y (brain embeddings)")
+        group = _dist_group() if module.global_negatives else None
+        state = module._state
+        want_y = ctx.needs_input_grad[1]
+        y_rows = False
+        if want_y:
+            y_rows = ops.rows_base(Y, B, F, T, dtype) is not None
+            if not y_rows and not Y.is_cuda:
+                raise L.SdaError("SigmoidLoss: x (speech embeddings) must live on the MI355X device (there is no CPU path)")
+            if not y_rows and Y.dtype not in ops.COMPUTE_DTYPES:
+                raise L.SdaError(f"SigmoidLoss: a speech embedding that requires a gradient must be fp32, bf16 or fp16, got {Y.dtype}")
+            if group is not None and dist.get_world_size(group) == 1:
+                from .distributed import emulated_world
+                if emulated_world() > 1:
+                    raise L.SdaError("SigmoidLoss: the emulated world (stand-in rows for the other ranks) has no gradient for the "
+                                     "speech embeddings; detach x or run real ranks")
+        yg = _take_prefetched(state, Y, dtype)
+        if yg is None:
+            Yt_local, slot = _pack_ring(state, Y, B, F, T, dtype, "x (speech embeddings)", "loss.Y")
+            yg = gather_speech_rows(Yt_local, B, T, group, state=state, slot=slot)
+        lab_all = None if lab is None else gather_labels(lab, B, group)
+        loss, a, cnt, cctx = clip.sigmoid_forward(yg.rows, Zt, temp.detach(), bias.detach(), Bm=yg.n, Bn=B, T=T, col0=yg.col0,
+                                                  reduction=module.reduction, B_global=yg.n, ysq=yg.sq, labels=lab_all,
+                                                  duplicates=module.duplicates)
+        ctx.z_gather = None
+        if want_y and group is not None:            # the brain rows of all ranks, for the speech-side gradient (as in _ClipFn)
+            ctx.z_gather = gather_speech_rows(Zt, B, T, group, async_op=True, state=state, ring_key="loss.Zall", sq=cctx.zsq)
+        ranks_known = True
+        if group is not None:
+            # the loss share -> global loss for reporting (backward uses the local share).  The rank counts of a row need its
+            # positive's logit, which lives on one rank: with more than one real rank they are left to the Classifier's own pass
+            # instead of a second collective here
+            ranks_known = dist.get_world_size(group) == 1
+            loss = loss.clone()
+            dist.all_reduce(loss, group=group)
+        ctx.cctx, ctx.shape, ctx.dtype, ctx.group, ctx.y_slot = cctx, (B, F, T), dtype, group, yg.slot
+        ctx.set_materialize_grads(False)
+        ctx.z_requires_grad = Z.requires_grad
+        ctx.y_requires_grad, ctx.y_rows, ctx.y_dtype = want_y, y_rows, Y.dtype
+        if ranks_known:
+            _cache_ranks(Y, Z, cnt[yg.col0: yg.col0 + B], None if lab is None else lab.key)
+        ctx.mark_non_differentiable(a)
+        return loss.reshape(()), a
+
+    @staticmethod
+    def backward(ctx, dloss, _da):
+        c = ctx.cctx
+        B, F, T = ctx.shape
+        dZ = dY = None
+        if dloss is None:
+            return None, None, None, None, None, None
+        scale = dloss.to(torch.float32)
+        if (ctx.z_requires_grad or ctx.y_requires_grad) and ctx.y_slot is not None and not ctx.y_slot.valid():
+            raise L.SdaError(_RECYCLED.format(what="speech").replace("CLIPLoss", "SigmoidLoss"))
+        if ctx.z_requires_grad:
+            dZt = ops.new_rows_uninit(B, T, c.Zt.shape[1], ctx.dtype, c.Zt.device)
+            clip.clip_backward(c, dZt, scale.reshape(1).contiguous())     # dloss folded into the GEMM epilogue
+            dZ = ops.rows_view(dZt, B, F, T)
+        if ctx.y_requires_grad:
+            dYt = _clip_dy(ctx, scale.reshape(1).contiguous())
+            dY = ops.rows_view(dYt, B, F, T) if ctx.y_rows else ops.unpack_rows(dYt, B, F, T, ctx.y_dtype)
+        dtemp = ops.scalar_mul(c.dtemp, scale.reshape(1))
+        dbias = ops.scalar_mul(c.dbias, scale.reshape(1))
+        return None, dY, dZ, dtemp, dbias, None
+
+
+class SigmoidLoss(nn.Module):
+    """The pairwise sigmoid contrastive loss (SigLIP): every (speech i, brain j) pair of the global batch is its own binary
+    decision on l_ij = cos(x_i, y_j) exp(temp) + bias — the positive pairs towards +, all others towards - :
+        loss = (1 / B, or 1 for reduction="sum") * sum_ij softplus(-z_ij l_ij),   z_ij = +1 for a positive pair, else -1.
+    forward(x, y, return_logits=False, labels=None): x = speech, y = brain embeddings (B, F, T), as CLIPLoss takes them (rows
+    views of encoder outputs or plain tensors; fp32 / bf16 / fp16); gradients reach y, x (when it requires one), temp and bias.
+    `labels`: the speech id of each local sample; two samples with one id are a further positive pair
+    (clip_duplicates="positive") or a pair that is left out ("mask").  No row or column couples its entries: under data
+    parallelism a rank's block of pairs is complete on its own and the loss is the sum of the blocks."""
+
+    def __init__(self, args):
+        super().__init__()
+        L.load()
+        self.reduction = str(args.reduction)
+        if self.reduction not in ("mean", "sum"):
+            raise ValueError("reduction must be 'mean' or 'sum'")
+        get = getattr(args, "get", None) or (lambda k, d: getattr(args, k, d))
+        self.duplicates = str(get("clip_duplicates", "positive"))
+        ops.clip_dup_code(self.duplicates)          # any other value: ValueError
+        self.temp = nn.Parameter(torch.tensor([float(get("sigmoid_init_temperature", np.log(10.0)))]))
+        self.bias = nn.Parameter(torch.tensor([float(get("sigmoid_init_bias", -10.0))]))
+        self.global_negatives = True
+        self.last_logits: Optional[torch.Tensor] = None      # the scaled cosines a of the last forward (the logits less the bias)
+        self._state = LossState()           # packed-speech ring + pending prefetch of THIS instance
+
+    def prefetch(self, x: torch.Tensor, compute_dtype=torch.float32):
+        """Optional: call with the speech embeddings BEFORE running the encoder (see prefetch_speech)."""
+        prefetch_speech(x, compute_dtype, self.global_negatives, state=self._state)
+
+    def drain(self):
+        """Wait for (and drop) a prefetch that no forward will consume — call before tearing the process group down."""
+        self._state.drain()
+
+    def release_buffers(self):
+        """Drop the persistent packed-speech buffers (e.g. between a training and an evaluation phase)."""
+        self._state.clear()
+
+    def forward(self, x, y, return_logits=False, labels=None):
+        batch_size = x.size(0)
+        if labels is not None:
+            labels = speech_labels(labels, batch_size, y.device)
+        loss, a = _SigmoidFn.apply(self, x, y, self.temp, self.bias, labels)
+        self.last_logits = a
+        if return_logits:                           # made on request only: the hot path stores a alone
+            return a + self.bias.detach(), loss
         return loss
 
 

@@ -1116,6 +1116,60 @@ def clip_ranks_labels(logits, diag, labels, col0):
     return cnt
 
 
+def _sigmoid_args(who: str, labels, duplicates, Bm: int, Bn: int, col0: int, *tensors):
+    """What the three sigmoid entry points check before anything is launched -> the C `mode`."""
+    mode = clip_dup_code(duplicates)
+    if Bm < 1 or Bn < 1 or col0 < 0 or col0 + Bn > Bm:
+        raise L.SdaError(f"{who}: need Bm, Bn >= 1 and 0 <= col0, col0 + Bn <= Bm, got Bm={Bm} Bn={Bn} col0={col0}")
+    if labels is not None:
+        _need_labels(who, labels, Bm)
+    _need_cuda(*tensors)
+    return mode
+
+
+def sigmoid_pairs(S, ysq, zsq, temp, bias, Bm, Bn, col0, dtype, labels=None, duplicates="positive"):
+    """One pass over a block of the pairwise sigmoid loss (sda_sigmoid_pairs): a = the scaled cosines fp32 (Bm, Bn), diag as
+    clip_logits_stats leaves it, G (Bm + 1, pad64(Bn)) of `dtype` and the per-column partials (ceil(Bm / 64), Bn, 3)."""
+    mode = _sigmoid_args("sigmoid_pairs", labels, duplicates, Bm, Bn, col0, S, ysq, zsq, temp, bias)
+    dev = S.device
+    a = torch.empty((Bm, Bn), dtype=torch.float32, device=dev)
+    diag = torch.empty(Bm, dtype=torch.float32, device=dev)
+    G = torch.empty((Bm + 1, L.pad_channels(Bn)), dtype=dtype, device=dev)      # zero row and pad columns written by the kernel
+    part = torch.empty(((Bm + 63) // 64, Bn, 3), dtype=torch.float32, device=dev)
+    L.check(L.load().sda_sigmoid_pairs(_p(S), S.shape[1], _p(ysq), _p(zsq), _p(temp), _p(bias), _p(labels), mode, col0, _p(a), _p(diag),
+                                       _p(G), G.shape[1], _p(part), Bm, Bn, dt_code(dtype), _st()), "sigmoid_pairs")
+    return a, diag, G, part
+
+
+def sigmoid_finish(part, ysq, zsq, temp, inv_norm):
+    """The partials of sigmoid_pairs -> (rscale, cscale) of clip_dz's contract and scalars[3] = this block's shares of
+    (loss, d loss / d temp, d loss / d bias)."""
+    _need_cuda(part, ysq, zsq, temp)
+    nparts, Bn, _ = part.shape
+    Bm = ysq.numel()
+    rscale = torch.empty(Bn, dtype=torch.float32, device=part.device)
+    cscale = torch.empty(Bn, dtype=torch.float32, device=part.device)
+    scalars = torch.empty(3, dtype=torch.float32, device=part.device)
+    L.check(L.load().sda_sigmoid_finish(_p(part), nparts, _p(ysq), _p(zsq), _p(temp), float(inv_norm), _p(rscale), _p(cscale),
+                                        _p(scalars), Bm, Bn, _st()), "sigmoid_finish")
+    return rscale, cscale, scalars
+
+
+def sigmoid_grad_y(a, bias, zsq, zsq_all, col0, dtype, labels=None, duplicates="positive", *, seg=None, seg_pitch=None, groups=1):
+    """clip_grad_y's twin for the sigmoid loss (sda_sigmoid_grad_y): Gy and the per-row partials in the same layouts, D
+    recomputed from a, bias and the labels."""
+    Bm, Bn = a.shape
+    mode = _sigmoid_args("sigmoid_grad_y", labels, duplicates, Bm, Bn, col0, a, bias, zsq, zsq_all)
+    seg = Bm if seg is None else seg
+    seg_pitch = L.pad_channels(seg) if seg_pitch is None else seg_pitch
+    dev = a.device
+    Gy = torch.empty((Bn + 1, groups * seg_pitch), dtype=dtype, device=dev)     # every element is written by the kernel
+    part = torch.empty(((Bn + 63) // 64, Bm), dtype=torch.float32, device=dev)
+    L.check(L.load().sda_sigmoid_grad_y(_p(a), _p(bias), _p(zsq), _p(zsq_all), zsq_all.numel(), _p(labels), mode, col0, _p(Gy),
+                                        Gy.shape[1], seg, seg_pitch, _p(part), Bm, Bn, dt_code(dtype), _st()), "sigmoid_grad_y")
+    return Gy, part
+
+
 def retrieval_scores_floats(n: int, M: int, chunk_cols: int) -> int:
     """Floats of the chunk-major score matrix sda_retrieval_select reads for n query rows against M candidates."""
     r = L.load().sda_retrieval_scores_floats(n, M, chunk_cols)

@@ -8,7 +8,8 @@ reference's `train.py`, own implementation.
 
 What is kept from the reference loop (train.py:148-259):
   * models: BrainEncoder + Classifier + CLIPLoss, Adam over encoder parameters and the loss temperature;
-    `loss=mse` trains on MSELoss instead (the reference's regression objective; Adam over the encoder alone);
+    `loss=mse` trains on MSELoss instead (the reference's regression objective; Adam over the encoder alone),
+    `loss=sigmoid` on SigmoidLoss (the pairwise sigmoid contrastive loss; Adam over the encoder, its temperature and its bias);
   * per batch: Z = encoder(X, subject_idxs); loss = CLIPLoss(Y, Z); top-1/top-10 from Classifier(Z, Y);
   * update cadence: Gwilliams2022 steps on every batch, Brennan2018 ONCE per epoch with the last batch's
     loss (train.py:200-209);
@@ -45,7 +46,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from speech_decoding.models import BrainEncoder, Classifier       # noqa: E402  (train.py:22 import path)
-from speech_decoding.utils.loss import CLIPLoss, MSELoss           # noqa: E402  (train.py:24)
+from speech_decoding.utils.loss import CLIPLoss, MSELoss, SigmoidLoss    # noqa: E402  (train.py:24)
 from speech_decoding_amd import data as D                          # noqa: E402  (feeds are looked up in the module when run() is called)
 from speech_decoding_amd import load_config                        # noqa: E402
 from speech_decoding_amd.distributed import allreduce_gradients, broadcast_parameters, shard_range  # noqa: E402
@@ -145,7 +146,7 @@ def build_data(args, data_kind: str, device, rank: int, world: int, with_ids: bo
 def make_backward_and_step(brain_encoder, loss_func, params, optimizer, scaler, world: int, device):
     """backward_and_step(loss) for the loop: backward of the scaled loss, the gradient all-reduce under data parallelism, fp16's
     overflow guard, Adam."""
-    clip = isinstance(loss_func, CLIPLoss)
+    clip = isinstance(loss_func, (CLIPLoss, SigmoidLoss))   # a contrastive loss: it has parameters of its own
     fp16 = scaler.enabled            # (not `scale != 1`: a scale halved down to 1, or fp16_loss_scale=1, keeps the overflow guard)
     one = torch.ones((), dtype=torch.float32, device=device)       # d loss / d loss, resident (autograd would fill one per step)
 
@@ -155,7 +156,7 @@ def make_backward_and_step(brain_encoder, loss_func, params, optimizer, scaler, 
         if world > 1:        # (SUM of the still-scaled gradients: every rank then sees the same overflow, or none)
             if not brain_encoder.grads_are_reduced:
                 allreduce_gradients(params)
-            elif clip:       # the temperature's gradient; MSELoss has none
+            elif clip:       # the temperature's (and the sigmoid loss's bias's) gradient; MSELoss has none
                 allreduce_gradients(list(loss_func.parameters()))
         # fp16 only: an activation gradient that overflowed to inf / NaN must not reach Adam — the finiteness check is a
         # host read-back per step of ONE device flag written by one fused launch (fp16 is configs[4]'s dtype; bf16 / fp32
@@ -177,7 +178,7 @@ def make_guarded_step(brain_encoder, loss_func, params, optimizer, world: int, d
     reduces the same bits and takes the same decision — no further collective.  A non-finite gradient skips the step in every
     dtype (bf16 / fp32 run at scale 1, not dynamic): torch.nn.utils.clip_grad_norm_ would pass the NaN on to every parameter
     instead; that difference is deliberate.  As in make_backward_and_step, a skipped step has still moved BatchNorm's statistics."""
-    clip = isinstance(loss_func, CLIPLoss)
+    clip = isinstance(loss_func, (CLIPLoss, SigmoidLoss))   # a contrastive loss: it has parameters of its own
     one = torch.ones((), dtype=torch.float32, device=device)
 
     def backward_and_step(loss):
@@ -210,7 +211,7 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
     if duplicates not in ("ignore", "positive", "mask"):
         raise ValueError(f"clip_duplicates={duplicates}: expected ignore, positive or mask")
     if duplicates != "ignore" and str(args.get("loss", "clip")).lower() == "mse":
-        raise ValueError(f"clip_duplicates={duplicates} is an option of the CLIP loss; loss=mse has no negatives to correct")
+        raise ValueError(f"clip_duplicates={duplicates} is an option of the contrastive losses; loss=mse has no negatives to correct")
     use_ids = duplicates != "ignore"
     if train_batches is None and data_kind == "continuous" and args.dataset != "Brennan2018":
         raise ValueError("data=continuous is Brennan2018's input path (one stimulus, every subject): use dataset=Brennan2018")
@@ -259,12 +260,12 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
         feed.pack_embeddings(brain_encoder.compute_dtype)      # Y batches arrive as the loss's packed operand
     classifier = Classifier(args)
     loss_kind = str(args.get("loss", "clip")).lower()
-    if loss_kind not in ("clip", "mse"):
-        raise ValueError(f"loss={loss_kind}: expected clip or mse")
-    clip = loss_kind == "clip"
+    if loss_kind not in ("clip", "sigmoid", "mse"):
+        raise ValueError(f"loss={loss_kind}: expected clip, sigmoid or mse")
+    clip = loss_kind != "mse"            # a contrastive loss: parameters of its own, the speech-side prefetch, labels
     # (`ignore` is this script's word for "no labels"; the loss itself knows the two ways of using them)
     loss_args = args if use_ids or "clip_duplicates" not in args else type(args)({**args, "clip_duplicates": "positive"})
-    loss_func = (CLIPLoss(loss_args) if clip else MSELoss()).to(device)
+    loss_func = {"clip": lambda: CLIPLoss(loss_args), "sigmoid": lambda: SigmoidLoss(loss_args), "mse": MSELoss}[loss_kind]().to(device)
     loss_func.train()
     broadcast_parameters(brain_encoder)
     # MSELoss has no parameters of its own: Adam steps the encoder alone
@@ -348,6 +349,8 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
                "lrate": optimizer.param_groups[0]["lr"]}
         if clip:
             row["temp"] = loss_func.temp.item()
+        if loss_kind == "sigmoid":
+            row["bias"] = loss_func.bias.item()
         if guarded:          # read back here, once per epoch: the last step's unscaled norm and the skips so far
             row["grad_norm"] = optimizer.last_grad_norm
             row["skipped_steps"] = optimizer.skipped_steps
@@ -355,7 +358,8 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
         if rank == 0:
             log(f"Ep {epoch}/{args.epochs} | ", f"train l: {row['train_loss']:.3f} | ", f"test l: {row['test_loss']:.3f} | ",
                 f"trainTop10acc: {row['trainTop10acc']:.3f} | ", f"testTop10acc: {row['testTop10acc']:.3f} | ",
-                f"lr: {row['lrate']:.5f}", *([f"temp: {row['temp']:.3f}"] if clip else []))
+                f"lr: {row['lrate']:.5f}", *([f"temp: {row['temp']:.3f}"] if clip else []),
+                *([f"bias: {row['bias']:.3f}"] if "bias" in row else []))
             if wandb is not None:
                 wandb.log(row)
             torch.save(brain_encoder.state_dict(), "model_last.pt")
