@@ -48,7 +48,9 @@ extern "C" {
                                   sda_conv_kernel — which kernel sda_conv_gemm routes a convolution to, asked instead of mirrored;
                                   sda_clip_label_counts / sda_clip_logits_stats_masked / sda_clip_grad_labels / sda_clip_grad_y_labels /
                                   sda_clip_ranks_labels — the loss tail with speech labels;
-                                  sda_sigmoid_pairs / sda_sigmoid_finish / sda_sigmoid_grad_y — the pairwise sigmoid loss tail) */
+                                  sda_sigmoid_pairs / sda_sigmoid_finish / sda_sigmoid_grad_y — the pairwise sigmoid loss tail;
+                                  sda_clip_neg_stats / sda_clip_neg_rows / sda_clip_neg_grad / sda_clip_dz_windows /
+                                  sda_clip_dz_windows_span — extra speech negatives read in place from resident tracks) */
 #define SDA_ROW_PAD 16
 #define SDA_CH_ALIGN 64
 
@@ -454,6 +456,41 @@ int sda_clip_grad_y_finish(const float* part, int nparts, int Bg, const float* y
 int sda_clip_dz_supported(int Bm, int Bn, long row_elems, int dtype);
 int sda_clip_dz(const void* G, long g_pitch, const void* Y, const void* Z, void* out, const float* cscale, const float* rscale,
                 const float* out_scale, int Bm, int Bn, long row_elems, int dtype, void* stream);
+/* Extra speech NEGATIVES for the loss, read in place from a table of plain rows (csrc/clip_negatives.hip; ABI 4, additions):
+ * negative n < N is the K = T * row_elems elements from table row starts[n] on (retrieval.WindowBank), with squared norm wsq[n].
+ * It has no brain partner: m_nj = <W_n, Z_j> exp(temp) / (|W_n| |Z_j|) joins the column (brain -> speech) soft-max only, there
+ * is no row term and no gradient into the table.  The raw scores S[j][n] = <Z_j, W_n> (brain-major, s_pitch >= N) come from
+ * sda_sim_gemm_windows with the brain rows as X.  16-bit storage only, no atomics, every sum in an order fixed by the shape.
+ * sda_clip_neg_stats: mlog fp32 [Bn][N] = m_nj (sda_clip_logits_stats' expression), and col_lse[j] <- logaddexp(col_lse[j],
+ * lse_n m_nj) IN PLACE — between sda_clip_logits_stats(_masked) and sda_clip_grad(_labels) / sda_clip_grad_y(_labels), which
+ * then compute the loss and the paired coefficients against the widened column soft-max without another term.
+ * sda_clip_neg_grad (after sda_clip_grad on the same stream), D_nj = exp(m_nj - col_lse[j]):
+ *   Gn[n][j] = D_nj wmax / |W_n| (wmax = max_n |W_n|) as `dtype`, [sda_clip_neg_rows(N)][g_pitch]: the rows from N on and the
+ *   columns >= Bn are written as zeros; cscale_n[j] = inv_norm exp(temp) / (wmax |Z_j|); rscale[j] += inv_norm sum_n D_nj m_nj
+ *   / |Z_j|^2 and scalars[1] += inv_norm sum_nj D_nj m_nj — one writer each; colpart: Bn floats of scratch.
+ * sda_clip_neg_rows(N): N rounded up to whole 32-row K-steps, the rows Gn is allocated and read with. */
+int sda_clip_neg_stats(const float* S, long s_pitch, const float* wsq, const float* zsq, const float* temp, float* mlog,
+                       float* col_lse, int Bn, int N, void* stream);
+int sda_clip_neg_rows(int N);
+int sda_clip_neg_grad(const float* mlog, const float* col_lse, const float* wsq, const float* zsq, const float* temp,
+                      float inv_norm, void* Gn, long g_pitch, float* cscale_n, float* rscale, float* colpart, float* scalars,
+                      int Bn, int N, int dtype, void* stream);
+/* The negatives' part of the brain-side gradient, added to what sda_clip_dz wrote (row-layout `out`: sample j is out_pitch
+ * elements, its data behind SDA_ROW_PAD pad rows of row_elems):
+ *     out[j][SDA_ROW_PAD * row_elems + k] += out_scale[0] * cscale_n[j] * sum_{n < N} Gn[n][j] * table[starts[n] * row_elems + k]
+ * for j < Bn, k < K; nothing else of `out` is touched (pad rows and slack keep their bytes), each element has one writer.
+ * 256 x 256 tiles of (j, k) over 32-row K-steps of negatives; N, Bn and K / 256 need not be whole tiles.  A negative is
+ * addressed as the wave-uniform base table + base_row * row_elems plus a 32-bit byte offset: the CALLER (who holds the starts
+ * on the host) guarantees 0 <= starts[n] - base_row <= span_rows <= sda_clip_dz_windows_span(row_elems) = (2^31 - 256) /
+ * row_elems and that every window lies inside the table; a start that breaks the first promise is clamped into the span (a
+ * wrong sum, no wrapped address).  Reads stay inside the windows named by starts[0, N).  Refused before any launch: null
+ * pointers (out_scale may be NULL = 1); fp32; N, Bn < 1; K % 32 != 0 or K not whole table rows; row_elems % 64 != 0;
+ * base_row < 0; g_pitch < Bn or % 8; out_pitch < SDA_ROW_PAD * row_elems + K or % 8; span_rows outside [0, the span]; Gn, table
+ * or out not 16-byte aligned, starts not 4-byte aligned. */
+long sda_clip_dz_windows_span(long row_elems);
+int sda_clip_dz_windows(const void* Gn, long g_pitch, const void* table, const int32_t* starts, int base_row, long span_rows,
+                        long row_elems, void* out, long out_pitch, const float* cscale_n, const float* out_scale, int N, int Bn,
+                        long K, int dtype, void* stream);
 /* cnt[i] = #{local j : logits[i][j] beats diag[i]} (ties: lower global index wins) — Classifier ranks */
 int sda_clip_ranks(const float* logits, const float* diag, int32_t* cnt, int Bm, int Bn, int col0, void* stream);
 /* The loss tail with speech labels (csrc/clip_labels.hip): samples of the global batch that carry the same speech segment are

@@ -41,18 +41,47 @@ class ClipCtx:
     # scaled cosines a (the logits less the bias) and there are no lse
     bias: Optional[torch.Tensor] = None
     dbias: Optional[torch.Tensor] = None
+    # extra speech negatives read in place from a resident table (None: none): the candidates, their coefficient matrix G^n
+    # (sda_clip_neg_grad) and the per-column factor taken out of it — the second pass of clip_backward
+    negatives: Optional["ClipNegatives"] = None
+    Gn: Optional[torch.Tensor] = None
+    cscale_n: Optional[torch.Tensor] = None
+
+
+@dataclass
+class ClipNegatives:
+    """N speech negatives that are windows of a resident table of plain rows (every candidate of a retrieval.WindowBank):
+    negative n is the T rows from table row starts[n] on.  `lo`, `hi`: the smallest and largest start, from the host copy —
+    the span one launch addresses is checked against them before anything runs.  `bank` keeps the table alive."""
+    bank: object
+    table: torch.Tensor          # (L_total, pad64(F)) of the compute dtype
+    starts: torch.Tensor         # int32 [N] on the device
+    wsq: torch.Tensor            # fp32 [N] squared norms
+    N: int
+    lo: int
+    hi: int
+
+    @classmethod
+    def of(cls, bank) -> "ClipNegatives":
+        host = bank.starts_host
+        return cls(bank, bank.table, bank.starts, bank.norms_sq, len(bank), int(host.min()), int(host.max()))
 
 
 def clip_forward(Yt: torch.Tensor, Zt: torch.Tensor, temp: torch.Tensor, *, Bm: int, Bn: int, T: int, col0: int = 0,
                  reduction: str = "mean", B_global: Optional[int] = None, dist_group=None, want_grad: bool = True,
-                 ysq: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, duplicates: str = "positive"):
+                 ysq: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, duplicates: str = "positive",
+                 negatives: Optional[ClipNegatives] = None):
     """CLIP loss (loss.py:58-79) on RL embeddings: Yt holds the Bm (global) speech rows, Zt the Bn local
     brain rows.  Returns (loss_local_share, logits, ranks_count, ctx).  With `dist_group`, row statistics
     and the diagonal are merged across ranks so that the negatives span the global batch.
     `labels` (device int32 [Bm], one per global sample): samples with one label carry the same speech and are matches of one
     another: extra positives (duplicates="positive") or left out of the soft-max denominators ("mask").  None: the unlabelled
-    loss, launch for launch."""
-    st = clip_block_stats(Yt, Zt, temp, Bm=Bm, Bn=Bn, T=T, col0=col0, ysq=ysq, labels=labels, duplicates=duplicates)
+    loss, launch for launch.
+    `negatives`: further speech candidates without a brain partner, scored in place against this rank's brain rows; they widen
+    the brain -> speech soft-max (the column direction) only.  The caller guarantees that none carries the speech of a sample of
+    the global batch and, under data parallelism, that every rank is handed the same ones.  None: today's launches, one for one."""
+    st = clip_block_stats(Yt, Zt, temp, Bm=Bm, Bn=Bn, T=T, col0=col0, ysq=ysq, labels=labels, duplicates=duplicates,
+                          negatives=negatives)
     if dist_group is None:                       # one process: the block IS the whole matrix, its row lse came with the logits
         row_lse, diag = st.row_lse, st.diag
     else:
@@ -81,10 +110,12 @@ class ClipBlockStats:
     row_lse: torch.Tensor          # lse of each row over this block's columns only
     labels: Optional[torch.Tensor] = None
     duplicates: str = "positive"
+    negatives: Optional[ClipNegatives] = None
+    neg_logits: Optional[torch.Tensor] = None      # (Bn, N) fp32, brain-major; col_lse already holds their share
 
 
 def clip_block_stats(Yt, Zt, temp, *, Bm: int, Bn: int, T: int, col0: int = 0, ysq=None, labels=None,
-                     duplicates: str = "positive") -> ClipBlockStats:
+                     duplicates: str = "positive", negatives: Optional[ClipNegatives] = None) -> ClipBlockStats:
     """First half of clip_forward: norms, the (Bm x Bn) logits block of this rank's brain columns, per-row (max, sum exp)
     over the block, per-column lse over all rows, the positives' logits.  Rank-local: no collective.  With labels and
     duplicates="mask" the statistics leave out the repeats of a sample's own speech; "positive" keeps the unlabelled ones."""
@@ -102,8 +133,19 @@ def clip_block_stats(Yt, Zt, temp, *, Bm: int, Bn: int, T: int, col0: int = 0, y
         logits, row_max, row_sum, col_lse, diag, row_lse = ops.clip_logits_stats_masked(S, ysq, zsq, temp, labels, Bm, Bn, col0)
     else:
         logits, row_max, row_sum, col_lse, diag, row_lse = ops.clip_logits_stats(S, ysq, zsq, temp, Bm, Bn, col0)
+    neg_logits = None
+    if negatives is not None:
+        # the negatives' raw scores against this block's brain rows (their data rows: the windowed GEMM's X with the sample
+        # pitch), then their logits and their share of the column lse (the masked one in mask mode).  Rank-local: no collective
+        ng, K = negatives, T * Fp
+        Sn = torch.empty((Bn, L.pad_channels(ng.N)), dtype=torch.float32, device=Zt.device)
+        ks = L.load().sda_sim_gemm_ksplit(Bn, ng.N, K, ops.dt_code(Zt.dtype))
+        partial = torch.empty(ks * Sn.numel() if ks > 1 else 0, dtype=torch.float32, device=Zt.device)
+        ops.sim_gemm_windows_into(Zt.reshape(-1)[L.ROW_PAD * Fp:], row_elems, ng.table.reshape(-1), ng.starts, ng.lo, ng.hi, Fp,
+                                  Bn, ng.N, K, ks, partial, Sn)
+        neg_logits = ops.clip_neg_stats(Sn, ng.wsq, zsq, temp, col_lse, Bn, ng.N)
     return ClipBlockStats(Yt, Zt, temp, Bm, Bn, col0, row_elems, ysq, zsq, logits, row_max, row_sum, col_lse, diag, row_lse,
-                          labels, duplicates)
+                          labels, duplicates, negatives, neg_logits)
 
 
 def clip_block_finish(st: ClipBlockStats, row_lse, diag, *, reduction: str = "mean", B_global: Optional[int] = None,
@@ -128,15 +170,24 @@ def clip_block_finish(st: ClipBlockStats, row_lse, diag, *, reduction: str = "me
         G, rscale, cscale, scalars = ops.clip_grad_labels(logits, row_lse, col_lse, ysq, zsq, temp, labels, counts, st.duplicates,
                                                           inv_norm, col0, Yt.dtype)
         cnt = ops.clip_ranks_labels(logits, diag, labels, col0)
+    Gn = cscale_n = None
+    if st.negatives is not None:                   # behind clip_grad: it adds the negatives' shares to rscale and d loss / d temp
+        Gn, cscale_n = ops.clip_neg_grad(st.neg_logits, col_lse, st.negatives.wsq, zsq, temp, inv_norm, rscale, scalars, Yt.dtype)
     ctx = ClipCtx(Bm=Bm, Bn=Bn, col0=col0, G=G, rscale=rscale, Yt=Yt, Zt=Zt, row_elems=row_elems, dtemp=scalars[1:2],
                   cscale=cscale, logits=logits, row_lse=row_lse, col_lse=col_lse, ysq=ysq, zsq=zsq, temp=temp, inv_norm=inv_norm,
-                  labels=labels, counts=counts, duplicates=st.duplicates)
+                  labels=labels, counts=counts, duplicates=st.duplicates, negatives=st.negatives, Gn=Gn, cscale_n=cscale_n)
     return scalars[0:1], logits, cnt, ctx
 
 
 def clip_backward(ctx: ClipCtx, dZt: torch.Tensor, dloss: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """dZ = dloss * (diag(c) G^T Y - diag(r) Z)  (gradient of the loss share w.r.t. the local brain embeddings)."""
-    return ops.clip_dz(ctx.G, ctx.Yt, ctx.Zt, dZt, ctx.rscale, ctx.cscale, Bm=ctx.Bm, Bn=ctx.Bn, row_elems=ctx.row_elems, out_scale=dloss)
+    """dZ = dloss * (diag(c) G^T Y - diag(r) Z)  (gradient of the loss share w.r.t. the local brain embeddings); with negatives
+    a second pass adds dloss * diag(c^n) G^n^T W, contracted over their windows in place (r already holds their share)."""
+    ops.clip_dz(ctx.G, ctx.Yt, ctx.Zt, dZt, ctx.rscale, ctx.cscale, Bm=ctx.Bm, Bn=ctx.Bn, row_elems=ctx.row_elems, out_scale=dloss)
+    ng = ctx.negatives
+    if ng is not None:
+        T = ctx.row_elems // ctx.Zt.shape[1] - L.ROW_PAD
+        ops.clip_dz_windows(ctx.Gn, ng.table, ng.starts, ng.lo, ng.hi, dZt, ctx.cscale_n, N=ng.N, Bn=ctx.Bn, T=T, out_scale=dloss)
+    return dZt
 
 
 def clip_grad_y_coeffs(ctx: ClipCtx, zsq_all: torch.Tensor, dtype, **layout):

@@ -159,6 +159,33 @@ class _ResidentEmbeddings:
             raise SdaError("speech_bank: this feed holds materialised Y (N, F, T) segments, not a WindowBank")
         return bank if indices is None else bank.select(indices)
 
+    negatives_seed = 0x6E6567     # of draw_negatives' own generator: the same on every rank
+    _neg_rng = None
+
+    def draw_negatives(self, n: int, batch_segments, pool) -> np.ndarray:
+        """`n` distinct segment indices out of `pool` (the train split) none of which carries the speech id of any segment of
+        `batch_segments` (the GLOBAL batch, on every rank alike) — what CLIPLoss.forward takes as `negatives` once speech_bank()
+        has selected them.  Drawn without replacement from a generator of the feed's own that nothing else uses (seeded with
+        `negatives_seed` at the first call: every rank makes the same draws; `rng` and NumPy's global generator stay reserved
+        as described above, and a run that never asks consumes nothing).  ValueError when the pool cannot supply `n`."""
+        bank = self._bank()
+        if bank is None:
+            raise SdaError("draw_negatives: this feed holds materialised Y (N, F, T) segments, not a WindowBank")
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"draw_negatives: n={n} must be at least 1")
+        pool = np.unique(np.asarray(pool, dtype=np.int64).reshape(-1))
+        batch = np.asarray(torch.as_tensor(batch_segments, dtype=torch.int64).numpy(), dtype=np.int64).reshape(-1)
+        self._check_segments(pool)
+        self._check_segments(batch)
+        ids = bank.starts_host
+        free = pool[~np.isin(ids[pool], ids[batch])]
+        if len(free) < n:
+            raise ValueError(f"draw_negatives: the pool holds {len(free)} segments whose speech is not in the batch, {n} were asked for")
+        if self._neg_rng is None:
+            self._neg_rng = np.random.RandomState(self.negatives_seed)
+        return free[self._neg_rng.choice(len(free), size=n, replace=False)]
+
     def pack_embeddings(self, dtype: torch.dtype, chunk: int = 128):
         """Keep the speech embeddings resident as a row-layout table in `dtype` (the encoder's compute dtype): batch() then
         hands out Y as a zero-copy (B, F, T) view of ONE gather kernel's output, which CLIPLoss consumes as its packed operand —

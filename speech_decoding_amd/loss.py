@@ -347,13 +347,42 @@ _RECYCLED = ("CLIPLoss.backward: the packed {what} rows of this forward were rec
              "(more than `ring_depth` forwards before this backward); raise loss_func._state.ring_depth or call backward earlier")
 
 
+def speech_negatives(negatives, F: int, T: int, dtype, device) -> Optional[clip.ClipNegatives]:
+    """Check the extra speech negatives of one forward — a retrieval.WindowBank, every candidate of which is a negative — against
+    the brain rows' shape, compute dtype and device, and name them for the kernels.  Everything is refused here, before the
+    first launch.  None passes."""
+    if negatives is None or isinstance(negatives, clip.ClipNegatives):
+        return negatives
+    from .retrieval import WindowBank
+    if not isinstance(negatives, WindowBank):
+        raise L.SdaError(f"CLIPLoss: negatives must be a WindowBank (windows of resident speech tracks, e.g. feed.speech_bank(idx)), "
+                         f"got {type(negatives).__name__}; a tensor of materialised segments is not taken: load each as a track")
+    if dtype == torch.float32:
+        raise L.SdaError("CLIPLoss: negatives with float32 compute; the windowed similarity GEMM serves 16-bit storage only (bfloat16 "
+                         "or float16) and nothing materialises the windows instead: run the loss on bfloat16 or float16 embeddings")
+    if (negatives.F, negatives.T) != (F, T) or negatives.dtype != dtype:
+        raise L.SdaError(f"CLIPLoss: negatives of F={negatives.F}, T={negatives.T}, {negatives.dtype} against brain embeddings of "
+                         f"F={F}, T={T}, {dtype} (the compute dtype)")
+    if len(negatives) == 0:
+        raise L.SdaError("CLIPLoss: an empty bank of negatives (pass negatives=None for none)")
+    ng = clip.ClipNegatives.of(negatives)
+    if ng.table.device != torch.device(device):
+        raise L.SdaError(f"CLIPLoss: the negatives' table is on {ng.table.device}, the brain embeddings on {device}")
+    span = min(ops.sim_gemm_windows_span(negatives.row_elems), ops.clip_dz_windows_span(negatives.row_elems))
+    if ng.hi - ng.lo > span:
+        raise L.SdaError(f"CLIPLoss: the negatives' windows span table rows {ng.lo} ... {ng.hi}, more than the {span} rows (4 GB) one "
+                         "launch addresses; draw them from neighbouring tracks (nothing is chunked)")
+    return ng
+
+
 class _ClipFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, module: "CLIPLoss", Y, Z, temp, labels=None):
+    def forward(ctx, module: "CLIPLoss", Y, Z, temp, labels=None, negatives=None):
         import torch.distributed as dist
         B, F, T = Z.shape
         lab = speech_labels(labels, B, Z.device)    # refused here, before the first launch, when they are malformed
         dtype = Z.dtype if Z.dtype in ops.COMPUTE_DTYPES else torch.float32
+        neg = speech_negatives(negatives, F, T, dtype, Z.device)
         Zt = as_rows(Z, B, F, T, dtype, "y (brain embeddings)")
         group = _dist_group() if module.global_negatives else None
         state = module._state
@@ -379,7 +408,7 @@ class _ClipFn(torch.autograd.Function):
         lab_all = None if lab is None else gather_labels(lab, B, group)
         loss, logits, cnt, cctx = clip.clip_forward(yg.rows, Zt, temp.detach(), Bm=yg.n, Bn=B, T=T, col0=yg.col0,
                                                     reduction=module.reduction, B_global=yg.n, dist_group=group, ysq=yg.sq,
-                                                    labels=lab_all, duplicates=module.duplicates)
+                                                    labels=lab_all, duplicates=module.duplicates, negatives=neg)
         ctx.z_gather = None
         if want_y and group is not None:
             # the speech-side gradient contracts over the brain rows of ALL ranks: gather them (and their norms) now, behind
@@ -405,7 +434,7 @@ class _ClipFn(torch.autograd.Function):
         B, F, T = ctx.shape
         dZ = dY = None
         if dloss is None:                           # (the loss itself took no part in what was differentiated)
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         scale = dloss.to(torch.float32)
         if (ctx.z_requires_grad or ctx.y_requires_grad) and ctx.y_slot is not None and not ctx.y_slot.valid():
             raise L.SdaError(_RECYCLED.format(what="speech"))
@@ -419,7 +448,7 @@ class _ClipFn(torch.autograd.Function):
             dYt = _clip_dy(ctx, scale.reshape(1).contiguous())
             dY = ops.rows_view(dYt, B, F, T) if ctx.y_rows else ops.unpack_rows(dYt, B, F, T, ctx.y_dtype)
         dtemp = ops.scalar_mul(c.dtemp, scale.reshape(1))
-        return None, dY, dZ, dtemp, None
+        return None, dY, dZ, dtemp, None, None
 
 
 def _clip_dy(ctx, scale: torch.Tensor) -> torch.Tensor:
@@ -484,12 +513,21 @@ class CLIPLoss(nn.Module):
         """Drop the persistent packed-speech buffers (e.g. between a training and an evaluation phase)."""
         self._state.clear()
 
-    def forward(self, x, y, fast=True, return_logits=False, labels=None):
+    def forward(self, x, y, fast=True, return_logits=False, labels=None, negatives=None):
         """`labels`: the speech id of each local sample (a host sequence, a numpy array or an int32 / int64 tensor of length B):
         samples of the global batch with one id carry the same speech segment and are treated as `self.duplicates` says.
-        None: every sample is its own class — the reference's loss."""
+        None: every sample is its own class — the reference's loss.
+        `negatives`: a retrieval.WindowBank (typically feed.speech_bank(feed.draw_negatives(...)), which shares the resident
+        table) every candidate of which is a further speech negative: it has no brain partner, so it joins the brain -> speech
+        soft-max only — B_g + N candidates per brain segment, the direction `retrieve` scores — and the loss stays normalised by
+        the global batch.  The windows are read in place (16-bit compute only); they get no gradient.  The caller guarantees
+        that none carries the speech id of a sample of the global batch and that every rank is handed the same ones.  The
+        returned logits stay the paired block.  None: today's launches."""
         batch_size = x.size(0)
         assert batch_size > 1, "Batch size must be greater than 1."               # loss.py:40
+        if negatives is not None:                   # refused before the labels' upload, the first launch of a labelled forward
+            negatives = speech_negatives(negatives, y.size(1), y.size(2), y.dtype if y.dtype in ops.COMPUTE_DTYPES else torch.float32,
+                                         y.device)
         if labels is not None:
             labels = speech_labels(labels, batch_size, y.device)
         if not fast:
@@ -497,10 +535,10 @@ class CLIPLoss(nn.Module):
             # temperature (which then receives no gradient).  The symmetric loss is the same function of it, so the same
             # kernels run with a zero log-temperature; only the returned logits are turned.
             zero = torch.zeros(1, dtype=torch.float32, device=self.temp.device)
-            loss, logits = _ClipFn.apply(self, x, y, zero, labels)
+            loss, logits = _ClipFn.apply(self, x, y, zero, labels, negatives)
             self.last_logits = logits
             return (logits.t(), loss) if return_logits else loss
-        loss, logits = _ClipFn.apply(self, x, y, self.temp, labels)
+        loss, logits = _ClipFn.apply(self, x, y, self.temp, labels, negatives)
         self.last_logits = logits
         if return_logits:
             return logits, loss

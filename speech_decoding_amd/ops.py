@@ -924,6 +924,87 @@ def clip_dz(G, Yt, Zt, out, rscale, cscale, *, Bm, Bn, row_elems, out_scale=None
                            acc_scale=cscale)
 
 
+def clip_neg_rows(N: int) -> int:
+    """Rows the negatives' coefficient matrix is allocated and read with: N in whole 32-row K-steps (asked, not mirrored)."""
+    return L.load().sda_clip_neg_rows(N)
+
+
+def clip_dz_windows_span(row_elems: int) -> int:
+    """Largest start - base_row one clip_dz_windows launch serves for table rows of `row_elems` elements (asked, not mirrored)."""
+    return L.load().sda_clip_dz_windows_span(row_elems)
+
+
+def _need_neg(who: str, N: int, Bn: int, **named):
+    """fp32 device vectors of the negatives' tail: name=(tensor, count)."""
+    if N < 1 or Bn < 1:
+        raise L.SdaError(f"{who}: needs at least one negative and one brain column, got N={N}, Bn={Bn}")
+    for name, (t, count) in named.items():
+        _need_values(t, torch.float32, count, f"{who}: {name} must hold {count} contiguous fp32 values on the device")
+
+
+def clip_neg_stats(S, wsq, zsq, temp, col_lse, Bn: int, N: int):
+    """The negatives' logits m [Bn][N] (brain-major fp32) from their raw scores S [Bn][>= N] against the brain rows, and their
+    share merged into col_lse IN PLACE: col_lse[j] <- logaddexp(col_lse[j], lse_n m[j][n]) (sda_clip_neg_stats)."""
+    _need_cuda(S, wsq, zsq, temp, col_lse)
+    if S.dtype != torch.float32 or S.dim() != 2 or S.stride(1) != 1 or S.shape[0] < Bn or S.shape[1] < N:
+        raise L.SdaError(f"clip_neg_stats: S must be an fp32 (>= {Bn}, >= {N}) matrix with unit column stride")
+    _need_neg("clip_neg_stats", N, Bn, wsq=(wsq, N), zsq=(zsq, Bn), temp=(temp, 1), col_lse=(col_lse, Bn))
+    mlog = torch.empty((Bn, N), dtype=torch.float32, device=S.device)
+    L.check(L.load().sda_clip_neg_stats(_p(S), S.stride(0), _p(wsq), _p(zsq), _p(temp), _p(mlog), _p(col_lse), Bn, N, _st()),
+            "clip_neg_stats")
+    return mlog
+
+
+def clip_neg_grad(mlog, col_lse, wsq, zsq, temp, inv_norm, rscale, scalars, dtype):
+    """(Gn, cscale_n) of the negatives' part of dZ (sda_clip_neg_grad): Gn [clip_neg_rows(N)][pad64(Bn)] of `dtype` with the rows
+    from N on and the pad columns zero.  The negatives' shares are ADDED to rscale [Bn] and to scalars[1] (d loss / d temp), which
+    clip_grad(_labels) has written before on the same stream."""
+    _need_cuda(mlog, col_lse, wsq, zsq, temp, rscale, scalars)
+    if dtype not in (torch.bfloat16, torch.float16):
+        raise L.SdaError(f"clip_neg_grad: dtype {dtype}; the window path serves 16-bit storage only (bfloat16 or float16)")
+    if mlog.dim() != 2:
+        raise L.SdaError("clip_neg_grad: mlog must be the (Bn, N) logits of clip_neg_stats")
+    Bn, N = mlog.shape
+    _need_neg("clip_neg_grad", N, Bn, mlog=(mlog, Bn * N), col_lse=(col_lse, Bn), wsq=(wsq, N), zsq=(zsq, Bn), temp=(temp, 1),
+              rscale=(rscale, Bn), scalars=(scalars, 2))
+    dev = mlog.device
+    Gn = torch.empty((clip_neg_rows(N), L.pad_channels(Bn)), dtype=dtype, device=dev)       # every element is written by the kernel
+    cscale_n = torch.empty(Bn, dtype=torch.float32, device=dev)
+    colpart = torch.empty(Bn, dtype=torch.float32, device=dev)
+    L.check(L.load().sda_clip_neg_grad(_p(mlog), _p(col_lse), _p(wsq), _p(zsq), _p(temp), float(inv_norm), _p(Gn), Gn.shape[1],
+                                       _p(cscale_n), _p(rscale), _p(colpart), _p(scalars), Bn, N, dt_code(dtype), _st()), "clip_neg_grad")
+    return Gn, cscale_n
+
+
+def clip_dz_windows(Gn, table, starts, lo: int, hi: int, out, cscale_n, *, N: int, Bn: int, T: int, out_scale=None):
+    """out[j][ROW_PAD * Fp + k] += out_scale * cscale_n[j] * sum_{n < N} Gn[n][j] * table[starts[n] * Fp + k], k < T * Fp: the
+    negatives' part of dZ on top of what clip_dz wrote into the row-layout buffer `out` (sda_clip_dz_windows).  `lo`, `hi`: the
+    smallest and largest start, from the caller's host copy — a span that does not fit the kernel's 32-bit offset and a window
+    past the table's end are refused here."""
+    _need_cuda(Gn, table, starts, out, cscale_n, out_scale)
+    _need_values(starts, torch.int32, N, "clip_dz_windows: starts must hold N contiguous int32 table rows")
+    if table.dim() != 2 or not table.is_contiguous() or table.dtype not in (torch.bfloat16, torch.float16):
+        raise L.SdaError("clip_dz_windows: the table must be a contiguous (rows, pad64(F)) matrix of bfloat16 or float16 (there is "
+                         "no fp32 window path)")
+    Fp = table.shape[1]
+    K = T * Fp
+    if Gn.dtype != table.dtype or out.dtype != table.dtype:
+        raise L.SdaError("clip_dz_windows: Gn, the table and out must share one 16-bit dtype")
+    if Gn.dim() != 2 or Gn.stride(1) != 1 or Gn.shape[0] < clip_neg_rows(N) or Gn.shape[1] < Bn:
+        raise L.SdaError(f"clip_dz_windows: Gn must hold {clip_neg_rows(N)} rows (N in whole K-steps, zeros from row N on) of >= {Bn} columns")
+    if not out.is_contiguous() or out.dim() != 2 or out.shape[1] != Fp or out.shape[0] < Bn * L.rows_tp(T):
+        raise L.SdaError(f"clip_dz_windows: out must be a row-layout buffer of >= {Bn} samples of {L.rows_tp(T)} rows of {Fp} elements")
+    _need_values(cscale_n, torch.float32, Bn, "clip_dz_windows: cscale_n must hold Bn contiguous fp32 values")
+    if hi - lo > clip_dz_windows_span(Fp):
+        raise L.SdaError(f"clip_dz_windows: the negatives' windows span table rows {lo} ... {hi}, more than the "
+                         f"{clip_dz_windows_span(Fp)} rows (4 GB) one launch addresses")
+    if lo < 0 or hi < lo or hi * Fp + K > table.numel():
+        raise L.SdaError(f"clip_dz_windows: windows [{lo}, {hi}] x {K} elements leave the table of {table.numel()} elements")
+    L.check(L.load().sda_clip_dz_windows(_p(Gn), Gn.stride(0), _p(table), _p(starts), lo, hi - lo, Fp, _p(out), L.rows_tp(T) * Fp,
+                                         _p(cscale_n), _p(out_scale), N, Bn, K, dt_code(table.dtype), _st()), "clip_dz_windows")
+    return out
+
+
 def sa_gemm_tables(cos_t: torch.Tensor, sin_t: torch.Tensor):
     """Operand tables of SpatialAttention's two contractions, built from the (K2, C) cos/sin buffers:
     forward  a[o][c] = sum_m Re z[o][m] cos[m][c] + Im z[o][m] sin[m][c]  ->  rows c of [cos | sin] interleaved in m,

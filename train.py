@@ -31,6 +31,8 @@ either one runs the step through `make_guarded_step` (GuardedAdam: norm, guard, 
 `clip_duplicates=positive|mask` (default `ignore`: the reference's loss) hands the feed's speech ids to the loss and the
 accuracies: the sampler draws with replacement, so a batch can hold one speech segment twice under two brain recordings, and the
 repeat then counts as a further positive (or as no negative) instead of a wrong answer.
+`clip_negatives=N` (default 0; data=tracks with loss=clip) contrasts every brain segment against N further speech windows per step,
+drawn from the training split's resident tracks and read in place (CLIPLoss.forward's `negatives`); evaluation is unchanged.
 """
 from __future__ import annotations
 
@@ -87,11 +89,13 @@ class SyntheticSegments:
         return self.X[i], self.Y[i], self.subj[i]
 
 
-def build_data(args, data_kind: str, device, rank: int, world: int, with_ids: bool = False):
+def build_data(args, data_kind: str, device, rank: int, world: int, with_ids: bool = False, negatives: int = 0):
     """The synthetic data of a `data=` kind -> (feed, train_batches, test_batch).  `feed` is None for the pool; otherwise the
     callables hand out THIS rank's shard of every batch, and feed.pack_embeddings is the caller's to call once the encoder's
     compute dtype is known.  `with_ids`: a feed's batches are the 4-tuples (X, Y, subject_idxs, chunkIDs) with the segments'
-    speech ids (the pool draws without repeats and has none to give).
+    speech ids (the pool draws without repeats and has none to give).  `negatives` (data=tracks): every training batch ends with
+    a WindowBank of that many further speech windows of the TRAINING split, none of which carries the speech of a segment of the
+    global batch (feed.draw_negatives: the same draw on every rank); the test batch has none.
 
     data=pool (default): a resident pool of ready-made segments, every rank slicing its shard out of the global batch;
     data=resident: the reference's own input path on the GPU — recordings resident in HBM, RandomSampler(replacement=True)
@@ -130,11 +134,20 @@ def build_data(args, data_kind: str, device, rank: int, world: int, with_ids: bo
     updates = int(args.get("updates_per_epoch", max(1, len(train_idx) // batch_size)))
     epoch_no = [0]
 
+    def sampler_seed(epoch: int) -> int:
+        return 4321 + epoch
+
     def train_batches():
-        sampler = D.ShardedRandomSampler(len(train_idx), batch_size, updates, rank, world, seed=4321 + epoch_no[0])
+        sampler = D.ShardedRandomSampler(len(train_idx), batch_size, updates, rank, world, seed=sampler_seed(epoch_no[0]))
         epoch_no[0] += 1
         # (under data parallelism the draws for the whole global batch are made on every rank alike and sliced)
-        yield from feed.batches(sampler, index_map=train_idx, with_ids=with_ids)
+        if not negatives:
+            yield from feed.batches(sampler, index_map=train_idx, with_ids=with_ids)
+            return
+        # the global batches once more, from a twin of the sampler: every rank excludes the WHOLE batch's speech and draws alike
+        twin = D.ShardedRandomSampler(len(train_idx), batch_size, updates, rank, world, seed=sampler_seed(epoch_no[0] - 1))
+        for out, gidx in zip(feed.batches(sampler, index_map=train_idx, with_ids=with_ids), twin.global_batches()):
+            yield (*out, feed.speech_bank(feed.draw_negatives(negatives, np.asarray(train_idx)[gidx.numpy()], train_idx)))
 
     def test_batch():
         lo, hi = shard_range(len(test_idx), rank, world)
@@ -213,6 +226,12 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
     if duplicates != "ignore" and str(args.get("loss", "clip")).lower() == "mse":
         raise ValueError(f"clip_duplicates={duplicates} is an option of the contrastive losses; loss=mse has no negatives to correct")
     use_ids = duplicates != "ignore"
+    n_neg = int(args.get("clip_negatives", 0))
+    if n_neg < 0:
+        raise ValueError(f"clip_negatives={n_neg}: expected a number of extra speech negatives per step, 0 for none")
+    if n_neg and (train_batches is not None or data_kind != "tracks" or str(args.get("loss", "clip")).lower() != "clip"):
+        raise ValueError(f"clip_negatives={n_neg} needs data=tracks (the negatives are windows of the resident speech tracks) and "
+                         "loss=clip")
     if train_batches is None and data_kind == "continuous" and args.dataset != "Brennan2018":
         raise ValueError("data=continuous is Brennan2018's input path (one stimulus, every subject): use dataset=Brennan2018")
     if train_batches is None and data_kind == "tracks" and args.dataset != "Gwilliams2022":
@@ -242,18 +261,20 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
 
     feed = None          # a resident feed hands out this rank's shard; batches of the pool, or the caller's, are whole and sliced here
     if train_batches is None:
-        feed, train_batches, test_batch = build_data(args, data_kind, device, rank, world, with_ids=use_ids)
+        feed, train_batches, test_batch = build_data(args, data_kind, device, rank, world, with_ids=use_ids, negatives=n_neg)
 
     def local_shard(batch):
-        """(X, Y, subject_idxs, labels): labels = the batch's speech ids as the loss takes them (checked and uploaded once for
-        the loss and the accuracies), or None — clip_duplicates=ignore, or a batch that comes without ids."""
+        """(X, Y, subject_idxs, labels, negatives): labels = the batch's speech ids as the loss takes them (checked and uploaded
+        once for the loss and the accuracies), or None — clip_duplicates=ignore, or a batch that comes without ids; negatives =
+        the bank of extra speech negatives a training batch ends with under clip_negatives, else None."""
         X, Y, subject_idxs = batch[:3]
-        ids = batch[3] if use_ids and len(batch) == 4 else None
+        neg = batch[-1] if n_neg and isinstance(batch[-1], D.WindowBank) else None
+        ids = batch[3] if use_ids and len(batch) - (neg is not None) == 4 else None
         if world > 1 and feed is None:
             lo, hi = shard_range(X.shape[0], rank, world)
             X, Y, subject_idxs = X[lo:hi], Y[lo:hi], subject_idxs[lo:hi]
             ids = None if ids is None else ids[lo:hi]
-        return X, Y, subject_idxs, None if ids is None else speech_labels(ids, X.shape[0], device)
+        return X, Y, subject_idxs, None if ids is None else speech_labels(ids, X.shape[0], device), neg
 
     brain_encoder = BrainEncoder(args).to(device)
     if feed is not None:
@@ -309,13 +330,16 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
         ahead = next(batches, None)
         first = True
         while ahead is not None:
-            X, Y, subject_idxs, labels = ahead
+            X, Y, subject_idxs, labels, negatives = ahead
             ahead = next(batches, None)
             if first and clip:
                 loss_func.prefetch(Y, brain_encoder.compute_dtype)
                 first = False
             Z = brain_encoder(X, subject_idxs)
-            loss = loss_func(Y, Z) if labels is None else loss_func(Y, Z, labels=labels)
+            if negatives is not None:
+                loss = loss_func(Y, Z, labels=labels, negatives=negatives)
+            else:
+                loss = loss_func(Y, Z) if labels is None else loss_func(Y, Z, labels=labels)
             # The reference reads loss.item() and the two accuracies back on the host here, every batch (train.py:194-198):
             # a host<->GPU synchronisation in the middle of the step.  The same numbers are kept on the device and read
             # once per epoch, below: the host keeps enqueueing while the GPU works (8 vs 16 ms per step at batch 256).
@@ -336,7 +360,7 @@ def run(args, train_batches: Optional[Callable] = None, test_batch: Optional[Cal
         brain_encoder.eval()
         te_loss, te_top1, te_top10 = [], [], []
         with torch.no_grad():
-            X, Y, subject_idxs, labels = local_shard(test_batch())
+            X, Y, subject_idxs, labels, _ = local_shard(test_batch())
             Z = brain_encoder(X, subject_idxs)
             te_loss.append((loss_func(Y, Z) if labels is None else loss_func(Y, Z, labels=labels)).item())
             t1, t10 = classifier(Z, Y, test=True, labels=labels)
