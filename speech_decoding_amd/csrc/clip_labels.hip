@@ -121,9 +121,11 @@ __global__ __launch_bounds__(256) void clip_grad_labels_kernel(const float* __re
     const float l = logits[(size_t)i * Bn + j];
     const bool same = labels[i] == lj;
     const float d = label_D<MODE>(l, row_lse[i], cl, same, i == col0 + j, two_over_n);
-    dl += d * l;
+    // a repeat under MASK is left out, not multiplied by its zero D: a non-finite logit or norm there reaches nothing
+    const bool drop = MODE == SDA_CLIP_DUP_MASK && same && i != col0 + j;
+    if (!drop) dl += d * l;
     if (MODE == SDA_CLIP_DUP_POSITIVE && same) ps += l;
-    Elem<E>::st(G + (size_t)i * g_pitch + j, d * (ymax / sqrtf(ysq[i])));
+    Elem<E>::st(G + (size_t)i * g_pitch + j, drop ? 0.f : d * (ymax / sqrtf(ysq[i])));
   }
   dl = block_sum(dl, sh) * inv_norm;
   if (MODE == SDA_CLIP_DUP_POSITIVE) ps = block_sum(ps, sh);
@@ -162,13 +164,18 @@ __global__ __launch_bounds__(256) void clip_grad_y_labels_kernel(const float* __
   for (int k = 0; k < 16; ++k) {
     const int cc = w + 4 * k, c = c0 + cc, s = c / seg_pitch, o = c - s * seg_pitch, i = s * seg + o;
     const bool iv = o < seg && i < Bm;             // (uniform over the wave)
-    float d = 0.f, dl = 0.f;
+    float g = 0.f, dl = 0.f;
     if (iv && jv) {
       const float l = logits[(size_t)i * Bn + j];
-      d = label_D<MODE>(l, row_lse[i], cl, labels[i] == lj, i == col0 + j, two_over_n);
-      dl = d * l;
+      const bool same = labels[i] == lj;
+      // (a repeat under MASK is left out, not multiplied by its zero D)
+      if (!(MODE == SDA_CLIP_DUP_MASK && same && i != col0 + j)) {
+        const float d = label_D<MODE>(l, row_lse[i], cl, same, i == col0 + j, two_over_n);
+        g = d * zf;
+        dl = d * l;
+      }
     }
-    tile[cc][lane] = (iv && jv) ? d * zf : 0.f;
+    tile[cc][lane] = g;
     dl = wave_sum(dl);
     if (iv && jt < nparts && lane == 0) part[(size_t)jt * Bm + i] = dl;
   }

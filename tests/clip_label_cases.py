@@ -180,11 +180,18 @@ def check_masked_stats(c, logits, row_max, row_sum, col_lse, diag, row_lse):
     return out
 
 
-def emul_masked_lse(x, keep, dim, hw=0):
-    """(max, sum exp(x - max), lse) along dim over the kept entries, fp32; nothing kept: (-inf, 0, -inf)"""
+def emul_masked_lse(x, keep, dim, hw=0, mutant=None):
+    """(max, sum exp(x - max), lse) along dim over the kept entries, fp32; nothing kept: (-inf, 0, -inf).  Every mask is a select:
+    an entry that is left out reaches nothing, whatever it holds.  mutant lse_max_skips_nan: the maximum is fmaxf's, which drops a
+    NaN operand (the sum still meets it: what the mutant loses is the row's maximum, which the cross-rank merge consumes)"""
     ninf = torch.full((), -math.inf)
-    mx = torch.where(keep, x, ninf).amax(dim)
-    sh = torch.where(torch.isinf(mx), torch.zeros_like(mx), mx).unsqueeze(dim)
+    xm = torch.where(keep, x, ninf)
+    if mutant == "lse_max_skips_nan":
+        xm = torch.where(torch.isnan(xm), ninf, xm)
+    mx = xm.amax(dim)
+    # nothing kept: no term is added, whatever the shift.  (Decided by the mask, not by the maximum's value: a row whose kept
+    # logits are all -inf has exp(-inf - -inf) = NaN in its sum, on the device and in float64 alike.)
+    sh = torch.where(keep.any(dim), mx, torch.zeros_like(mx)).unsqueeze(dim)
     s = torch.where(keep, _exp(x - sh, hw), torch.zeros(())).sum(dim)
     return mx, s, mx + _log(s)
 
@@ -198,8 +205,8 @@ def emul_masked_stats(c, hw=0, mutant=None):
         keep = ~c["same"]
     if mutant == "labels_without_col0":
         keep = ~(c["labels"][:, None] == c["labels"][None, :Bn]) | c["pos"]
-    mx, s, rl = emul_masked_lse(l, keep, 1, hw)
-    cl = emul_masked_lse(l, torch.ones_like(keep) if mutant == "mask_rows_not_columns" else keep, 0, hw)[2]
+    mx, s, rl = emul_masked_lse(l, keep, 1, hw, mutant)
+    cl = emul_masked_lse(l, torch.ones_like(keep) if mutant == "mask_rows_not_columns" else keep, 0, hw, mutant)[2]
     ii = torch.arange(Bm)
     diag = torch.where(c["inb"], l[ii, (ii - col0).clamp(0, Bn - 1)], torch.zeros(Bm))
     return l, mx, s, cl, diag, rl
@@ -249,11 +256,13 @@ def grad_labels_ref(c, mode, dtype):
     ymax = math.sqrt(float(ysq.max()))
     f = (ymax / torch.sqrt(ysq))[:, None]
     G = torch.zeros(Bm + 1, pad64(Bn), dtype=F64)
-    G[:Bm, :Bn] = D * f
+    drop, zero = dropped(c, mode), torch.zeros((), dtype=F64)          # (selected out, never 0 * l or 0 * f)
+    G[:Bm, :Bn] = torch.where(drop, zero, D * f)
     tol_G = torch.ones_like(G)
     tol_G[:Bm, :Bn] = f * tol_D + 5 * U32 * G[:Bm, :Bn].abs() + ulp(G[:Bm, :Bn], dtype)
-    dl = (D * l).sum(0)
-    tol_dl = sum_tol(D * l, tol_D * l.abs() + U32 * (D * l).abs(), block_acc(Bm), dim=0)
+    Dl = torch.where(drop, zero, D * l)
+    dl = Dl.sum(0)
+    tol_dl = sum_tol(Dl, tol_D * l.abs() + U32 * Dl.abs(), block_acc(Bm), dim=0)
     rscale = inv * dl / zsq
     alpha = float(torch.exp(c["temp"].double()))
     cscale = inv * alpha / (ymax * torch.sqrt(zsq))
@@ -294,6 +303,33 @@ def check_grad_labels(c, mode, dtype, G_buf, rscale, cscale, scalars):
     return out
 
 
+NONFINITE_MUTANTS = ("mask_by_multiply", "saturating_store", "colsum_skips_nonfinite")      # (tests/test_nonfinite_cpu.py)
+
+
+def dropped(c, mode):
+    """the entries that take no part under `mode`: the repeats of a column's speech under mask, none under positive"""
+    return c["same"] & ~c["pos"] if mode == "mask" else torch.zeros_like(c["same"])
+
+
+def store(v, dtype, mutant=None):
+    """q(), the round-to-nearest store of an fp32 value.  mutant saturating_store: a convert that clamps to the type's largest
+    finite value (NaN stays NaN)"""
+    if mutant == "saturating_store" and dtype != F32:
+        big = torch.finfo(dtype).max
+        v = torch.where(torch.isnan(v), v, v.clamp(-big, big))
+    return q(v, dtype)
+
+
+def summed(terms, drop, mutant=None):
+    """the terms a column or row sum adds up: a dropped entry is selected out (never multiplied by its zero coefficient).
+    mutants: mask_by_multiply leaves the product 0 * l in the sum, colsum_skips_nonfinite adds `isfinite(t) ? t : 0`"""
+    if mutant not in ("mask_by_multiply", "masked_entry_leaks_into_sums"):
+        terms = torch.where(drop, torch.zeros(()), terms)
+    if mutant == "colsum_skips_nonfinite":
+        terms = torch.where(torch.isfinite(terms), terms, torch.zeros(()))
+    return terms
+
+
 def emul_D(c, mode, hw=0, mutant=None):
     rl, cl = lse_inputs(c, mode)
     l, same, pos = c["logits"], c["same"], c["pos"]
@@ -315,20 +351,22 @@ def emul_D(c, mode, hw=0, mutant=None):
     return torch.where(same & ~pos, torch.zeros(()), d)
 
 
-def emul_grad_labels(c, mode, dtype, hw=0, mutant=None):
+def emul_grad_labels_parts(c, mode, dtype, hw=0, mutant=None):
+    """clip_grad_labels_kernel and the scalars kernel behind it: G (with its sentinel row), rscale, cscale, the per-column pairs
+    colpart [Bn][2] = (loss share, inv_norm sum_i D l) and scalars"""
     Bm, Bn, col0 = c["Bm"], c["Bn"], c["col0"]
     l, ysq, zsq = c["logits"], c["ysq"], c["zsq"]
     rl, cl = lse_inputs(c, mode)
     inv = torch.tensor(c["inv_norm"], dtype=F32)
     d = emul_D(c, mode, hw, mutant)
-    dG = d
-    if mutant == "masked_entry_leaks_into_sums":       # G itself is masked, the sums behind rscale and dtemp are not
-        dG = torch.where(c["same"] & ~c["pos"], torch.zeros(()), d)
+    drop = dropped(c, mode)
     ymax = torch.sqrt(ysq.max())
     G = torch.full((Bm + 2, pad64(Bn)), SENT)
     G[:Bm + 1] = 0.0
-    G[:Bm, :Bn] = q(dG * (ymax / torch.sqrt(ysq))[:, None], dtype)
-    dl = (d * l).sum(0) * inv
+    coef = d * (ymax / torch.sqrt(ysq))[:, None]
+    # (masked_entry_leaks_into_sums: G itself is masked, the sums behind rscale and dtemp are not)
+    G[:Bm, :Bn] = store(coef if mutant == "mask_by_multiply" else torch.where(drop, torch.zeros(()), coef), dtype, mutant)
+    dl = summed(d * l, drop, mutant).sum(0) * inv
     jj = torch.arange(Bn)
     if mode == "positive":
         n = c["counts"][col0:col0 + Bn].float()
@@ -339,7 +377,12 @@ def emul_grad_labels(c, mode, dtype, hw=0, mutant=None):
         pb = l[col0 + jj, jj]
     cp0 = (rl[col0 + jj] - pb) + (cl - pb)
     scal = torch.stack([(cp0.double().sum() * float(inv)).float(), dl.double().sum().float()])
-    return G, dl / zsq, inv * _exp(c["temp"], hw) / (ymax * torch.sqrt(zsq)), scal
+    return dict(G=G, rscale=dl / zsq, cscale=inv * _exp(c["temp"], hw) / (ymax * torch.sqrt(zsq)), colpart=torch.stack([cp0, dl], 1), scalars=scal)
+
+
+def emul_grad_labels(c, mode, dtype, hw=0, mutant=None):
+    r = emul_grad_labels_parts(c, mode, dtype, hw, mutant)
+    return r["G"], r["rscale"], r["cscale"], r["scalars"]
 
 
 # ---- sda_clip_grad_y_labels
@@ -351,12 +394,14 @@ def grad_y_labels_ref(c, mode, dtype):
     fz = (math.sqrt(float(c["zsq_all"].double().max())) / torch.sqrt(c["zsq"].double()))[:, None]
     i, ok = gy_rows(c)
     Gy = torch.zeros(Bn + 1, i.numel(), dtype=F64)
-    Gy[:Bn] = torch.where(ok[None, :], (D * fz.t())[i].t(), torch.zeros((), dtype=F64))
+    drop, zero = dropped(c, mode), torch.zeros((), dtype=F64)          # (selected out, never 0 * l or 0 * fz)
+    Gy[:Bn] = torch.where(ok[None, :], torch.where(drop, zero, D * fz.t())[i].t(), zero)
     tol = torch.ones_like(Gy)
     tol[:Bn] = torch.where(ok[None, :], (tol_D * fz.t())[i].t(), torch.ones((), dtype=F64)) + 5 * U32 * Gy[:Bn].abs() + ulp(Gy[:Bn], dtype)
     nparts = (Bn + 63) // 64
-    part = torch.stack([(D * l)[:, t * 64:(t + 1) * 64].sum(1) for t in range(nparts)])
-    tol_part = torch.stack([sum_tol((D * l)[:, t * 64:(t + 1) * 64], (tol_D * l.abs() + U32 * (D * l).abs())[:, t * 64:(t + 1) * 64], 7, dim=1)
+    Dl = torch.where(drop, zero, D * l)
+    part = torch.stack([Dl[:, t * 64:(t + 1) * 64].sum(1) for t in range(nparts)])
+    tol_part = torch.stack([sum_tol(Dl[:, t * 64:(t + 1) * 64], (tol_D * l.abs() + U32 * Dl.abs())[:, t * 64:(t + 1) * 64], 7, dim=1)
                             for t in range(nparts)])
     return dict(Gy=Gy, tol_Gy=tol, ok=ok, i=i, part=part, tol_part=tol_part)
 
@@ -379,16 +424,19 @@ def emul_grad_y_labels(c, mode, dtype, hw=0, mutant=None):
     Bm, Bn = c["Bm"], c["Bn"]
     l = c["logits"]
     d = emul_D(c, mode, hw, mutant)
+    drop = dropped(c, mode)
     zmax = torch.sqrt(c["zsq_all"].max())
     i, ok = gy_rows(c)
     Gy = torch.full((Bn + 2, i.numel()), SENT)
-    vals = (d * (zmax / torch.sqrt(c["zsq"]))[None, :])[i].t()
-    Gy[:Bn] = q(torch.where(ok[None, :], vals, torch.zeros(())), dtype)
+    coef = d * (zmax / torch.sqrt(c["zsq"]))[None, :]
+    vals = (coef if mutant == "mask_by_multiply" else torch.where(drop, torch.zeros(()), coef))[i].t()
+    Gy[:Bn] = store(torch.where(ok[None, :], vals, torch.zeros(())), dtype, mutant)
     Gy[Bn] = 0.0
     nparts = (Bn + 63) // 64
     part = torch.full((nparts + 1, Bm), SENT)
+    dl = summed(d * l, drop, mutant)
     for t in range(nparts):
-        part[t] = (d * l)[:, t * 64:(t + 1) * 64].sum(1)
+        part[t] = dl[:, t * 64:(t + 1) * 64].sum(1)
     return Gy, part
 
 

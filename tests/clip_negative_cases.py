@@ -29,6 +29,7 @@ import torch
 
 from tests.sa_loss_cases import (C_D, C_LOGIT, C_LSE, DTYPES, F32, F64, FTZ, HW, SENT, U32, _exp, _gen, _log, block_acc, exact, host,  # noqa: F401
                                  lse_tol, pad64, q, ratio, sum_tol, ulp, ulp32)
+from tests.clip_label_cases import store
 
 I32 = torch.int32
 C_MERGE = 10.0
@@ -106,7 +107,18 @@ def check_neg_stats(c, mlog_buf, col_lse_buf):
     return out
 
 
-def emul_merge(a, b, hw=0):
+NONFINITE_MUTANTS = ("merge_with_fmaxf", "saturating_store", "colsum_skips_nonfinite", "window_row_outside_times_zero")
+
+
+def emul_merge(a, b, hw=0, mutant=None):
+    """logaddexp(a, b) as the kernel writes it; torch.maximum hands a NaN on.  mutant merge_with_fmaxf: the hand-written form on
+    fmaxf / fminf, M + log(1 + exp(min - M)) — both drop a NaN operand, and a NaN paired lse comes out as the negatives' lse + log 2.
+    (fmaxf under the kernel's own two exponentials would still meet the NaN in exp(a - M): the two-sided form is the one that
+    swallows.)"""
+    if mutant == "merge_with_fmaxf":
+        skip = lambda x, other: torch.where(torch.isnan(x), other, x)
+        M, m = torch.maximum(skip(a, b), skip(b, a)), torch.minimum(skip(a, b), skip(b, a))
+        return M + _log(1.0 + _exp(m - M, hw))
     M = torch.maximum(a, b)
     return M + _log(_exp(a - M, hw) + _exp(b - M, hw))
 
@@ -120,7 +132,7 @@ def emul_neg_stats(c, hw=0, mutant=None):
         return m, c["col_lse"].clone()
     if mutant == "merge_replaces_col_lse":
         return m, nl
-    return m, emul_merge(c["col_lse"], nl, hw)
+    return m, emul_merge(c["col_lse"], nl, hw, mutant)
 
 
 def neg_D(c):
@@ -169,7 +181,9 @@ def check_neg_grad(c, dtype, G_buf, cscale_n, rscale, scalars):
             "scalars[0] loss untouched": exact(float(host(scalars)[0]) == float(c["scalars_in"][0]))}
 
 
-def emul_neg_grad(c, dtype, hw=0, mutant=None):
+def emul_neg_grad(c, dtype, hw=0, mutant=None, colpart=False):
+    """(G^n with its sentinel row, cscale_n, rscale, scalars); colpart: also the per-column shares the kernel leaves for the
+    scalars kernel behind it"""
     Bn, N = c["Bn"], c["N"]
     m, cl, wsq, zsq = c["mlog"], c["col_lse_merged"], c["wsq"], c["zsq"]
     inv = torch.tensor(c["inv_norm"], dtype=F32)
@@ -181,13 +195,17 @@ def emul_neg_grad(c, dtype, hw=0, mutant=None):
     nr = neg_rows(N)
     G = torch.full((nr + 1, pad64(Bn)), SENT)
     G[:nr] = 0.0
-    G[:N, :Bn] = q(d.t() * scale[:, None], dtype)
-    dl = (d * m).sum(1) * inv
+    G[:N, :Bn] = store(d.t() * scale[:, None], dtype, mutant)
+    dm = d * m
+    if mutant == "colsum_skips_nonfinite":
+        dm = torch.where(torch.isfinite(dm), dm, torch.zeros(()))
+    dl = dm.sum(1) * inv
     rscale = c["rscale_in"].clone() if mutant == "rscale_share_missing" else c["rscale_in"] + dl / zsq
     scal = c["scalars_in"].clone()
     if mutant != "dtemp_share_missing":
         scal[1] = (scal[1].double() + dl.double().sum()).float()
-    return G, inv * _exp(c["temp"], hw) / (wmax * torch.sqrt(zsq)), rscale, scal
+    out = G, inv * _exp(c["temp"], hw) / (wmax * torch.sqrt(zsq)), rscale, scal
+    return out + (dl,) if colpart else out
 
 
 def measure_constants(cases):
@@ -310,11 +328,33 @@ def check_dz_windows(c, dtype, out_buf):
 def emul_dz_windows(c, dtype, mutant=None):
     ref, _ = dz_windows_ref(c, dtype, shift={"window_row_early": -1, "window_row_late": 1}.get(mutant, 0),
                             n_used=c["N"] // 32 * 32 if mutant == "last_partial_kstep_dropped" else None)
+    if mutant == "window_row_outside_times_zero":
+        # the K-steps past N re-read a window against zero coefficients — here not the last candidate's own (whose elements are in
+        # the sum anyway) but the one a row later (earlier at the table's end): 0 * table row outside every term of the sum
+        s, L, T = int(c["starts"][-1]), c["table"].shape[0], c["T"]
+        s = s + 1 if s + 1 + T <= L else s - 1
+        ref[c["data_rows"]] += (0.0 * c["table"][s:s + T].double()).repeat(c["Bn"], 1)
     out = torch.full((ref.shape[0] + 1, c["Fp"]), SENT)
     out[:-1] = q(ref.float(), dtype)
     if mutant == "pad_rows_written":
         out[:ROW_PAD] += 1.0
     return out
+
+
+# ---- sda_sim_gemm_windows (and sda_sim_gemm on the same windows cut out), for tests/nonfinite_cases.py
+def sim_case(M, N, T, Fp, dtype):
+    """X (M, T * Fp) and a table whose windows start every third row from row 2 on: with T = 4 a row 2 + 3 n + 3 lies in the
+    windows of candidates n and n + 1, the two rows in front of it in candidate n's alone, rows 0 and 1 and the last four in none"""
+    g = _gen(523 * M + 29 * N + T)
+    starts = (2 + 3 * np.arange(N)).astype(np.int32)
+    L = int(starts[-1]) + T + 4
+    return dict(name=f"sim M={M} N={N} T={T}", M=M, N=N, T=T, Fp=Fp, K=T * Fp, X=q(torch.randn(M, T * Fp, generator=g), dtype),
+                table=q(torch.randn(L, Fp, generator=g), dtype), starts=starts)
+
+
+def sim_windows_ref(c):
+    """float64 S[i][n] = <X_i, window n>, (M, N)"""
+    return c["X"].double() @ windows_of(c["table"], c["starts"], c["T"]).double().t()
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -24,7 +24,7 @@ import math
 
 import torch
 
-from tests.clip_label_cases import I32, LABEL_PATTERNS, LABEL_SHAPES, MODES, labels_of  # noqa: F401
+from tests.clip_label_cases import I32, LABEL_PATTERNS, LABEL_SHAPES, MODES, labels_of, store  # noqa: F401
 from tests.sa_loss_cases import (C_LOGIT, CLIP_REGIMES, DTYPES, F32, F64, FTZ, GY_LAYOUT, HW, SENT, U32, _exp, clip_case,  # noqa: F401
                                  exact, gy_layout, host, pad64, q, ratio, sum_tol, ulp, ulp32)
 from tests.elementwise_cases import _nudge
@@ -260,6 +260,14 @@ def emul_terms(a, bias, z, hw=0, mutant=None):
     return torch.where(z != 0, sp, zero), torch.where(z != 0, d, zero)
 
 
+NONFINITE_MUTANTS = ("masked_times_zero", "saturating_store", "colsum_skips_nonfinite")      # (tests/test_nonfinite_cpu.py)
+
+
+def _sum_terms(t, mutant=None):
+    """the terms of a partial sum.  mutant colsum_skips_nonfinite: `isfinite(t) ? t : 0`"""
+    return torch.where(torch.isfinite(t), t, torch.zeros(())) if mutant == "colsum_skips_nonfinite" else t
+
+
 def _tile_colsum(v):
     """(rows <= 64, Bn) -> (Bn,): wave w adds rows w, w + 4, ... in order; the four wave sums are added in wave order"""
     n, Bn = v.shape
@@ -289,7 +297,7 @@ def emul_pairs(c, mode, dtype, hw=0, mutant=None):
     G = torch.full((Bm + 2, pad64(Bn)), SENT)
     G[:Bm + 1] = 0.0
     g = d * (ymax / torch.sqrt(c["ysq"]))[:, None]
-    G[:Bm, :Bn] = q(g if mutant == "masked_times_zero" else torch.where(z != 0, g, torch.zeros(())), dtype)
+    G[:Bm, :Bn] = store(g if mutant == "masked_times_zero" else torch.where(z != 0, g, torch.zeros(())), dtype, mutant)
     if mutant == "zero_row_unwritten":
         G[Bm] = SENT
     if mutant == "pad_column_unwritten" and pad64(Bn) > Bn:
@@ -307,6 +315,7 @@ def emul_pairs(c, mode, dtype, hw=0, mutant=None):
     da = d * ((a + c["bias"]) if mutant == "sum_Dl_not_Da" else a)
     if mutant != "masked_times_zero":
         da = torch.where(z != 0, da, torch.zeros(()))        # (a dropped pair's a never enters a sum)
+    sp, da, d = _sum_terms(sp, mutant), _sum_terms(da, mutant), _sum_terms(d, mutant)
     for p in range(nparts):
         r = slice(p * 64, (p + 1) * 64)
         part[p] = torch.stack([_tile_colsum(sp[r]), _tile_colsum(da[r]), _tile_colsum(d[r])], -1)
@@ -342,8 +351,10 @@ def emul_grad_y(c, mode, dtype, hw=0, mutant=None):
     zmax = torch.sqrt(c["zsq_all"].max())
     i, ok = gy_rows(c)
     Gy = torch.full((Bn + 2, i.numel()), SENT)
-    vals = (d * (zmax / torch.sqrt(c["zsq"]))[None, :])[i].t()
-    Gy[:Bn] = q(torch.where(ok[None, :], vals, torch.zeros(())), dtype)
+    g = d * (zmax / torch.sqrt(c["zsq"]))[None, :]
+    # (a dropped pair's coefficient is selected, never 0 * zmax / |Z_j|: a non-finite norm stays out of it)
+    vals = (g if mutant == "masked_times_zero" else torch.where(z != 0, g, torch.zeros(())))[i].t()
+    Gy[:Bn] = store(torch.where(ok[None, :], vals, torch.zeros(())), dtype, mutant)
     Gy[Bn] = 0.0
     if mutant == "zero_row_unwritten":
         Gy[Bn] = SENT
@@ -354,6 +365,7 @@ def emul_grad_y(c, mode, dtype, hw=0, mutant=None):
     da = d * ((a + c["bias"]) if mutant == "sum_Dl_not_Da" else a)
     if mutant != "masked_times_zero":
         da = torch.where(z != 0, da, torch.zeros(()))        # (a dropped pair's a never enters a sum)
+    da = _sum_terms(da, mutant)
     for p in range(nparts):
         part[p] = da[:, p * 64:(p + 1) * 64].sum(1)
     return Gy, part

@@ -1,6 +1,12 @@
 """CPU proof that the propagation and containment checks of tests/nonfinite_cases.py have teeth: each of the four ways a kernel
 swallows or leaks a non-finite value, planted into the plain-torch restatement of the construct, is caught, and every unmutated
-restatement passes.  Without this file tests/test_nonfinite_gpu.py proves nothing."""
+restatement passes.  Without this file tests/test_nonfinite_gpu.py proves nothing.
+
+The same for the cases of tests/test_nonfinite_losses_gpu.py (the labelled, sigmoid and negatives loss kernels): every case it
+runs reaches an output and leaves something for the bit check, and the mutants planted in the case modules' emul_* functions —
+a masked lse whose maximum skips NaN, a label mask applied by multiplication, a logaddexp on fmaxf / fminf, a saturating 16-bit
+store, a partial sum that skips non-finite terms, a windows product that reads a row outside the window against a zero
+coefficient — fail N.check where their restatements pass."""
 import pytest
 import torch
 
@@ -80,12 +86,105 @@ def test_positions_name_every_edge():
                                                                "memory row 55, below the boundary at 56"}     # row 56 is a pad row
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# the loss kernels behind labels, SigmoidLoss and extra negatives: the cases tests/test_nonfinite_losses_gpu.py runs
+# ---------------------------------------------------------------------------------------------------------------
+def loss_case_groups():
+    """(id, maker) of every group of cases the GPU tests run"""
+    for b in N.LOSS_BLOCKS:
+        for p in N.LOSS_PATTERNS:
+            yield f"labels-{b}-{p}", lambda b=b, p=p: N.label_cases(*b, p)
+            yield f"sigmoid-{b}-{p}", lambda b=b, p=p: N.sigmoid_cases(*b, p)
+    for s in N.NEG_SHAPES:
+        yield f"negatives-{s}", lambda s=s: N.neg_cases(*s)
+    for s in N.DZ_SHAPES:
+        for p in N.DZ_PATTERNS:
+            yield f"dz_windows-{s}-{p}", lambda s=s, p=p: N.dz_cases(*s, p)
+    for s in N.SIM_SHAPES:
+        yield f"sim_gemm-{s}", lambda s=s: N.sim_cases(*s)
+
+
+GROUPS = dict(loss_case_groups())
+
+
+@pytest.mark.parametrize("group", GROUPS)
+def test_no_loss_case_passes_vacuously(group):
+    """for every case used on the GPU: every site reaches an output with at least one poison value (a dropped pair's site: with
+    none, by the contract), and unless the maths couples the whole output (said per site) at least one element stays finite and
+    independent of the poison, so the bit check has something to hold"""
+    n = 0
+    for case in GROUPS[group]():
+        o, ref = case["operands"], case["ref"]
+        ref_clean = ref(o)
+        assert case["unreached"] <= {s[0] for s in case["sites"]} and case["coupled"] <= {s[0] for s in case["sites"]}
+        if case["finite_clean"]:
+            assert all(bool(torch.isfinite(t).all()) for t in ref_clean.values()), (case["kernel"], case["what"])
+        for site, key, index in case["sites"]:
+            reached = False
+            for vname, v in case["values"].items():
+                r = ref(dict(o, **{key: N.poisoned(o[key], index, v)}))
+                reached = reached or any(bool((torch.isfinite(t) != torch.isfinite(ref_clean[k])).any()) for k, t in r.items())
+                independent = any(bool((torch.isfinite(t) & (t == ref_clean[k])).any()) for k, t in r.items())
+                assert independent or site in case["coupled"], (case["kernel"], case["what"], site, vname, "nothing is left for the bit check")
+                n += 1
+            assert reached == (site not in case["unreached"]), (case["kernel"], case["what"], site, "reached" if reached else "no value reaches an output")
+    assert n > 0
+
+
+# mutant -> (group of cases, kernels it is planted in, the check that has to catch it)
+LOSS_MUTANTS = {
+    "lse_max_skips_nan": ("labels-(15, 5, 10)-pair", {"clip_logits_stats_masked"}, "propagation"),
+    "mask_by_multiply": ("labels-(15, 5, 10)-pair", {"clip_grad_labels", "clip_grad_y_labels"}, "containment"),
+    "masked_times_zero": ("sigmoid-(15, 5, 10)-pair", {"sigmoid_grad_y", "sigmoid_pairs + sigmoid_finish"}, "containment"),
+    "merge_with_fmaxf": ("negatives-(2, 31)", {"clip_neg_stats"}, "propagation"),
+    "saturating_store": ("labels-(15, 5, 10)-pair", {"clip_grad_labels", "clip_grad_y_labels"}, "propagation"),
+    "saturating_store (SigmoidLoss)": ("sigmoid-(15, 5, 10)-pair", {"sigmoid_grad_y", "sigmoid_pairs + sigmoid_finish"}, "propagation"),
+    "saturating_store (negatives)": ("negatives-(2, 31)", {"clip_neg_grad"}, "propagation"),
+    "colsum_skips_nonfinite": ("labels-(15, 5, 10)-pair", {"clip_grad_labels", "clip_grad_y_labels"}, "propagation"),
+    "colsum_skips_nonfinite (SigmoidLoss)": ("sigmoid-(15, 5, 10)-pair", {"sigmoid_grad_y", "sigmoid_pairs + sigmoid_finish"}, "propagation"),
+    "colsum_skips_nonfinite (negatives)": ("negatives-(2, 31)", {"clip_neg_grad"}, "propagation"),
+    "window_row_outside_times_zero": ("dz_windows-(2, 31, 5)-overlap", {"clip_dz_windows"}, "containment"),
+}
+
+
+def loss_failures(case, mutant):
+    """{(site, value): {output: check -> message}} of one case with `mutant` standing in for its restatement"""
+    o, ref = case["operands"], case["ref"]
+    clean, ref_clean = ref(o, mutant), ref(o)
+    out = {}
+    for site, key, index in case["sites"]:
+        for vname, v in case["values"].items():
+            p = dict(o, **{key: N.poisoned(o[key], index, v)})
+            r, got = ref(p), ref(p, mutant)
+            bad = {k: res for k in r for res in [N.check(r[k], got[k], clean[k], ref_clean[k])] if res}
+            if bad:
+                out[(site, vname)] = bad
+    return out
+
+
+@pytest.mark.parametrize("mutant", LOSS_MUTANTS)
+def test_every_loss_mutant_is_caught_and_its_restatement_passes(mutant):
+    group, kernels, kind = LOSS_MUTANTS[mutant]
+    seen = set()
+    for case in GROUPS[group]():
+        if case["kernel"] not in kernels or (mutant.startswith("saturating") and case["dtype"] == torch.float32):
+            continue
+        if mutant in ("mask_by_multiply", "masked_times_zero") and case.get("mode") != "mask":
+            continue
+        assert loss_failures(case, None) == {}, (case["kernel"], case["what"])
+        bad = loss_failures(case, mutant.split(" (")[0])
+        kinds = {k for per_case in bad.values() for per_out in per_case.values() for k in per_out}
+        assert kind in kinds, (mutant, case["kernel"], case["what"], bad)
+        seen.add(case["kernel"])
+    assert seen == kernels, (mutant, seen)
+
+
 def test_the_exceptions_waive_no_more_than_they_say():
     """the data-gradient conv: pad channels only, and only in frames whose real channels are non-finite — a leak into another
     real channel of a poisoned frame, into a pad channel of another frame, or into a real channel's sum is still caught.
     wgrad_gemm: the other taps of a weight with a non-finite tap, nothing else."""
     k = "conv_gemm (data gradient)"
-    assert set(N.EXCEPTIONS) == {k, "wgrad_gemm"}
+    assert set(N.EXCEPTIONS) == {k, "wgrad_gemm", "sim_gemm"}
     B, C, Cp, T = 2, 3, 5, 4
     clean = torch.arange(B * Cp * T, dtype=torch.float32).reshape(B, Cp, T)
     ref = clean.clone()
@@ -131,3 +230,19 @@ def test_the_exceptions_waive_no_more_than_they_say():
         except AssertionError:
             res = "caught"
         assert res == want, (at, res)
+    # sim_gemm: the pad columns of a row whose last real column is non-finite, nothing else
+    s0, p0 = torch.ones(3, 4), torch.zeros(3, 2)
+    sref = s0.clone()
+    sref[1, 3] = N.NAN                                     # row 1's last real column
+    sref[2, 0] = N.INF                                     # row 2: a non-finite column that is not the last
+    for name, at, want in (("S" + N.PAD_COLS, (1, 0), "passes"), ("S" + N.PAD_COLS, (2, 1), "caught"), ("S" + N.PAD_COLS, (0, 1), "caught"),
+                           ("S", (0, 3), "caught"), ("S", (1, 0), "caught")):
+        got = {"S": sref.clone(), "S" + N.PAD_COLS: p0.clone()}
+        got[name][at] = N.NAN
+        try:
+            N.check_all("sim_gemm", {"S": sref, "S" + N.PAD_COLS: p0}, got, {"S": s0, "S" + N.PAD_COLS: p0}, {"S": s0, "S" + N.PAD_COLS: p0})
+            res = "passes"
+        except AssertionError as e:
+            assert "containment" in str(e) and "propagation" not in str(e)
+            res = "caught"
+        assert res == want, (name, at, res)

@@ -21,7 +21,15 @@ Kernel -> test:
   clip_logits_stats, clip_grad, clip_grad_y + clip_grad_y_finish, clip_dz         test_clip_*
   sa_softmax_backward, sa_weights_backward                                        test_sa_softmax_backward_and_weights_backward
   (forward, same file's maxima) sa_weights_forward, clip_merge_rows               test_sa_weights_forward, test_clip_merge_rows
-  eval-mode BrainEncoder (Z and dX), retrieve                                     test_eval_mode_encoder_..., test_retrieve_..."""
+  eval-mode BrainEncoder (Z and dX), retrieve                                     test_eval_mode_encoder_..., test_retrieve_...
+and in tests/test_nonfinite_losses_gpu.py (the losses with labels, the sigmoid loss, extra negatives):
+  clip_logits_stats_masked (rows and columns kernels), clip_grad_labels,          test_labelled_clip_kernels
+    clip_grad_y_labels: positive and mask mode, fp32 / bf16 / fp16 G and Gy
+  sigmoid_grad_y (labels, both modes), sigmoid_pairs + sigmoid_finish (mask)      test_sigmoid_loss_kernels
+    (positive mode of the pair: tests/test_sigmoid_loss_gpu.py::test_nonfinite_inputs_propagate)
+  clip_neg_stats, clip_neg_grad (with clip_neg_dtemp behind it)                   test_negatives_scalar_kernels
+  clip_dz_windows                                                                 test_clip_dz_windows
+  sim_gemm_windows, sim_gemm (256 x 256 tiles; kernel's K split and one slice)    test_sim_gemm_windows_and_sim_gemm"""
 import pytest
 import torch
 
@@ -62,23 +70,7 @@ def run_cases(kernel, run, ref, operands, sites, dtype, typed=(), values=None):
     every poison value.  `typed` operands live in `dtype` on the device: the reference sees them as rounded (a 1e5 handed to an
     fp16 operand IS an inf)."""
     seen = lambda o: {k: (E.q(v, dtype) if k in typed else v) for k, v in o.items()}
-    clean, ref_clean = run(operands), ref(seen(operands))
-    for k, r in ref_clean.items():
-        assert bool(torch.isfinite(r).all()), (kernel, k, "the unpoisoned reference is not finite")
-    N.check_all(kernel, ref_clean, clean, clean, ref_clean, f"{name(dtype)} unpoisoned")
-    values = N.poisons(dtype) if values is None else values
-    n = 0
-    for what, key, index in sites:
-        reached = False
-        for vname, v in values.items():
-            o = dict(operands)
-            o[key] = N.poisoned(operands[key], index, v)
-            r = ref(seen(o))
-            reached = reached or any(not bool(torch.isfinite(t).all()) for t in r.values())
-            N.check_all(kernel, r, run(o), clean, ref_clean, f"{name(dtype)}, {vname} in {key} at {what}")
-            n += 1
-        assert reached, (kernel, what, key, "no poison value at this site reaches an output")      # (a gate of +-inf alone does not)
-    return n
+    return N.run_cases(kernel, run, ref, operands, sites, N.poisons(dtype) if values is None else values, name(dtype), seen=seen)
 
 
 def sites_of(key, pos, index_of):
